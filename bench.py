@@ -12,8 +12,12 @@ per GPU. --config kitti_stereo (configs[2]): a step is P 1241x376 stereo pairs: 
 Frame::ComputeStereoMatches. --config local_ba (configs[3]): a step is one batch of W = 20 LocalBundleAdjustmentNavState windows.
 Weak scaling: every rank owns the same amount of work; the path shards by stream / pair / window with no data-path collective, the
 only RCCL traffic is the (units, time) reduction at the end. Inputs are resident in HBM before the timed region (local_ba: host
-buffers, as its caller is the LocalMapping thread). Rank 0 prints ONE JSON line. `roofline` / `roofline_pose` are measured live with
-HIP events on the launching stream; `cpu_baseline` times the CPU oracle (a port: the reference cannot be built here) on the host.
+buffers, as its caller is the LocalMapping thread). Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the line (`roofline`, `cpu_baseline` null). --full adds everything else:
+`roofline` / `roofline_pose` measured live with HIP events on the launching stream, `cpu_baseline` timing the CPU oracle (a port: the
+reference cannot be built here) on the host, and the context passes after the timed region. --dump-outputs DIR writes the last timed
+step's results as .npy files; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -68,6 +72,43 @@ def load_traffic_table():
         except Exception:
             pass
     return None
+
+
+DUMP_MAX_BYTES = 64 << 20                     # --dump-outputs: all files together
+DUMP_SAMPLE_BYTES = 4 << 20                   # an output larger than this keeps a fixed sample of its rows
+DUMP_SAMPLE_ROWS = 64
+
+
+def sample_rows(n, k=DUMP_SAMPLE_ROWS, seed=0):
+    """Fixed, seeded choice of k of n rows (sorted), the same in every run and build."""
+    return np.arange(n) if n <= k else np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: what the timed path handed its caller in the last step, one DIR/<name>.npy per array. float32 sources and integers
+    that float32 holds exactly stay float32, everything else becomes float64. An array of more than DUMP_SAMPLE_BYTES keeps the rows
+    sample_rows() picks, whose indices are written to DIR/<name>_rows.npy."""
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        exact32 = a.dtype == np.float32 or (a.dtype.kind in "biu" and (a.size == 0 or np.abs(a.astype(np.int64)).max() < (1 << 24)))
+        a = a.astype(np.float32 if exact32 else np.float64)
+        if a.nbytes > DUMP_SAMPLE_BYTES and a.ndim >= 2:
+            rows = sample_rows(a.shape[0])
+            out[name + "_rows"] = rows.astype(np.float64)
+            a = a[rows]
+        out[name] = np.ascontiguousarray(a)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_MAX_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def kernel_events(args):
+    """HIP events around the roofline kernels (or every kernel) inside the timed region: --full only, as the figures they feed."""
+    return args.full and not args.no_kernel_events
 
 
 def _gen_stream(args):
@@ -207,7 +248,7 @@ def run_tracking(args, cfg, rank, dev_index, dev, world):
     # live feed: the same frames in page-locked host memory, uploaded by the tracker's copy stream inside the step (viorb_tracker_inputs.h_images)
     if world > 1:
         args.no_host_input_pass = True                                   # the context passes after the timed region are N = 1 only
-    need_host = args.host_input or not args.no_host_input_pass       # 8 x S x frame bytes of page-locked memory: only when a pass reads it
+    need_host = args.host_input or (args.full and not args.no_host_input_pass)       # 8 x S x frame bytes of page-locked memory: only when a pass reads it
     frames_host = torch.from_numpy(np.stack([s["frames"] for s in streams], 1)).pin_memory() if need_host else None
     feed = {"frames": frames_host if args.host_input else frames}
 
@@ -226,7 +267,7 @@ def run_tracking(args, cfg, rank, dev_index, dev, world):
             tr.step(frames[j], imu[j], t_frames[j], pose_true[j])
 
     single_stream = None
-    if world == 1 and rank == 0 and not args.no_host_input_pass:
+    if args.full and world == 1 and rank == 0 and not args.no_host_input_pass:
         # north_star's single-stream figure, BEFORE the timed region (a single stream leaves the GPU nearly idle; measured after the saturating
         # batch the same sequence reads ~17 % lower): ONE stream per step (stream 0 of this run), device-resident frames, through
         # the same C++ tracker — (a) ORB extract + match only (extraction, undistortion, grid, IMU prediction, SearchByProjection with its
@@ -274,7 +315,7 @@ def run_tracking(args, cfg, rank, dev_index, dev, world):
     L = viorb_amd.lib()
     timed = None if args.all_kernel_events else b"k_fast_cells,k_pose_opt_vi"
     L.viorb_profile_select(timed)
-    L.viorb_profile_reset(); L.viorb_profile_enable(0 if args.no_kernel_events else 1)
+    L.viorb_profile_reset(); L.viorb_profile_enable(1 if kernel_events(args) else 0)
     tr.host_stats(reset=True)
     if world > 1:
         dist.barrier()
@@ -290,9 +331,11 @@ def run_tracking(args, cfg, rank, dev_index, dev, world):
     elapsed = time.perf_counter() - t0
     L.viorb_profile_enable(0)
     hs = tr.host_stats()
+    if args.dump_outputs and rank == 0:                 # the last timed step's results, before any pass after the timed region moves the trackers on
+        dump_outputs(args.dump_outputs, tr.results())
     # ---- the other input mode, outside the timed region: HBM-resident frames when the line was measured on the live feed and vice versa
     other = {}
-    if not args.no_host_input_pass:
+    if args.full and not args.no_host_input_pass:
         feed["frames"] = frames if args.host_input else frames_host
         n_other = max(8, min(args.steps, 48))
         for _ in range(4):
@@ -431,15 +474,16 @@ def run_tracking(args, cfg, rank, dev_index, dev, world):
             out["config"]["single_stream"] = single_stream
         if not (res["status"] == 0).all():
             raise SystemExit("a stream reported a capacity / status error: %s" % res["status"])
-        if args.config == "synth720p" and world == 1 and not args.no_host_input_pass and S < 128:
+        if args.full and args.config == "synth720p" and world == 1 and not args.no_host_input_pass and S < 128:
             # BASELINE configs[4] gives every GPU 8 of the 64 streams: a latency-bound batch that any number of GPUs runs at the same per-GPU
             # rate. What ONE GPU does with this workload when it has enough streams to fill it (the same 8 scenes replicated, own state each):
             import copy
             a2 = copy.copy(args); a2.distinct = distinct; a2.streams = 128; a2.steps = 24; a2.warmup = 6; a2.no_host_input_pass = True; a2.no_cpu_baseline = True; a2.no_kernel_events = True
+            a2.dump_outputs = None
             sat = run_tracking(a2, cfg, rank, dev_index, dev, world)
             out["config"]["saturated_frames_per_s"] = round(sat["units"] / sat["elapsed"], 1)
             out["config"]["saturated_note"] = "the same 1280x720 / 1500-feature sequence at 128 streams per GPU per step (the 8 scenes replicated, own tracker state each), 24 steps after the timed region"
-        if not args.no_cpu_baseline and world == 1:          # the CPU baseline is timed on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:          # the CPU baseline is timed on rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline_tracking(base, W_IMG, H_IMG, NFEAT, 200 if args.config == "euroc" else 60, 20 if args.config == "euroc" else 8, lens)
     out["metric"] = "frames/sec ORB extract+match+pose-opt, EuRoC 752x480, 1/2/4/8 GPUs" if args.config == "euroc" else \
         "frames/sec ORB extract+match+pose-opt, synthetic 1280x720 / 1500 features, batched streams"
@@ -461,7 +505,7 @@ def run_dropin(args, cfg, rank, dev_index, dev, world):
     tr = DropinTracker(s["cam"], s["gw"], cfg["w"], cfg["h"], cfg["nfeat"], dist_coef=dist)
     mci = np.eye(12) * 1e3
     tr.bootstrap(s["frames"][0], s["pose_true"][0], s["t"][0], s["ns_true"][0], mci)
-    states = []
+    states, last = [], {}
 
     def run_step(k):
         j = k % N_FRAMES
@@ -470,6 +514,7 @@ def run_dropin(args, cfg, rank, dev_index, dev, world):
         else:
             r = tr.step(s["frames"][j], s["imu"][j], s["t"][j], s["pose_true"][j], map_updated=(j == 1 and k > 1))
         states.append(r["state"])
+        last["r"] = r
     k = 1
     for _ in range(args.warmup):
         run_step(k); k += 1
@@ -480,6 +525,8 @@ def run_dropin(args, cfg, rank, dev_index, dev, world):
         run_step(k); k += 1
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["r"])
     out = dict(units=args.steps, elapsed=elapsed)
     if rank == 0:
         per_call = {name: {"ms_per_call": round(v[0] / v[1] * 1e3, 4), "calls_per_frame": round(v[1] / args.steps, 2)} for name, v in sorted(tr.times.items())}
@@ -494,7 +541,7 @@ def run_dropin(args, cfg, rank, dev_index, dev, world):
                          "frames_per_s_inside_the_calls": round(args.steps / in_calls, 1),
                          "tracked_frames": int(sum(1 for x in states if x == 0)), "frames": len(states)}
         out["roofline"] = None
-        if not args.no_cpu_baseline and world == 1:          # the CPU baseline is timed on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:          # the CPU baseline is timed on rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline_tracking([s], cfg["w"], cfg["h"], cfg["nfeat"], 100, 10, dist)
     out["metric"] = "frames/sec ORB extract+match+pose-opt, EuRoC 752x480, single stream through the host-buffer drop-ins"
     out["unit"] = "frames/s"; out["dtype"] = "u8"
@@ -527,7 +574,7 @@ def run_stereo(args, cfg, rank, dev_index, dev, world):
     torch.cuda.synchronize()
     L = lib()
     L.viorb_profile_select(None if args.all_kernel_events else b"k_fast_cells,k_stereo_match")
-    L.viorb_profile_reset(); L.viorb_profile_enable(0 if args.no_kernel_events else 1)
+    L.viorb_profile_reset(); L.viorb_profile_enable(1 if kernel_events(args) else 0)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -540,6 +587,8 @@ def run_stereo(args, cfg, rank, dev_index, dev, world):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     L.viorb_profile_enable(0)
+    if args.dump_outputs and rank == 0:                 # Frame::mvuRight / mvDepth and the match count of every pair
+        dump_outputs(args.dump_outputs, {"u_right": u.cpu().numpy(), "depth": d.cpu().numpy(), "n_stereo": n.cpu().numpy()})
     names = C.create_string_buffer(4096); ms = (C.c_double * 64)(); calls = (C.c_int * 64)(); k = C.c_int()
     L.viorb_profile_read(names, 4096, ms, calls, 64, C.byref(k))
     prof = {nm_: (ms[i], calls[i]) for i, nm_ in enumerate(names.value.decode().split("\n")[:k.value])}
@@ -563,7 +612,7 @@ def run_stereo(args, cfg, rank, dev_index, dev, world):
                                      "(one batched handle) + Frame::ComputeStereoMatches (row buckets, Hamming, 11x11 SAD, sub-pixel, median rejection)",
                          "baseline_config": cfg["baseline_config"], "pairs_per_gpu_per_step": Pn, "pairs_per_step": Pn * world,
                          "mean_stereo_matches_per_pair": round(float(n.float().mean().item()), 1), "keypoint_capacity": ex.cap}
-        if not args.no_cpu_baseline and world == 1:          # the CPU baseline is timed on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:          # the CPU baseline is timed on rank 0 at N = 1 only
             from oracle import binding as ora
             exo = [ora.Extractor(NFEAT, 1.2, 8, 20, 7), ora.Extractor(NFEAT, 1.2, 8, 20, 7)]
             times = []
@@ -614,7 +663,7 @@ def run_local_ba(args, cfg, rank, dev_index, dev, world):
     for _ in range(max(1, args.warmup)):
         LocalBundleAdjustmentNavStateBatch(batch[:max(fl, 2)], max_in_flight=fl)
     L = viorb_amd.lib()
-    L.viorb_profile_select(None); L.viorb_profile_reset(); L.viorb_profile_enable(0 if args.no_kernel_events else 1)
+    L.viorb_profile_select(None); L.viorb_profile_reset(); L.viorb_profile_enable(1 if kernel_events(args) else 0)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -626,6 +675,18 @@ def run_local_ba(args, cfg, rank, dev_index, dev, world):
         dist.barrier()
     elapsed = time.perf_counter() - t0
     L.viorb_profile_enable(0)
+    if args.dump_outputs and rank == 0:
+        # every window's chi2 and iteration counts; the solved key frames, points and erase flags of a fixed sample of the windows,
+        # concatenated in window order (window_* give each sampled window's id and row counts)
+        wins = sample_rows(nwin, 16)                    # 16 windows of at most 3000 points / 24000 edges stay under DUMP_SAMPLE_BYTES per array
+        dump_outputs(args.dump_outputs, {
+            "chi2_first": [r["chi2_first"] for r in res], "chi2_final": [r["chi2_final"] for r in res],
+            "its_first": [r["its_first"] for r in res], "its_second": [r["its_second"] for r in res],
+            "window_ids": wins, "window_kfs_rows": [len(res[i]["kfs"]) for i in wins], "window_points_rows": [len(res[i]["points"]) for i in wins],
+            "window_erase_rows": [len(res[i]["erase"]) for i in wins],
+            "kfs": np.concatenate([np.asarray(res[i]["kfs"], np.float64) for i in wins]),
+            "points": np.concatenate([np.asarray(res[i]["points"], np.float64) for i in wins]),
+            "erase": np.concatenate([np.asarray(res[i]["erase"]).ravel() for i in wins])})
     out = dict(units=nwin * args.steps, elapsed=elapsed, metric="windows/sec LocalBundleAdjustmentNavState, 10-20-key-frame windows, 1000-3000 points", unit="windows/s", dtype="f64")
     if rank == 0:
         names = C.create_string_buffer(4096); ms = (C.c_double * 64)(); calls = (C.c_int * 64)(); n = C.c_int()
@@ -645,25 +706,27 @@ def run_local_ba(args, cfg, rank, dev_index, dev, world):
                      "cholesky": nred ** 3 / 3 + 2 * nred ** 2, "backsub": 36.0 * ne + 30.0 * npt}
             return parts
         its = np.array([r["its_first"] + r["its_second"] for r in res], np.float64)
-        parts = [trial_flop(batch[i]) for i in range(nwin)]
-        flop_step = float(sum(sum(pp.values()) * its[i] for i, pp in enumerate(parts)))
-        chol_step = float(sum(pp["cholesky"] * its[i] for i, pp in enumerate(parts)))
-        ach = flop_step * args.steps / elapsed / 1e12
-        kern = {k: round(v[0] / args.steps, 3) for k, v in sorted(prof.items())}
-        roof = {"bound": "fp64_vector", "kernel": "viorb_local_ba_navstate_batch (whole lock-step solve)", "achieved": round(ach, 3), "peak": FP64_VECTOR_PEAK_TFLOPS,
-                "unit": "TFLOP/s", "frac": round(ach / FP64_VECTOR_PEAK_TFLOPS, 5), "traffic": None,
-                "flop_per_step": int(flop_step), "kernel_ms_per_step": kern,
-                "note": "FP64 FLOP of every LM iteration of every window of a step (model above; rejected trials not counted) over the step's wall time, host "
-                        "preparation and transfers included; v_mfma_f64_16x16x4_f64 runs at the FP64 vector rate on gfx950, so one peak serves both. "
-                        "MFMA-busy counters: profiles/r04_pmc_mfma_local_ba.txt"}
-        if prof.get("k_bab_chol_solve", (0, 0))[1]:
-            tms = prof["k_bab_chol_solve"][0]
-            roof["cholesky"] = {"kernel": "k_bab_chol_solve", "ms_per_step": round(tms / args.steps, 3), "launches_per_step": prof["k_bab_chol_solve"][1] // args.steps,
-                                "achieved": round(chol_step * args.steps / (tms * 1e-3) / 1e12, 3), "unit": "TFLOP/s",
-                                "frac": round(chol_step * args.steps / (tms * 1e-3) / 1e12 / FP64_VECTOR_PEAK_TFLOPS, 5),
-                                "note": "n^3/3 + 2 n^2 of every iterating window over the kernel's HIP-event time (a launch factors the whole group; the MFMA trailing updates "
-                                        "and panel solves are the FLOPs, the diagonal blocks' dependent 1/sqrt chains are the time)"}
-        out["roofline"] = roof
+        out["roofline"] = None
+        if args.full:
+            parts = [trial_flop(batch[i]) for i in range(nwin)]
+            flop_step = float(sum(sum(pp.values()) * its[i] for i, pp in enumerate(parts)))
+            chol_step = float(sum(pp["cholesky"] * its[i] for i, pp in enumerate(parts)))
+            ach = flop_step * args.steps / elapsed / 1e12
+            kern = {k: round(v[0] / args.steps, 3) for k, v in sorted(prof.items())}
+            roof = {"bound": "fp64_vector", "kernel": "viorb_local_ba_navstate_batch (whole lock-step solve)", "achieved": round(ach, 3), "peak": FP64_VECTOR_PEAK_TFLOPS,
+                    "unit": "TFLOP/s", "frac": round(ach / FP64_VECTOR_PEAK_TFLOPS, 5), "traffic": None,
+                    "flop_per_step": int(flop_step), "kernel_ms_per_step": kern,
+                    "note": "FP64 FLOP of every LM iteration of every window of a step (model above; rejected trials not counted) over the step's wall time, host "
+                            "preparation and transfers included; v_mfma_f64_16x16x4_f64 runs at the FP64 vector rate on gfx950, so one peak serves both. "
+                            "MFMA-busy counters: profiles/r04_pmc_mfma_local_ba.txt"}
+            if prof.get("k_bab_chol_solve", (0, 0))[1]:
+                tms = prof["k_bab_chol_solve"][0]
+                roof["cholesky"] = {"kernel": "k_bab_chol_solve", "ms_per_step": round(tms / args.steps, 3), "launches_per_step": prof["k_bab_chol_solve"][1] // args.steps,
+                                    "achieved": round(chol_step * args.steps / (tms * 1e-3) / 1e12, 3), "unit": "TFLOP/s",
+                                    "frac": round(chol_step * args.steps / (tms * 1e-3) / 1e12 / FP64_VECTOR_PEAK_TFLOPS, 5),
+                                    "note": "n^3/3 + 2 n^2 of every iterating window over the kernel's HIP-event time (a launch factors the whole group; the MFMA trailing updates "
+                                            "and panel solves are the FLOPs, the diagonal blocks' dependent 1/sqrt chains are the time)"}
+            out["roofline"] = roof
         Ws = [int(q["n_local"]) for q in probs]; nps = [len(q["points"]) for q in probs]; nes = [len(q["edge_idx"]) for q in probs]
         out["config"] = {"workload": "synthetic EuRoC-shaped local windows, %d DISTINCT per step (W = %d..%d key frames of 12 unknowns + 4 fixed, %d..%d points seen by 3-8 key "
                                      "frames, %d..%d mono edges, IMU + bias factors); LocalBundleAdjustmentNavState = optimize(5), chi2 gate, optimize(10); "
@@ -672,7 +735,7 @@ def run_local_ba(args, cfg, rank, dev_index, dev, world):
                          "baseline_config": cfg["baseline_config"], "windows_per_gpu_per_step": nwin, "distinct_windows": n_distinct, "windows_in_flight": fl,
                          "lm_iterations_mean_min_max": [round(float(its.mean()), 2), int(its.min()), int(its.max())],
                          "final_chi2_window0": round(float(res[0]["chi2_final"]), 3)}
-        if not args.no_cpu_baseline and world == 1:          # the CPU baseline is timed on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:          # the CPU baseline is timed on rank 0 at N = 1 only
             from oracle import binding as ora               # checker, used as the CPU baseline only
             times, ti = [], 0
             t_all = time.perf_counter()
@@ -709,7 +772,13 @@ def main():
     ap.add_argument("--timeline", default=None, help="dev aid (with --all-kernel-events): write start / end / duration (us) of the last kernels to this file")
     ap.add_argument("--timeline-rows", type=int, default=120)
     ap.add_argument("--all-kernel-events", action="store_true", help="time every kernel of the step, not only the roofline kernels (costs ~5 %% of the step)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: per-kernel HIP events and rooflines, the CPU baseline, and the "
+                    "context passes after the timed region (other input mode, single stream, pinhole camera, saturated synth720p)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path returned in its last step to DIR/<name>.npy "
+                    "(float32 / float64, at most 64 MB; larger outputs keep a fixed sample of their rows)")
     args = ap.parse_args()
+    if (args.all_kernel_events or args.timeline) and not args.full:
+        ap.error("--all-kernel-events and --timeline belong to the per-kernel figures of --full")
     cfg = CONFIGS[args.config]
     if args.streams is None:
         args.streams = cfg["streams"]
@@ -736,7 +805,7 @@ def main():
         n_own = min(args.streams, (args.distinct or 256) if full else 4)
         seeds = stream_seeds(rank, n_own)
         units, elapsed = reduce_throughput(args.streams * args.steps, 1.0 + 0.5 * rank)
-        host_pass = args.host_input or (world == 1 and not args.no_host_input_pass)
+        host_pass = args.host_input or (args.full and world == 1 and not args.no_host_input_pass)
         mine = {"rank": rank, "local_rank": local_rank, "seeds": seeds if not full else [seeds[0], seeds[-1], len(seeds)], "gen_procs": generator_procs(n_own, args.gen_procs),
                 "host_bytes": host_memory_estimate(cfg, args.streams, min(args.streams, args.distinct or 256), world, host_pass) if args.config in ("euroc", "synth720p") else None}
         owned = [None] * world
@@ -751,7 +820,7 @@ def main():
         if world > 1:
             dist.barrier(); dist.destroy_process_group()
         return
-    pinhole_pass = args.config == "euroc" and world == 1 and not args.no_distortion and not args.no_host_input_pass
+    pinhole_pass = args.full and args.config == "euroc" and world == 1 and not args.no_distortion and not args.no_host_input_pass
     args.pregenerated = {}
     if args.config in ("euroc", "synth720p"):
         # Every rank's synthetic streams are generated HERE, before the process group (RCCL initialises the device eagerly with device_id=)
@@ -781,7 +850,7 @@ def main():
         import copy
         a2 = copy.copy(args)
         a2.no_distortion = a2.no_cpu_baseline = a2.no_host_input_pass = a2.no_kernel_events = True
-        a2.steps = max(8, min(args.steps, 64)); a2.timeline = None
+        a2.steps = max(8, min(args.steps, 64)); a2.timeline = None; a2.dump_outputs = None
         r2 = run_tracking(a2, cfg, rank, dev_index, dev, 1)
         r["config"]["pinhole_camera_frames_per_s"] = round(r2["units"] / r2["elapsed"], 1)
         r["config"]["pinhole_camera_note"] = "same scenes and step without the lens (--no-distortion, the round-1/2 workload), %d steps after the timed region" % a2.steps

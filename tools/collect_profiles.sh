@@ -8,9 +8,9 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 500 python3 $R/bench.py > $OUT/${TAG}_bench256.json 2> $OUT/${TAG}_bench256.err
+timeout -k 10 500 python3 $R/bench.py --full > $OUT/${TAG}_bench256.json 2> $OUT/${TAG}_bench256.err
 echo "bench done"; date
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_stats -- python3 $R/bench.py --no-cpu-baseline --no-extra-passes > $OUT/${TAG}_bench256_under_rocprof.json 2> /dev/null
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_stats -- python3 $R/bench.py --full --no-cpu-baseline --no-extra-passes > $OUT/${TAG}_bench256_under_rocprof.json 2> /dev/null
 find $OUT/${TAG}_stats -name "*kernel_stats.csv" -exec cp {} $OUT/${TAG}_bench256_kernel_stats.csv \;
 echo "kernel stats done"; date
 for C in FETCH_SIZE WRITE_SIZE; do
@@ -28,10 +28,10 @@ python3 $R/tools/extract_times.py 256 > $OUT/${TAG}_extract_times.txt 2>&1
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_bf -- python3 $R/tools/bruteforce_bench.py 256 1000 50 > $OUT/${TAG}_bruteforce.txt 2>&1
 find $OUT/${TAG}_bf -name "*kernel_stats.csv" -exec cp {} $OUT/${TAG}_bruteforce_kernel_stats.csv \;
 python3 $R/tools/make_traffic_table.py $TAG > /dev/null 2>&1
-timeout -k 10 300 python3 $R/bench.py --host-input --no-cpu-baseline > $OUT/${TAG}_bench_host_input.json 2> $OUT/${TAG}_bench_host_input.err
-for c in synth720p kitti_stereo local_ba dropin; do echo "bench $c"; timeout -k 10 400 python3 $R/bench.py --config $c > $OUT/${TAG}_bench_$c.json 2> $OUT/${TAG}_bench_$c.err; done
+timeout -k 10 300 python3 $R/bench.py --full --host-input --no-cpu-baseline > $OUT/${TAG}_bench_host_input.json 2> $OUT/${TAG}_bench_host_input.err
+for c in synth720p kitti_stereo local_ba dropin; do echo "bench $c"; timeout -k 10 400 python3 $R/bench.py --full --config $c > $OUT/${TAG}_bench_$c.json 2> $OUT/${TAG}_bench_$c.err; done
 rm -rf $OUT/${TAG}_stats $OUT/${TAG}_bf $OUT/${TAG}_pmc_FETCH_SIZE $OUT/${TAG}_pmc_WRITE_SIZE $OUT/${TAG}_pmc_sq $OUT/${TAG}_pmc_step_FETCH_SIZE $OUT/${TAG}_pmc_step_WRITE_SIZE
-timeout -k 10 300 python3 $R/bench.py --no-cpu-baseline --steps 60 --all-kernel-events --timeline $OUT/${TAG}_timeline.txt > $OUT/${TAG}_bench256_all_events.json 2> /dev/null
+timeout -k 10 300 python3 $R/bench.py --full --no-cpu-baseline --steps 60 --all-kernel-events --timeline $OUT/${TAG}_timeline.txt > $OUT/${TAG}_bench256_all_events.json 2> /dev/null
 bash $R/tools/lba_profile.sh $TAG > /dev/null 2>&1
 bash $R/tools/pmc_step.sh $TAG 1024 > /dev/null 2>&1
 ls $OUT | grep ${TAG}

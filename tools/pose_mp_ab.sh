@@ -8,7 +8,7 @@ for c in $cfgs; do
 done
 for c in $cfgs; do
   n=$(echo $c | tr ',' '_')
-  VIORB_POSE_MP=$c timeout -k 10 300 python bench.py --steps 60 --warmup 10 --no-cpu-baseline --no-extra-passes > $out/bench_$n.json 2> $out/bench_$n.err
+  VIORB_POSE_MP=$c timeout -k 10 300 python bench.py --full --steps 60 --warmup 10 --no-cpu-baseline --no-extra-passes > $out/bench_$n.json 2> $out/bench_$n.err
   python - "$out/bench_$n.json" "$c" <<'PY'
 import json,sys
 try:
