@@ -651,6 +651,100 @@ int viorb_fuse(const viorb_keypoint* kps, const uint8_t* desc, const float* urig
                const float* pts_f, const uint8_t* pts_valid, const uint8_t* pts_desc, int npts, float th, int32_t* best_idx,
                int* nfused);
 
+/* ---- Map-point creation (reference src/LocalMapping.cc:1227-1483, src/MapPoint.cc:249-314, :337-378, src/KeyFrame.cc:952-968) -----
+ * The piece of LocalMapping::Run between SearchForTriangulation and Fuse: triangulate and vet the matched pairs, and give every new
+ * (or changed) map point its representative descriptor, normal and depth range, in the pts_f[p][8] / pts_desc[p][32] layout that
+ * viorb_fuse, viorb_frontend_fuse_device and the local-point search read. The map graph itself (new MapPoint, AddObservation,
+ * covisibility, culling) stays with the caller, who passes flat snapshots. One camera per call: every key frame of a map shares
+ * fx fy cx cy mb mbf and the scale tables, as the reference's single Tracking object gives them. */
+typedef struct viorb_mapping_camera {
+    float   fx, fy, cx, cy;               /* KeyFrame::fx.. (invfx = 1.0f / fx as Frame computes it) */
+    float   mb, mbf;                      /* KeyFrame::mb, mbf (unused when every uright < 0) */
+    float   scale_factor;                 /* mfScaleFactor: ratioFactor = 1.5f * scale_factor (src/LocalMapping.cc:1262) */
+    int32_t nlevels;                      /* mnScaleLevels, 1..16 */
+    float   scale_factors[16];            /* mvScaleFactors */
+    float   level_sigma2[16];             /* mvLevelSigma2 */
+} viorb_mapping_camera;
+
+/* reason[i1]: which statement of src/LocalMapping.cc:1319-1464 ended the pair */
+#define VIORB_TRI_ACCEPT     0   /* "Triangulation is succesfull" (:1466) */
+#define VIORB_TRI_NO_POINT   1   /* no stereo and very low parallax (:1376), x3D[3] == 0 (:1362), UnprojectStereo of a depth <= 0 */
+#define VIORB_TRI_BEHIND_1   2   /* z1 <= 0 (:1382) */
+#define VIORB_TRI_BEHIND_2   3   /* z2 <= 0 (:1386) */
+#define VIORB_TRI_REPROJ_1   4   /* reprojection error in the current key frame: > 5.991 sigma^2 mono, > 7.8 sigma^2 stereo (:1401-1417) */
+#define VIORB_TRI_REPROJ_2   5   /* the same in the second key frame (:1424-1443) */
+#define VIORB_TRI_SCALE      6   /* dist == 0 or scale consistency (:1452-1464) */
+#define VIORB_TRI_NO_PAIR  255   /* match12[i1] < 0 (or i1 >= n1): nothing to do */
+
+/* The per-pair loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:1312-1464) without the map writes: for every i1 with
+ * i2 = match12[i1] >= 0, accept[i1] (1 = a map point would be created), Pw[i1][3] = x3D (zeros when no point exists) and reason[i1].
+ * k = mvKeysUn, keys_dist_xy = mvKeys[i].pt (KeyFrame::UnprojectStereo reads the DISTORTED key points), uright = mvuRight (< 0
+ * mono), depth = mvDepth, pose12 = Rcw(9) tcw(3), Ow = GetCameraCenter(). Key frame 1 is mpCurrentKeyFrame. The second view's stereo
+ * reprojection uses the current key frame's mbf, as :1439 does. Device form: key frame 1 arrays [b][cap], key frame 2 arrays
+ * [b][cap], poses [b][12], centres [b][3], match12 / accept / reason [b][cap], Pw [b][cap][3]; only enqueues. */
+int viorb_triangulate_pairs_device(const viorb_mapping_camera* cam, const viorb_keypoint* k1, const float* keys_dist_xy1,
+                                   const float* uright1, const float* depth1, const int32_t* n1, const float* pose12_1,
+                                   const float* Ow1, const viorb_keypoint* k2, const float* keys_dist_xy2, const float* uright2,
+                                   const float* depth2, const float* pose12_2, const float* Ow2, const int32_t* match12, int cap,
+                                   int batch, uint8_t* accept, float* Pw, uint8_t* reason, void* stream);
+int viorb_triangulate_pairs(const viorb_mapping_camera* cam, const viorb_keypoint* k1, const float* keys_dist_xy1,
+                            const float* uright1, const float* depth1, int n1, const float pose12_1[12], const float Ow1[3],
+                            const viorb_keypoint* k2, const float* keys_dist_xy2, const float* uright2, const float* depth2, int n2,
+                            const float pose12_2[12], const float Ow2[3], const int32_t* match12, uint8_t* accept, float* Pw,
+                            uint8_t* reason);
+
+/* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:249-314) and MapPoint::UpdateNormalAndDepth (:337-378) for npts points.
+ * Observations of point p are obs_kf / obs_feat [obs_start[p] .. obs_start[p + 1]) (key-frame index, feature index) IN THE ORDER THE
+ * CALLER ITERATES mObservations: the reference walks a std::map<KeyFrame*, size_t>, i.e. in pointer order, and the first row with
+ * the smallest median wins, so the order is part of the input (bad key frames are left out by the caller, :273-274). Key-frame
+ * tables: kf_row_base[k] = the row of key frame k's feature 0 in desc_rows[pool_rows][32] (mDescriptors) and octave_rows[pool_rows]
+ * (mvKeysUn[i].octave), kf_Ow[k][3] = GetCameraCenter(). ref_obs[p] = which observation (0-based within the point) is mpRefKF's.
+ * Out: pts_desc[p][32] = mDescriptor, best_obs[p] = BestIdx, pts_f[p][8] = mWorldPos3 mNormalVector3 mfMinDistance mfMaxDistance.
+ * A point without observations keeps a zero descriptor, best_obs -1 and pts_f = Pw and zeros. No workspace is needed for any
+ * observation count. Device form: only enqueues. */
+int viorb_map_points_update_device(const int32_t* obs_start, const int32_t* obs_kf, const int32_t* obs_feat, const int32_t* ref_obs,
+                                   const float* Pw, int npts, const int64_t* kf_row_base, const float* kf_Ow, int nkf,
+                                   const uint8_t* desc_rows, const int32_t* octave_rows, int64_t pool_rows,
+                                   const viorb_mapping_camera* cam, uint8_t* pts_desc, int32_t* best_obs, float* pts_f, void* stream);
+int viorb_map_points_update(const int32_t* obs_start, const int32_t* obs_kf, const int32_t* obs_feat, const int32_t* ref_obs,
+                            const float* Pw, int npts, const int64_t* kf_row_base, const float* kf_Ow, int nkf,
+                            const uint8_t* desc_rows, const int32_t* octave_rows, int64_t pool_rows,
+                            const viorb_mapping_camera* cam, uint8_t* pts_desc, int32_t* best_obs, float* pts_f);
+
+/* LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:1227-1483) for `batch` streams in one call: per stream the current key frame
+ * (arrays [b][cap], as viorb_search_for_triangulation_device takes key frame 1) and J neighbour slots (arrays [b][j][cap], counts,
+ * poses, centres, F12 [b][j][9], median_depth2 [b][j] = pKF2->ComputeSceneMedianDepth(2), kf2_first [b][j] != 0 when the
+ * neighbour's KeyFrame* orders before the current key frame's in mObservations). For j = j_begin .. j_end - 1, with j < n_neigh[b]:
+ * the baseline test (:1272-1289; `monocular` = mbMonocular), SearchForTriangulation with ORBmatcher(0.6, false) and bOnlyStereo =
+ * false reading the working has_point1, the per-pair vetting above, and the append of the accepted pairs in ascending i1 after those
+ * of earlier neighbours (the reference's nnew order): new_idx[b][p][3] = (i1, j, i2), new_pts_f[b][p][8], new_desc[b][p][32] (the
+ * two-observation ComputeDistinctiveDescriptors: the first in map order, chosen by kf2_first) and has_point1[i1] = 1 for the next
+ * neighbour. has_point1, n_new[b] and status[b] are in / out (zero n_new and status before the first call of a key frame), so
+ * neighbours 0..5 in one call equal 0..2 then 3..5 — the caller's place for the CheckNewKeyFrames() exit. A stream whose points would
+ * exceed pcap gets status VIORB_ERR_CAPACITY: its first pcap points are written, n_new[b] = pcap, and its later neighbours are
+ * skipped. workspace: viorb_create_new_map_points_workspace_bytes(cap, batch) bytes of device memory, 256-byte aligned. Only
+ * enqueues on `stream`: no allocation, no host synchronisation. */
+size_t viorb_create_new_map_points_workspace_bytes(int cap, int batch);
+int viorb_create_new_map_points_device(const viorb_mapping_camera* cam, int monocular, const viorb_keypoint* k1, const uint8_t* d1,
+                                       uint8_t* has_point1, const float* uright1, const float* depth1, const float* keys_dist_xy1,
+                                       const int32_t* node1, const int32_t* n1, const float* pose12_1, const float* Ow1,
+                                       const viorb_keypoint* k2, const uint8_t* d2, const uint8_t* has_point2, const float* uright2,
+                                       const float* depth2, const float* keys_dist_xy2, const int32_t* node2, const int32_t* n2,
+                                       const float* pose12_2, const float* Ow2, const float* F12, const float* median_depth2,
+                                       const uint8_t* kf2_first, const int32_t* n_neigh, int J, int j_begin, int j_end, int cap,
+                                       int batch, int pcap, int32_t* new_idx, float* new_pts_f, uint8_t* new_desc, int32_t* n_new,
+                                       int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+/* Host-buffer drop-in for one key frame and its J neighbours: every array of key frame 1 has n1 <= cap entries, every neighbour array
+ * is [j][cap] with n2[j] <= cap entries used, poses [j][12], centres [j][3], F12 [j][9]. has_point1 is updated in place. Returns
+ * VIORB_ERR_CAPACITY (after writing the first pcap points, *n_new = pcap) when more than pcap points are created. */
+int viorb_create_new_map_points(const viorb_mapping_camera* cam, int monocular, const viorb_keypoint* k1, const uint8_t* d1,
+                                uint8_t* has_point1, const float* uright1, const float* depth1, const float* keys_dist_xy1,
+                                const int32_t* node1, int n1, const float pose12_1[12], const float Ow1[3], const viorb_keypoint* k2,
+                                const uint8_t* d2, const uint8_t* has_point2, const float* uright2, const float* depth2,
+                                const float* keys_dist_xy2, const int32_t* node2, const int32_t* n2, const float* pose12_2,
+                                const float* Ow2, const float* F12, const float* median_depth2, const uint8_t* kf2_first, int J,
+                                int cap, int pcap, int32_t* new_idx, float* new_pts_f, uint8_t* new_desc, int* n_new);
+
 /* Host-only test hooks (no GPU needed; used by the CPU test-suite to compare product host code with
  * the oracle): the flat-array formulation of DistributeOctTree that the device kernel mirrors
  * (keys packed x | y<<12 | score<<24, border-relative), and the scalar math shared with the kernels. */
@@ -668,6 +762,15 @@ void viorb_debug_prior_edge(const double* pvr22, const double* bias22, const dou
 void viorb_debug_update_ns(const double* ns22, const double* preint142, const double* gw, const double* cam16,
                            double* out22, float* pose12);
 void viorb_debug_preint_step(double* small60, const double* omega, const double* acc, double dt);
+/* mapping_core.h (the per-pair and per-point functions of the map-point creation kernels) compiled for the host: one pair of
+ * viorb_triangulate_pairs (key1 / key2 = u v uright depth u_dist v_dist, octaves apart; returns the reason code), and one point of
+ * viorb_map_points_update (same arguments as the host form, for point p alone). */
+int viorb_debug_triangulate_pair(const viorb_mapping_camera* cam, const float* pose12_1, const float* Ow1, const float* pose12_2,
+                                 const float* Ow2, const float* key1_6, int octave1, const float* key2_6, int octave2, float* Pw3);
+int viorb_debug_map_point_update(const int32_t* obs_start, const int32_t* obs_kf, const int32_t* obs_feat, const int32_t* ref_obs,
+                                 const float* Pw, int p, const int64_t* kf_row_base, const float* kf_Ow, int nkf,
+                                 const uint8_t* desc_rows, const int32_t* octave_rows, int64_t pool_rows,
+                                 const viorb_mapping_camera* cam, uint8_t* pts_desc32, int32_t* best_obs, float* pts_f8);
 
 #ifdef __cplusplus
 }

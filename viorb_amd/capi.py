@@ -55,6 +55,12 @@ class VocabularyFlat(C.Structure):
                 ("child_ids", C.c_void_p), ("word_id", C.c_void_p), ("desc", C.c_void_p), ("weight", C.c_void_p)]
 
 
+class MappingCamera(C.Structure):
+    """viorb_mapping_camera (include/viorb.h)."""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("mb", C.c_float), ("mbf", C.c_float),
+                ("scale_factor", C.c_float), ("nlevels", C.c_int32), ("scale_factors", C.c_float * 16), ("level_sigma2", C.c_float * 16)]
+
+
 class TrackerConfig(C.Structure):
     """viorb_tracker_config (include/viorb.h)."""
     _fields_ = [("extractor", ExtractorParams), ("frontend", FrontendConfig), ("width", C.c_int32), ("height", C.c_int32), ("batch", C.c_int32),
@@ -180,6 +186,15 @@ SIGNATURES = {
     "viorb_debug_octree_host": (i32, [vp, i32, i32, i32, i32, vp, i32, PP(i32)]),
     "viorb_debug_fast_atan2": (f32, [f32, f32]),
     "viorb_debug_sincos": (None, [f32, PP(f32), PP(f32)]),
+    "viorb_triangulate_pairs_device": (i32, [vp] * 15 + [i32, i32] + [vp] * 4),
+    "viorb_triangulate_pairs": (i32, [vp] * 5 + [i32] + [vp] * 6 + [i32] + [vp] * 6),
+    "viorb_map_points_update_device": (i32, [vp] * 5 + [i32, vp, vp, i32, vp, vp, C.c_int64] + [vp] * 5),
+    "viorb_map_points_update": (i32, [vp] * 5 + [i32, vp, vp, i32, vp, vp, C.c_int64] + [vp] * 4),
+    "viorb_create_new_map_points_workspace_bytes": (sz, [i32, i32]),
+    "viorb_create_new_map_points_device": (i32, [vp, i32] + [vp] * 24 + [i32] * 6 + [vp] * 6 + [sz, vp]),
+    "viorb_create_new_map_points": (i32, [vp, i32] + [vp] * 7 + [i32] + [vp] * 15 + [i32] * 3 + [vp] * 3 + [PP(i32)]),
+    "viorb_debug_triangulate_pair": (i32, [vp] * 6 + [i32, vp, i32, vp]),
+    "viorb_debug_map_point_update": (i32, [vp] * 5 + [i32, vp, vp, i32, vp, vp, C.c_int64] + [vp] * 4),
 }
 
 _lib = None

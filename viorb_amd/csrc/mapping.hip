@@ -1,0 +1,562 @@
+// viorb_amd/csrc/mapping.hip — map-point creation on the device: the piece of LocalMapping::Run between SearchForTriangulation and
+// Fuse (reference src/LocalMapping.cc:1227-1483, src/MapPoint.cc:249-314, :337-378, src/KeyFrame.cc:952-968).
+//   k_triangulate_pairs   one lane per (i1, match12[i1]) pair: rays / parallax, linear triangulation (4 x 4 one-sided Jacobi SVD in
+//                         registers) or UnprojectStereo, depth, reprojection and scale gates (mapping_core.h)
+//   k_map_point_update    one wavefront per point: representative descriptor (median of Hamming rows), normal, depth range
+//   k_stage_neighbour     baseline test + gather of neighbour j's [b][j][cap] slices into the [b][cap] form the search kernel reads
+//   k_append_new_points   ordered compaction of the accepted pairs, has_point1 update, pts_f / descriptor of the two-view points
+// viorb_create_new_map_points_device chains stage -> k_search_triangulation -> triangulate -> append for every neighbour on one
+// stream: no host round trip between neighbours although neighbour j + 1 depends on the points neighbour j created.
+#include <algorithm>
+#include <vector>
+#include "viorb_common.h"
+#include "mapping_core.h"
+
+namespace viorb {
+
+MAP_HD MapCam make_cam(const viorb_mapping_camera& c) {
+    MapCam m;
+    m.fx = c.fx; m.fy = c.fy; m.cx = c.cx; m.cy = c.cy; m.invfx = 1.0f / c.fx; m.invfy = 1.0f / c.fy; m.mb = c.mb; m.mbf = c.mbf;
+    m.ratio_factor = 1.5f * c.scale_factor; m.nlevels = c.nlevels;
+    for (int i = 0; i < 16; i++) { const int l = i < c.nlevels ? i : c.nlevels - 1; m.sf[i] = c.scale_factors[l]; m.sigma2[i] = c.level_sigma2[l]; }
+    return m;
+}
+
+// Key frame 2's arrays are [row2][cap] with row2 = b * stride2 + off2: (1, 0) for the stand-alone entry, (J, j) inside the chain.
+struct TriPairsArgs {
+    MapCam c;
+    const viorb_keypoint *k1, *k2; const float *xy1, *xy2, *ur1, *ur2, *dep1, *dep2, *T1, *T2, *Ow1, *Ow2; const int* n1; const int* match12;
+    uint8_t *accept, *reason; float* Pw;
+    int cap, stride2, off2;
+};
+
+__device__ __forceinline__ MapKey load_key(const viorb_keypoint* k, const float* xy, const float* ur, const float* dep, size_t i) {
+    MapKey m; const viorb_keypoint kp = k[i];
+    m.u = kp.x; m.v = kp.y; m.octave = kp.octave; m.ur = ur[i]; m.depth = dep[i]; m.ud = xy[2 * i]; m.vd = xy[2 * i + 1];
+    return m;
+}
+
+__global__ __launch_bounds__(256) void k_triangulate_pairs(TriPairsArgs A) {
+    const int b = blockIdx.y, i1 = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i1 >= A.cap) return;
+    const size_t o1 = (size_t)b * A.cap, row2 = (size_t)b * A.stride2 + A.off2, o2 = row2 * A.cap;
+    const int i2 = i1 < min(A.n1[b], A.cap) ? A.match12[o1 + i1] : -1;
+    int reason = TRI_NO_PAIR;
+    float X[3] = {0.0f, 0.0f, 0.0f};
+    if (i2 >= 0 && i2 < A.cap) {
+        const MapKey k1 = load_key(A.k1, A.xy1, A.ur1, A.dep1, o1 + i1), k2 = load_key(A.k2, A.xy2, A.ur2, A.dep2, o2 + i2);
+        reason = triangulate_pair(A.c, A.T1 + (size_t)b * 12, A.Ow1 + (size_t)b * 3, A.T2 + row2 * 12, A.Ow2 + row2 * 3, k1, k2, X);
+    }
+    A.accept[o1 + i1] = reason == TRI_ACCEPT; A.reason[o1 + i1] = (uint8_t)reason;
+    float* P = A.Pw + (o1 + i1) * 3; P[0] = X[0]; P[1] = X[1]; P[2] = X[2];
+}
+
+// ---------------------------------------------------------------------------------------------
+// MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth. One 64-lane block per point. N <= 64: the descriptors and the
+// symmetric N x N distance matrix sit in LDS (u16, read column-wise so that lane i walks its own row without bank conflicts) and
+// lane i finds the element of rank m of row i by counting (binary search on the value: the smallest v with #{d <= v} > m).
+// N > 64: rows one after the other, the 64 lanes fill a 257-bin histogram of the row's distances and a wave prefix sum finds the
+// same rank. The first row with the smallest median wins (strict <).
+struct MpuArgs {
+    const int *obs_start, *obs_kf, *obs_feat, *ref_obs; const float* Pw; const long long* kf_row_base; const float* kf_Ow; int nkf;
+    const uint8_t* desc_rows; const int* octave_rows; long long pool_rows;
+    float sf[16]; int nlevels;
+    uint8_t* pts_desc; int* best_obs; float* pts_f;
+};
+
+__device__ __forceinline__ long long obs_row(const MpuArgs& A, int e) {
+    const int kf = A.obs_kf[e];
+    if (kf < 0 || kf >= A.nkf) return -1;
+    const long long r = A.kf_row_base[kf] + A.obs_feat[e];
+    return (r >= 0 && r < A.pool_rows) ? r : -1;
+}
+
+__global__ __launch_bounds__(64) void k_map_point_update(MpuArgs A) {
+    __shared__ uint32_t s_desc[64][8];
+    __shared__ unsigned short s_d[64 * 64];
+    __shared__ int s_hist[320];
+    __shared__ int s_med;
+    const int p = blockIdx.x, lane = threadIdx.x;
+    const int e0 = A.obs_start[p], N = A.obs_start[p + 1] - e0;
+    uint8_t* out_desc = A.pts_desc + (size_t)p * 32;
+    float* out_f = A.pts_f + (size_t)p * 8;
+    const float* Pw = A.Pw + (size_t)p * 3;
+    if (N <= 0) {
+        if (lane < 8) reinterpret_cast<uint32_t*>(out_desc)[lane] = 0;
+        if (lane < 8) out_f[lane] = lane < 3 ? Pw[lane] : 0.0f;
+        if (lane == 0) A.best_obs[p] = -1;
+        return;
+    }
+    int best = 0;
+    if (N <= 64) {
+        uint32_t mine[8];
+        const long long r = lane < N ? obs_row(A, e0 + lane) : -1;
+#pragma unroll
+        for (int k = 0; k < 8; k++) { mine[k] = r >= 0 ? reinterpret_cast<const uint32_t*>(A.desc_rows + r * 32)[k] : 0u; s_desc[lane][k] = mine[k]; }
+        __syncthreads();
+        for (int j = 0; j < N; j++) {
+            uint32_t o[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) o[k] = s_desc[j][k];
+            s_d[j * 64 + lane] = (unsigned short)hamming256(mine, o);       // d[lane][j] stored at [j][lane]
+        }
+        const int m = (int)(0.5 * (N - 1));
+        int lo = 0, hi = 256;                                                // smallest v with #{j : d[lane][j] <= v} > m
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            int cnt = 0;
+            for (int j = 0; j < N; j++) cnt += s_d[j * 64 + lane] <= mid;
+            if (cnt > m) hi = mid; else lo = mid + 1;
+        }
+        int key = lane < N ? (lo << 8) | lane : 0x7fffffff;                   // min over (median, row): the first smallest median
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) key = min(key, __shfl_xor(key, s));
+        best = key & 255;
+    } else {
+        const int m = (int)(0.5 * (N - 1));
+        int bestMedian = 0x7fffffff;
+        for (int i = 0; i < N; i++) {
+            for (int k = lane; k < 320; k += 64) s_hist[k] = 0;
+            __syncthreads();
+            const long long ri = obs_row(A, e0 + i);
+            uint32_t di[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) di[k] = ri >= 0 ? reinterpret_cast<const uint32_t*>(A.desc_rows + ri * 32)[k] : 0u;
+            for (int j = lane; j < N; j += 64) {
+                const long long rj = obs_row(A, e0 + j);
+                uint32_t dj[8];
+#pragma unroll
+                for (int k = 0; k < 8; k++) dj[k] = rj >= 0 ? reinterpret_cast<const uint32_t*>(A.desc_rows + rj * 32)[k] : 0u;
+                atomicAdd(&s_hist[hamming256(di, dj)], 1);
+            }
+            __syncthreads();
+            int h[5], sum = 0;                                               // lane owns bins 5 * lane .. 5 * lane + 4
+#pragma unroll
+            for (int k = 0; k < 5; k++) { h[k] = s_hist[5 * lane + k]; sum += h[k]; }
+            int incl = sum;
+#pragma unroll
+            for (int s = 1; s < 64; s <<= 1) { const int t = __shfl_up(incl, s); if (lane >= s) incl += t; }
+            int cum = incl - sum;
+            if (cum <= m && m < incl) {
+                int v = 5 * lane;
+#pragma unroll
+                for (int k = 0; k < 5; k++) { if (cum + h[k] > m) break; cum += h[k]; v++; }
+                s_med = v;
+            }
+            __syncthreads();
+            const int median = s_med;
+            if (median < bestMedian) { bestMedian = median; best = i; }
+        }
+    }
+    const long long rb = obs_row(A, e0 + best);
+    if (lane < 8) reinterpret_cast<uint32_t*>(out_desc)[lane] = rb >= 0 ? reinterpret_cast<const uint32_t*>(A.desc_rows + rb * 32)[lane] : 0u;
+    if (lane == 0) {
+        A.best_obs[p] = best;
+        float nsum[3] = {0.0f, 0.0f, 0.0f};
+        for (int e = 0; e < N; e++) {                                        // float sum in observation order
+            const int kf = A.obs_kf[e0 + e];
+            const float* Ow = A.kf_Ow + (size_t)(kf >= 0 && kf < A.nkf ? kf : 0) * 3;
+            normal_add(Pw, Ow, nsum);
+        }
+        int ro = A.ref_obs[p]; ro = ro < 0 ? 0 : (ro >= N ? N - 1 : ro);
+        const int kfr = A.obs_kf[e0 + ro];
+        const float* Owr = A.kf_Ow + (size_t)(kfr >= 0 && kfr < A.nkf ? kfr : 0) * 3;
+        const long long rr = obs_row(A, e0 + ro);
+        int level = rr >= 0 ? A.octave_rows[rr] : 0; level = level < 0 ? 0 : (level > 15 ? 15 : level);
+        finish_point(Pw, nsum, N, Owr, A.sf[level], A.sf[A.nlevels - 1], out_f);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+struct ChainArgs {
+    MapCam c; int monocular;
+    const viorb_keypoint *k1, *k2; const uint8_t *d1, *d2, *hp2; uint8_t* hp1; const float *ur2, *Ow1, *Ow2, *T2, *F12, *median_depth2;
+    const int *node2, *n2, *n_neigh; const uint8_t* kf2_first;
+    int J, j, cap, pcap;
+    // staging (k_search_triangulation reads key frame 2 as [b][cap])
+    viorb_keypoint* s_k2; uint8_t *s_d2, *s_hp2; float *s_ur2, *s_F12, *s_T2; int *s_node2, *s_n2;
+    // per-pair results
+    const int* match12; const uint8_t* accept; const float* Pw;
+    int *new_idx, *n_new, *status; float* new_pts_f; uint8_t* new_desc;
+};
+
+// Baseline test (src/LocalMapping.cc:1272-1289) and the gather of neighbour j. A stream that is past its neighbour count, already
+// out of capacity, or whose baseline is too short gets n2 = 0: the search then matches nothing and the rest of the chain is a no-op.
+__global__ __launch_bounds__(256) void k_stage_neighbour(ChainArgs A) {
+    __shared__ int s_n;
+    const int b = blockIdx.x, t = threadIdx.x;
+    const size_t row2 = (size_t)b * A.J + A.j, o2 = row2 * A.cap, os = (size_t)b * A.cap;
+    if (t == 0) {
+        int n = min(A.n2[row2], A.cap);
+        if (A.j >= A.n_neigh[b] || A.status[b] != 0) n = 0;
+        else {
+            const float* O1 = A.Ow1 + (size_t)b * 3; const float* O2 = A.Ow2 + row2 * 3;
+            const float baseline = (float)map_norm3d(O2[0] - O1[0], O2[1] - O1[1], O2[2] - O1[2]);
+            if (!A.monocular) { if (baseline < A.c.mb) n = 0; }
+            else { const float ratio = baseline / A.median_depth2[row2]; if ((double)ratio < 0.01) n = 0; }
+        }
+        s_n = n; A.s_n2[b] = n;
+    }
+    if (t < 9) A.s_F12[(size_t)b * 9 + t] = A.F12[row2 * 9 + t];
+    if (t < 12) A.s_T2[(size_t)b * 12 + t] = A.T2[row2 * 12 + t];
+    __syncthreads();
+    const int n = s_n;
+    const uint32_t* ks = reinterpret_cast<const uint32_t*>(A.k2 + o2); uint32_t* kd = reinterpret_cast<uint32_t*>(A.s_k2 + os);
+    for (int i = t; i < n * 7; i += blockDim.x) kd[i] = ks[i];
+    const uint4* ds = reinterpret_cast<const uint4*>(A.d2 + o2 * 32); uint4* dd = reinterpret_cast<uint4*>(A.s_d2 + os * 32);
+    for (int i = t; i < n * 2; i += blockDim.x) dd[i] = ds[i];
+    for (int i = t; i < n; i += blockDim.x) { A.s_hp2[os + i] = A.hp2[o2 + i]; A.s_ur2[os + i] = A.ur2[o2 + i]; A.s_node2[os + i] = A.node2[o2 + i]; }
+}
+
+// Ordered compaction (ascending i1, after the points of earlier neighbours: the reference's nnew order), the working has_point1, and
+// the new point's descriptor / normal / depth range: two observations, so the median rule of ComputeDistinctiveDescriptors takes the
+// first in map order (kf2_first), and UpdateNormalAndDepth runs with the current key frame as mpRefKF.
+__global__ __launch_bounds__(256) void k_append_new_points(ChainArgs A) {
+    __shared__ int s_scan[256];
+    __shared__ int s_base;
+    const int b = blockIdx.x, t = threadIdx.x;
+    const size_t row2 = (size_t)b * A.J + A.j, o2 = row2 * A.cap, o1 = (size_t)b * A.cap;
+    const int chunk = (A.cap + 255) / 256, i_lo = min(t * chunk, A.cap), i_hi = min(i_lo + chunk, A.cap);
+    int cnt = 0;
+    for (int i = i_lo; i < i_hi; i++) cnt += A.accept[o1 + i] != 0;
+    if (t == 0) s_base = A.n_new[b];
+    s_scan[t] = cnt;
+    __syncthreads();
+    for (int s = 1; s < 256; s <<= 1) {
+        const int v = t >= s ? s_scan[t - s] : 0;
+        __syncthreads();
+        s_scan[t] += v;
+        __syncthreads();
+    }
+    const int total = s_base + s_scan[255];
+    int pos = s_base + s_scan[t] - cnt;
+    const float* O1 = A.Ow1 + (size_t)b * 3; const float* O2 = A.Ow2 + row2 * 3;
+    const bool second_first = A.kf2_first[row2] != 0;
+    for (int i = i_lo; i < i_hi; i++) {
+        if (!A.accept[o1 + i]) continue;
+        if (pos < A.pcap) {
+            const int i2 = A.match12[o1 + i];
+            const size_t q = (size_t)b * A.pcap + pos;
+            A.new_idx[q * 3] = i; A.new_idx[q * 3 + 1] = A.j; A.new_idx[q * 3 + 2] = i2;
+            const uint4* src = reinterpret_cast<const uint4*>(second_first ? A.d2 + (o2 + i2) * 32 : A.d1 + (o1 + i) * 32);
+            uint4* dst = reinterpret_cast<uint4*>(A.new_desc + q * 32);
+            dst[0] = src[0]; dst[1] = src[1];
+            const float* P = A.Pw + (o1 + i) * 3;
+            float nsum[3] = {0.0f, 0.0f, 0.0f};
+            normal_add(P, second_first ? O2 : O1, nsum); normal_add(P, second_first ? O1 : O2, nsum);
+            int level = A.k1[o1 + i].octave; level = level < 0 ? 0 : (level > 15 ? 15 : level);
+            finish_point(P, nsum, 2, O1, A.c.sf[level], A.c.sf[A.c.nlevels - 1], A.new_pts_f + q * 8);
+            A.hp1[o1 + i] = 1;
+        }
+        pos++;
+    }
+    if (t == 0) {
+        if (total > A.pcap) { A.n_new[b] = A.pcap; A.status[b] = VIORB_ERR_CAPACITY; }
+        else A.n_new[b] = total;
+    }
+}
+
+} // namespace viorb
+
+using namespace viorb;
+
+namespace {
+struct MapBuf {                                              // host-form helper: device allocations freed on return
+    std::vector<void*> ptrs;
+    ~MapBuf() { for (void* p : ptrs) (void)hipFree(p); }
+    bool ok = true;
+    // n_alloc zeroed elements, the first n_src of them copied from src
+    template <class T> T* up(const T* src, size_t n_src, size_t n_alloc) {
+        T* d = nullptr;
+        n_alloc = std::max<size_t>(std::max(n_alloc, n_src), 1);
+        if (!ok || hipMalloc((void**)&d, n_alloc * sizeof(T)) != hipSuccess) { ok = false; return nullptr; }
+        ptrs.push_back(d);
+        if (hipMemset(d, 0, n_alloc * sizeof(T)) != hipSuccess) ok = false;
+        if (ok && src && n_src && hipMemcpy(d, src, n_src * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) ok = false;
+        return d;
+    }
+};
+bool no_device() {
+    if (viorb_device_count() >= 1) return false;
+    set_error("no HIP device: libviorb_hip has no CPU fallback");
+    return true;
+}
+bool cam_ok(const viorb_mapping_camera* c) { return c && c->nlevels >= 1 && c->nlevels <= 16 && c->fx != 0 && c->fy != 0; }
+
+size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
+struct ChainLayout { size_t k2, d2, hp2, ur2, node2, F12, T2, n2, match12, nmatch, accept, reason, Pw, total; };
+ChainLayout chain_layout(int cap, int batch) {
+    ChainLayout L; size_t o = 0; const size_t n = (size_t)cap * batch;
+    auto take = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
+    L.k2 = take(n * sizeof(viorb_keypoint)); L.d2 = take(n * 32); L.hp2 = take(n); L.ur2 = take(n * 4); L.node2 = take(n * 4);
+    L.F12 = take((size_t)batch * 36); L.T2 = take((size_t)batch * 48); L.n2 = take((size_t)batch * 4); L.match12 = take(n * 4);
+    L.nmatch = take((size_t)batch * 4); L.accept = take(n); L.reason = take(n); L.Pw = take(n * 12);
+    L.total = o;
+    return L;
+}
+
+int launch_triangulate(const MapCam& c, const viorb_keypoint* k1, const float* xy1, const float* ur1, const float* dep1, const int* n1,
+                       const float* T1, const float* Ow1, const viorb_keypoint* k2, const float* xy2, const float* ur2, const float* dep2,
+                       const float* T2, const float* Ow2, int stride2, int off2, const int* match12, int cap, int batch, uint8_t* accept,
+                       float* Pw, uint8_t* reason, hipStream_t st) {
+    TriPairsArgs A;
+    A.c = c; A.k1 = k1; A.k2 = k2; A.xy1 = xy1; A.xy2 = xy2; A.ur1 = ur1; A.ur2 = ur2; A.dep1 = dep1; A.dep2 = dep2; A.T1 = T1; A.T2 = T2;
+    A.Ow1 = Ow1; A.Ow2 = Ow2; A.n1 = n1; A.match12 = match12; A.accept = accept; A.reason = reason; A.Pw = Pw;
+    A.cap = cap; A.stride2 = stride2; A.off2 = off2;
+    ProfScope ps("k_triangulate_pairs", st);
+    hipLaunchKernelGGL(k_triangulate_pairs, dim3((cap + 255) / 256, batch), dim3(256), 0, st, A);
+    VIORB_HIP_TRY(hipGetLastError());
+    return VIORB_OK;
+}
+} // namespace
+
+extern "C" {
+
+int viorb_triangulate_pairs_device(const viorb_mapping_camera* cam, const viorb_keypoint* k1, const float* keys_dist_xy1,
+                                   const float* uright1, const float* depth1, const int32_t* n1, const float* pose12_1,
+                                   const float* Ow1, const viorb_keypoint* k2, const float* keys_dist_xy2, const float* uright2,
+                                   const float* depth2, const float* pose12_2, const float* Ow2, const int32_t* match12, int cap,
+                                   int batch, uint8_t* accept, float* Pw, uint8_t* reason, void* stream) {
+    VIORB_REQUIRE(cam_ok(cam), "camera: nlevels 1..16, fx, fy != 0");
+    VIORB_REQUIRE(k1 && keys_dist_xy1 && uright1 && depth1 && n1 && pose12_1 && Ow1 && k2 && keys_dist_xy2 && uright2 && depth2 && pose12_2 && Ow2 &&
+                  match12 && accept && Pw && reason, "null array");
+    VIORB_REQUIRE(cap >= 1 && batch >= 1 && batch <= 65535, "cap >= 1, 1 <= batch <= 65535");
+    if (no_device()) return VIORB_ERR_NO_DEVICE;
+    return launch_triangulate(make_cam(*cam), k1, keys_dist_xy1, uright1, depth1, n1, pose12_1, Ow1, k2, keys_dist_xy2, uright2, depth2, pose12_2,
+                              Ow2, 1, 0, match12, cap, batch, accept, Pw, reason, (hipStream_t)stream);
+}
+
+int viorb_triangulate_pairs(const viorb_mapping_camera* cam, const viorb_keypoint* k1, const float* keys_dist_xy1,
+                            const float* uright1, const float* depth1, int n1, const float pose12_1[12], const float Ow1[3],
+                            const viorb_keypoint* k2, const float* keys_dist_xy2, const float* uright2, const float* depth2, int n2,
+                            const float pose12_2[12], const float Ow2[3], const int32_t* match12, uint8_t* accept, float* Pw,
+                            uint8_t* reason) {
+    VIORB_REQUIRE(cam_ok(cam), "camera: nlevels 1..16, fx, fy != 0");
+    VIORB_REQUIRE(n1 >= 0 && n2 >= 0, "negative count");
+    if (n1 == 0) return VIORB_OK;
+    VIORB_REQUIRE(k1 && keys_dist_xy1 && uright1 && depth1 && pose12_1 && Ow1 && pose12_2 && Ow2 && match12 && accept && Pw && reason &&
+                  (n2 == 0 || (k2 && keys_dist_xy2 && uright2 && depth2)), "null array");
+    for (int i = 0; i < n1; i++) VIORB_REQUIRE(match12[i] < n2, "match12[i1] >= n2");
+    if (no_device()) return VIORB_ERR_NO_DEVICE;
+    const size_t cap = (size_t)std::max(n1, std::max(n2, 1));
+    MapBuf B;
+    viorb_keypoint* dk1 = B.up(k1, n1, cap); viorb_keypoint* dk2 = B.up(k2, n2, cap);
+    float *dx1 = B.up(keys_dist_xy1, 2 * (size_t)n1, 2 * cap), *dx2 = B.up(keys_dist_xy2, 2 * (size_t)n2, 2 * cap);
+    float *du1 = B.up(uright1, n1, cap), *du2 = B.up(uright2, n2, cap), *dz1 = B.up(depth1, n1, cap), *dz2 = B.up(depth2, n2, cap);
+    float *dT1 = B.up(pose12_1, 12, 12), *dT2 = B.up(pose12_2, 12, 12), *dO1 = B.up(Ow1, 3, 3), *dO2 = B.up(Ow2, 3, 3);
+    float* dP = B.up((const float*)nullptr, 0, 3 * cap);
+    int *dn1 = B.up(&n1, 1, 1), *dm = B.up(match12, n1, cap);
+    uint8_t *da = B.up((const uint8_t*)nullptr, 0, cap), *dr = B.up((const uint8_t*)nullptr, 0, cap);
+    if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
+    const int rc = viorb_triangulate_pairs_device(cam, dk1, dx1, du1, dz1, dn1, dT1, dO1, dk2, dx2, du2, dz2, dT2, dO2, dm, (int)cap, 1, da, dP, dr, nullptr);
+    if (rc != VIORB_OK) return rc;
+    VIORB_HIP_TRY(hipDeviceSynchronize());
+    VIORB_HIP_TRY(hipMemcpy(accept, da, n1, hipMemcpyDeviceToHost));
+    VIORB_HIP_TRY(hipMemcpy(reason, dr, n1, hipMemcpyDeviceToHost));
+    VIORB_HIP_TRY(hipMemcpy(Pw, dP, sizeof(float) * 3 * n1, hipMemcpyDeviceToHost));
+    return VIORB_OK;
+}
+
+int viorb_map_points_update_device(const int32_t* obs_start, const int32_t* obs_kf, const int32_t* obs_feat, const int32_t* ref_obs,
+                                   const float* Pw, int npts, const int64_t* kf_row_base, const float* kf_Ow, int nkf,
+                                   const uint8_t* desc_rows, const int32_t* octave_rows, int64_t pool_rows,
+                                   const viorb_mapping_camera* cam, uint8_t* pts_desc, int32_t* best_obs, float* pts_f, void* stream) {
+    VIORB_REQUIRE(cam_ok(cam), "camera: nlevels 1..16, fx, fy != 0");
+    VIORB_REQUIRE(npts >= 0 && nkf >= 1 && pool_rows >= 1, "npts >= 0, nkf >= 1, pool_rows >= 1");
+    if (npts == 0) return VIORB_OK;
+    VIORB_REQUIRE(obs_start && obs_kf && obs_feat && ref_obs && Pw && kf_row_base && kf_Ow && desc_rows && octave_rows && pts_desc && best_obs && pts_f,
+                  "null array");
+    if (no_device()) return VIORB_ERR_NO_DEVICE;
+    MpuArgs A;
+    A.obs_start = obs_start; A.obs_kf = obs_kf; A.obs_feat = obs_feat; A.ref_obs = ref_obs; A.Pw = Pw;
+    A.kf_row_base = reinterpret_cast<const long long*>(kf_row_base); A.kf_Ow = kf_Ow; A.nkf = nkf; A.desc_rows = desc_rows; A.octave_rows = octave_rows;
+    A.pool_rows = pool_rows; A.nlevels = cam->nlevels;
+    const MapCam c = make_cam(*cam);
+    for (int i = 0; i < 16; i++) A.sf[i] = c.sf[i];
+    A.pts_desc = pts_desc; A.best_obs = best_obs; A.pts_f = pts_f;
+    ProfScope ps("k_map_point_update", (hipStream_t)stream);
+    hipLaunchKernelGGL(k_map_point_update, dim3(npts), dim3(64), 0, (hipStream_t)stream, A);
+    VIORB_HIP_TRY(hipGetLastError());
+    return VIORB_OK;
+}
+
+int viorb_map_points_update(const int32_t* obs_start, const int32_t* obs_kf, const int32_t* obs_feat, const int32_t* ref_obs,
+                            const float* Pw, int npts, const int64_t* kf_row_base, const float* kf_Ow, int nkf,
+                            const uint8_t* desc_rows, const int32_t* octave_rows, int64_t pool_rows,
+                            const viorb_mapping_camera* cam, uint8_t* pts_desc, int32_t* best_obs, float* pts_f) {
+    VIORB_REQUIRE(cam_ok(cam), "camera: nlevels 1..16, fx, fy != 0");
+    VIORB_REQUIRE(npts >= 0 && nkf >= 1 && pool_rows >= 1, "npts >= 0, nkf >= 1, pool_rows >= 1");
+    if (npts == 0) return VIORB_OK;
+    VIORB_REQUIRE(obs_start && obs_kf && obs_feat && ref_obs && Pw && kf_row_base && kf_Ow && desc_rows && octave_rows && pts_desc && best_obs && pts_f,
+                  "null array");
+    VIORB_REQUIRE(obs_start[0] == 0, "obs_start[0] must be 0");
+    for (int p = 0; p < npts; p++) VIORB_REQUIRE(obs_start[p + 1] >= obs_start[p], "obs_start must not decrease");
+    if (no_device()) return VIORB_ERR_NO_DEVICE;
+    const size_t ne = (size_t)obs_start[npts];
+    MapBuf B;
+    int *ds = B.up(obs_start, (size_t)npts + 1, 0), *dk = B.up(obs_kf, ne, 0), *df = B.up(obs_feat, ne, 0), *dr = B.up(ref_obs, npts, 0);
+    float *dP = B.up(Pw, 3 * (size_t)npts, 0), *dO = B.up(kf_Ow, 3 * (size_t)nkf, 0), *dpf = B.up((const float*)nullptr, 0, 8 * (size_t)npts);
+    int64_t* db = B.up(kf_row_base, nkf, 0);
+    uint8_t *dd = B.up(desc_rows, 32 * (size_t)pool_rows, 0), *dpd = B.up((const uint8_t*)nullptr, 0, 32 * (size_t)npts);
+    int *doc = B.up(octave_rows, (size_t)pool_rows, 0), *dbo = B.up((const int*)nullptr, 0, npts);
+    if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
+    const int rc = viorb_map_points_update_device(ds, dk, df, dr, dP, npts, db, dO, nkf, dd, doc, pool_rows, cam, dpd, dbo, dpf, nullptr);
+    if (rc != VIORB_OK) return rc;
+    VIORB_HIP_TRY(hipDeviceSynchronize());
+    VIORB_HIP_TRY(hipMemcpy(pts_desc, dpd, 32 * (size_t)npts, hipMemcpyDeviceToHost));
+    VIORB_HIP_TRY(hipMemcpy(best_obs, dbo, sizeof(int) * (size_t)npts, hipMemcpyDeviceToHost));
+    VIORB_HIP_TRY(hipMemcpy(pts_f, dpf, sizeof(float) * 8 * (size_t)npts, hipMemcpyDeviceToHost));
+    return VIORB_OK;
+}
+
+size_t viorb_create_new_map_points_workspace_bytes(int cap, int batch) {
+    if (cap < 1 || batch < 1) return 0;
+    return chain_layout(cap, batch).total;
+}
+
+int viorb_create_new_map_points_device(const viorb_mapping_camera* cam, int monocular, const viorb_keypoint* k1, const uint8_t* d1,
+                                       uint8_t* has_point1, const float* uright1, const float* depth1, const float* keys_dist_xy1,
+                                       const int32_t* node1, const int32_t* n1, const float* pose12_1, const float* Ow1,
+                                       const viorb_keypoint* k2, const uint8_t* d2, const uint8_t* has_point2, const float* uright2,
+                                       const float* depth2, const float* keys_dist_xy2, const int32_t* node2, const int32_t* n2,
+                                       const float* pose12_2, const float* Ow2, const float* F12, const float* median_depth2,
+                                       const uint8_t* kf2_first, const int32_t* n_neigh, int J, int j_begin, int j_end, int cap,
+                                       int batch, int pcap, int32_t* new_idx, float* new_pts_f, uint8_t* new_desc, int32_t* n_new,
+                                       int32_t* status, void* workspace, size_t workspace_bytes, void* stream) {
+    VIORB_REQUIRE(cam_ok(cam), "camera: nlevels 1..16, fx, fy != 0");
+    VIORB_REQUIRE(k1 && d1 && has_point1 && uright1 && depth1 && keys_dist_xy1 && node1 && n1 && pose12_1 && Ow1 && k2 && d2 && has_point2 && uright2 &&
+                  depth2 && keys_dist_xy2 && node2 && n2 && pose12_2 && Ow2 && F12 && median_depth2 && kf2_first && n_neigh && new_idx && new_pts_f &&
+                  new_desc && n_new && status && workspace, "null array");
+    VIORB_REQUIRE(J >= 1 && 0 <= j_begin && j_begin <= j_end && j_end <= J, "0 <= j_begin <= j_end <= J");
+    VIORB_REQUIRE(cap >= 1 && cap <= 16384 && batch >= 1 && batch <= 65535 && pcap >= 1, "1 <= cap <= 16384, 1 <= batch <= 65535, pcap >= 1");
+    const ChainLayout L = chain_layout(cap, batch);
+    VIORB_REQUIRE(workspace_bytes >= L.total && ((uintptr_t)workspace & 255) == 0, "workspace smaller than viorb_create_new_map_points_workspace_bytes or not 256-byte aligned");
+    if (no_device()) return VIORB_ERR_NO_DEVICE;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned char* W = static_cast<unsigned char*>(workspace);
+    ChainArgs A;
+    A.c = make_cam(*cam); A.monocular = monocular;
+    A.k1 = k1; A.k2 = k2; A.d1 = d1; A.d2 = d2; A.hp2 = has_point2; A.hp1 = has_point1; A.ur2 = uright2; A.Ow1 = Ow1; A.Ow2 = Ow2; A.T2 = pose12_2;
+    A.F12 = F12; A.median_depth2 = median_depth2; A.node2 = node2; A.n2 = n2; A.n_neigh = n_neigh; A.kf2_first = kf2_first;
+    A.J = J; A.cap = cap; A.pcap = pcap;
+    A.s_k2 = reinterpret_cast<viorb_keypoint*>(W + L.k2); A.s_d2 = W + L.d2; A.s_hp2 = W + L.hp2; A.s_ur2 = reinterpret_cast<float*>(W + L.ur2);
+    A.s_F12 = reinterpret_cast<float*>(W + L.F12); A.s_T2 = reinterpret_cast<float*>(W + L.T2); A.s_node2 = reinterpret_cast<int*>(W + L.node2);
+    A.s_n2 = reinterpret_cast<int*>(W + L.n2);
+    int* w_match = reinterpret_cast<int*>(W + L.match12); int* w_nmatch = reinterpret_cast<int*>(W + L.nmatch);
+    uint8_t* w_accept = W + L.accept; uint8_t* w_reason = W + L.reason; float* w_Pw = reinterpret_cast<float*>(W + L.Pw);
+    A.match12 = w_match; A.accept = w_accept; A.Pw = w_Pw;
+    A.new_idx = new_idx; A.n_new = n_new; A.status = status; A.new_pts_f = new_pts_f; A.new_desc = new_desc;
+    const float intr4[4] = {cam->fx, cam->fy, cam->cx, cam->cy};
+    for (int j = j_begin; j < j_end; j++) {
+        A.j = j;
+        { ProfScope ps("k_stage_neighbour", st); hipLaunchKernelGGL(k_stage_neighbour, dim3(batch), dim3(256), 0, st, A); }
+        VIORB_HIP_TRY(hipGetLastError());
+        // ORBmatcher matcher(0.6, false); SearchForTriangulation(.., false) (src/LocalMapping.cc:1245, 1296)
+        int rc = viorb_search_for_triangulation_device(k1, d1, has_point1, uright1, node1, n1, A.s_k2, A.s_d2, A.s_hp2, A.s_ur2, A.s_node2, A.s_n2, A.s_F12,
+                                                       Ow1, A.s_T2, intr4, cam->scale_factors, cam->level_sigma2, cam->nlevels, 0, 0, cap, batch, w_match,
+                                                       w_nmatch, stream);
+        if (rc != VIORB_OK) return rc;
+        rc = launch_triangulate(A.c, k1, keys_dist_xy1, uright1, depth1, n1, pose12_1, Ow1, k2, keys_dist_xy2, uright2, depth2, pose12_2, Ow2, J, j,
+                                w_match, cap, batch, w_accept, w_Pw, w_reason, st);
+        if (rc != VIORB_OK) return rc;
+        { ProfScope ps("k_append_new_points", st); hipLaunchKernelGGL(k_append_new_points, dim3(batch), dim3(256), 0, st, A); }
+        VIORB_HIP_TRY(hipGetLastError());
+    }
+    return VIORB_OK;
+}
+
+int viorb_create_new_map_points(const viorb_mapping_camera* cam, int monocular, const viorb_keypoint* k1, const uint8_t* d1,
+                                uint8_t* has_point1, const float* uright1, const float* depth1, const float* keys_dist_xy1,
+                                const int32_t* node1, int n1, const float pose12_1[12], const float Ow1[3], const viorb_keypoint* k2,
+                                const uint8_t* d2, const uint8_t* has_point2, const float* uright2, const float* depth2,
+                                const float* keys_dist_xy2, const int32_t* node2, const int32_t* n2, const float* pose12_2,
+                                const float* Ow2, const float* F12, const float* median_depth2, const uint8_t* kf2_first, int J,
+                                int cap, int pcap, int32_t* new_idx, float* new_pts_f, uint8_t* new_desc, int* n_new) {
+    VIORB_REQUIRE(cam_ok(cam), "camera: nlevels 1..16, fx, fy != 0");
+    VIORB_REQUIRE(n_new && n1 >= 0 && J >= 0 && cap >= 1 && n1 <= cap && pcap >= 1, "n1 <= cap, J >= 0, pcap >= 1");
+    *n_new = 0;
+    if (n1 == 0 || J == 0) return VIORB_OK;
+    VIORB_REQUIRE(k1 && d1 && has_point1 && uright1 && depth1 && keys_dist_xy1 && node1 && pose12_1 && Ow1 && k2 && d2 && has_point2 && uright2 && depth2 &&
+                  keys_dist_xy2 && node2 && n2 && pose12_2 && Ow2 && F12 && median_depth2 && kf2_first && new_idx && new_pts_f && new_desc, "null array");
+    for (int j = 0; j < J; j++) VIORB_REQUIRE(n2[j] >= 0 && n2[j] <= cap, "n2[j] out of 0..cap");
+    if (no_device()) return VIORB_ERR_NO_DEVICE;
+    const size_t c = (size_t)cap, jc = (size_t)J * cap;
+    MapBuf B;
+    viorb_keypoint *dk1 = B.up(k1, n1, c), *dk2 = B.up(k2, jc, 0);
+    uint8_t *dd1 = B.up(d1, 32 * (size_t)n1, 32 * c), *dh1 = B.up(has_point1, n1, c), *dd2 = B.up(d2, 32 * jc, 0), *dh2 = B.up(has_point2, jc, 0);
+    float *du1 = B.up(uright1, n1, c), *dz1 = B.up(depth1, n1, c), *dx1 = B.up(keys_dist_xy1, 2 * (size_t)n1, 2 * c);
+    float *du2 = B.up(uright2, jc, 0), *dz2 = B.up(depth2, jc, 0), *dx2 = B.up(keys_dist_xy2, 2 * jc, 0);
+    int *dnode1 = B.up(node1, n1, c), *dnode2 = B.up(node2, jc, 0), *dn1 = B.up(&n1, 1, 1), *dn2 = B.up(n2, J, 0), *dnn = B.up(&J, 1, 1);
+    float *dT1 = B.up(pose12_1, 12, 0), *dO1 = B.up(Ow1, 3, 0), *dT2 = B.up(pose12_2, 12 * (size_t)J, 0), *dO2 = B.up(Ow2, 3 * (size_t)J, 0);
+    float *dF = B.up(F12, 9 * (size_t)J, 0), *dmd = B.up(median_depth2, J, 0);
+    uint8_t* dkf = B.up(kf2_first, J, 0);
+    int *didx = B.up((const int*)nullptr, 0, 3 * (size_t)pcap), *dnew = B.up((const int*)nullptr, 0, 1), *dst = B.up((const int*)nullptr, 0, 1);
+    float* dpf = B.up((const float*)nullptr, 0, 8 * (size_t)pcap);
+    uint8_t* dpd = B.up((const uint8_t*)nullptr, 0, 32 * (size_t)pcap);
+    const size_t wb = viorb_create_new_map_points_workspace_bytes(cap, 1);
+    unsigned char* dw = B.up((const unsigned char*)nullptr, 0, wb);
+    if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
+    const int rc = viorb_create_new_map_points_device(cam, monocular, dk1, dd1, dh1, du1, dz1, dx1, dnode1, dn1, dT1, dO1, dk2, dd2, dh2, du2, dz2, dx2, dnode2,
+                                                      dn2, dT2, dO2, dF, dmd, dkf, dnn, J, 0, J, cap, 1, pcap, didx, dpf, dpd, dnew, dst, dw, wb, nullptr);
+    if (rc != VIORB_OK) return rc;
+    VIORB_HIP_TRY(hipDeviceSynchronize());
+    int status = 0;
+    VIORB_HIP_TRY(hipMemcpy(n_new, dnew, sizeof(int), hipMemcpyDeviceToHost));
+    VIORB_HIP_TRY(hipMemcpy(&status, dst, sizeof(int), hipMemcpyDeviceToHost));
+    VIORB_HIP_TRY(hipMemcpy(has_point1, dh1, n1, hipMemcpyDeviceToHost));
+    if (*n_new > 0) {
+        VIORB_HIP_TRY(hipMemcpy(new_idx, didx, sizeof(int) * 3 * (size_t)*n_new, hipMemcpyDeviceToHost));
+        VIORB_HIP_TRY(hipMemcpy(new_pts_f, dpf, sizeof(float) * 8 * (size_t)*n_new, hipMemcpyDeviceToHost));
+        VIORB_HIP_TRY(hipMemcpy(new_desc, dpd, 32 * (size_t)*n_new, hipMemcpyDeviceToHost));
+    }
+    if (status != VIORB_OK) { set_error("more than pcap = %d map points created; the first %d are returned", pcap, pcap); return status; }
+    return VIORB_OK;
+}
+
+// ---- host-only test hooks: mapping_core.h compiled for the host ----------------------------------
+int viorb_debug_triangulate_pair(const viorb_mapping_camera* cam, const float* pose12_1, const float* Ow1, const float* pose12_2,
+                                 const float* Ow2, const float* key1_6, int octave1, const float* key2_6, int octave2, float* Pw3) {
+    const MapCam c = make_cam(*cam);
+    MapKey a, b;
+    a.u = key1_6[0]; a.v = key1_6[1]; a.ur = key1_6[2]; a.depth = key1_6[3]; a.ud = key1_6[4]; a.vd = key1_6[5]; a.octave = octave1;
+    b.u = key2_6[0]; b.v = key2_6[1]; b.ur = key2_6[2]; b.depth = key2_6[3]; b.ud = key2_6[4]; b.vd = key2_6[5]; b.octave = octave2;
+    float X[3];
+    const int r = triangulate_pair(c, pose12_1, Ow1, pose12_2, Ow2, a, b, X);
+    Pw3[0] = X[0]; Pw3[1] = X[1]; Pw3[2] = X[2];
+    return r;
+}
+
+int viorb_debug_map_point_update(const int32_t* obs_start, const int32_t* obs_kf, const int32_t* obs_feat, const int32_t* ref_obs,
+                                 const float* Pw, int p, const int64_t* kf_row_base, const float* kf_Ow, int nkf,
+                                 const uint8_t* desc_rows, const int32_t* octave_rows, int64_t pool_rows,
+                                 const viorb_mapping_camera* cam, uint8_t* pts_desc32, int32_t* best_obs, float* pts_f8) {
+    (void)nkf; (void)pool_rows;
+    const MapCam c = make_cam(*cam);
+    const int e0 = obs_start[p], N = obs_start[p + 1] - e0;
+    const float* P = Pw + (size_t)p * 3;
+    memset(pts_desc32, 0, 32);
+    for (int k = 0; k < 8; k++) pts_f8[k] = k < 3 ? P[k] : 0.0f;
+    *best_obs = -1;
+    if (N <= 0) return VIORB_OK;
+    auto row = [&](int e) { return reinterpret_cast<const uint32_t*>(desc_rows + (size_t)(kf_row_base[obs_kf[e0 + e]] + obs_feat[e0 + e]) * 32); };
+    const int m = (int)(0.5 * (N - 1));
+    int best = 0, bestMedian = 0x7fffffff;
+    std::vector<int> hist(257);
+    for (int i = 0; i < N; i++) {                            // rank by counting, as the kernel's histogram form
+        std::fill(hist.begin(), hist.end(), 0);
+        for (int j = 0; j < N; j++) hist[hamming256(row(i), row(j))]++;
+        int v = 0, cum = 0;
+        while (cum + hist[v] <= m) cum += hist[v++];
+        if (v < bestMedian) { bestMedian = v; best = i; }
+    }
+    memcpy(pts_desc32, row(best), 32);
+    *best_obs = best;
+    float nsum[3] = {0.0f, 0.0f, 0.0f};
+    for (int e = 0; e < N; e++) normal_add(P, kf_Ow + (size_t)obs_kf[e0 + e] * 3, nsum);
+    int ro = ref_obs[p]; ro = ro < 0 ? 0 : (ro >= N ? N - 1 : ro);
+    int level = octave_rows[kf_row_base[obs_kf[e0 + ro]] + obs_feat[e0 + ro]]; level = level < 0 ? 0 : (level > 15 ? 15 : level);
+    finish_point(P, nsum, N, kf_Ow + (size_t)obs_kf[e0 + ro] * 3, c.sf[level], c.sf[c.nlevels - 1], pts_f8);
+    return VIORB_OK;
+}
+
+} // extern "C"

@@ -1,0 +1,153 @@
+// viorb_amd/shim/LocalMapping_shim.h — reference-side glue for map-point creation: function templates over the reference's KeyFrame /
+// MapPoint member names that flatten the objects, call the C ABI of include/viorb.h and hand the results back. The library allocates
+// nothing of the map: `new MapPoint`, AddObservation, AddMapPoint and mpMap->AddMapPoint stay in LocalMapping.cc.
+// A GPU error is thrown with viorb_last_error() (viorb_shim::check), never reported as "0 new points".
+//
+//   create_new_map_points   LocalMapping::CreateNewMapPoints, everything between GetBestCovisibilityKeyFrames and `new MapPoint`
+//                           for all neighbours in one call                                              src/LocalMapping.cc:1242-1464
+//   update_map_points       MapPoint::ComputeDistinctiveDescriptors + MapPoint::UpdateNormalAndDepth for a list of points
+//                                                                                                       src/MapPoint.cc:249-314, 337-378
+//
+// KeyFrame members read: N, mvKeysUn, mvKeys, mvuRight, mvDepth, mDescriptors, mFeatVec, GetMapPoint, GetPose, GetCameraCenter, isBad,
+// fx fy cx cy mb mbf, mfScaleFactor, mnScaleLevels, mvScaleFactors, mvLevelSigma2. One accessor the reference does not have is needed
+// on MapPoint for update_map_points (mDescriptor, mNormalVector, mfMinDistance and mfMaxDistance are protected):
+//   void SetDescriptorNormalAndDepth(const cv::Mat& desc, const cv::Mat& normal, float minDist, float maxDist)
+// storing the four members under mMutexFeatures / mMutexPos — a five-line addition to include/MapPoint.h.
+#ifndef VIORB_LOCALMAPPING_SHIM_H
+#define VIORB_LOCALMAPPING_SHIM_H
+
+#include <algorithm>
+#include <functional>
+#include <map>
+#include <vector>
+#include "ORBmatcher_shim.h"
+
+namespace viorb_shim {
+
+// One accepted pair of CreateNewMapPoints, in the reference's creation order: the caller runs src/LocalMapping.cc:1466-1481 on it.
+struct NewMapPoint {
+    size_t idx1, neighbour, idx2;          // mpCurrentKeyFrame feature, index into vpNeighKFs, pKF2 feature
+    cv::Mat x3D;                           // 3 x 1 CV_32F
+    cv::Mat descriptor;                    // 1 x 32 CV_8U: what ComputeDistinctiveDescriptors would pick for the two observations
+    cv::Mat normal;                        // 3 x 1 CV_32F: UpdateNormalAndDepth with mpCurrentKeyFrame as mpRefKF
+    float minDistance, maxDistance;
+};
+
+template <class KeyFrameT> inline viorb_mapping_camera mapping_camera(const KeyFrameT* pKF) {
+    viorb_mapping_camera c;
+    c.fx = pKF->fx; c.fy = pKF->fy; c.cx = pKF->cx; c.cy = pKF->cy; c.mb = pKF->mb; c.mbf = pKF->mbf; c.scale_factor = pKF->mfScaleFactor;
+    c.nlevels = pKF->mnScaleLevels;
+    for (int l = 0; l < 16; l++) { const int k = l < c.nlevels ? l : c.nlevels - 1; c.scale_factors[l] = pKF->mvScaleFactors[k]; c.level_sigma2[l] = pKF->mvLevelSigma2[k]; }
+    return c;
+}
+
+// vF12[j] = ComputeF12(pCur, vpNeighKFs[j]) (3 x 3 CV_32F), vMedianDepth[j] = vpNeighKFs[j]->ComputeSceneMedianDepth(2) (unused when
+// !bMonocular). The neighbours' map-point flags are read once; pCur's are updated between neighbours on the device as AddMapPoint
+// (:1472) does. Returns the number of new points; vNew holds them in the reference's nnew order.
+template <class KeyFrameT>
+inline int create_new_map_points(KeyFrameT* pCur, const std::vector<KeyFrameT*>& vpNeighKFs, const std::vector<cv::Mat>& vF12,
+                                 const std::vector<float>& vMedianDepth, bool bMonocular, std::vector<NewMapPoint>& vNew) {
+    vNew.clear();
+    const int J = (int)vpNeighKFs.size(), n1 = pCur->N;
+    if (J == 0 || n1 == 0) return 0;
+    int cap = n1;
+    for (int j = 0; j < J; j++) cap = std::max(cap, (int)vpNeighKFs[j]->N);
+    const size_t jc = (size_t)J * cap;
+    std::vector<viorb_keypoint> k1, k2(jc), tmpk;
+    std::vector<unsigned char> h1(n1 + 1, 0), d2(jc * 32, 0), h2(jc, 0), first(J, 0);
+    std::vector<float> xy1((size_t)2 * n1 + 2, 0.f), ur2(jc, -1.f), dep2(jc, -1.f), xy2(jc * 2, 0.f), pose2((size_t)J * 12), Ow2((size_t)J * 3), F((size_t)J * 9), md(J, 1.f);
+    std::vector<int32_t> node1, node2(jc, -1), tmpn, n2(J, 0);
+    flatten_keys(pCur->mvKeysUn, n1, k1); flatten_featvec(pCur->mFeatVec, n1, node1);
+    for (int i = 0; i < n1; i++) { h1[i] = pCur->GetMapPoint(i) ? 1 : 0; xy1[2 * i] = pCur->mvKeys[i].pt.x; xy1[2 * i + 1] = pCur->mvKeys[i].pt.y; }
+    for (int j = 0; j < J; j++) {
+        KeyFrameT* p2 = vpNeighKFs[j];
+        const int n = p2->N; const size_t o = (size_t)j * cap;
+        n2[j] = n;
+        flatten_keys(p2->mvKeysUn, n, tmpk); flatten_featvec(p2->mFeatVec, n, tmpn);
+        for (int i = 0; i < n; i++) {
+            k2[o + i] = tmpk[i]; node2[o + i] = tmpn[i]; h2[o + i] = p2->GetMapPoint(i) ? 1 : 0; ur2[o + i] = p2->mvuRight[i]; dep2[o + i] = p2->mvDepth[i];
+            xy2[2 * (o + i)] = p2->mvKeys[i].pt.x; xy2[2 * (o + i) + 1] = p2->mvKeys[i].pt.y;
+        }
+        if (n) std::memcpy(&d2[o * 32], p2->mDescriptors.data, (size_t)n * 32);
+        flatten_pose(p2->GetPose(), &pose2[(size_t)j * 12]);
+        const cv::Mat C2 = p2->GetCameraCenter();
+        for (int c = 0; c < 3; c++) Ow2[(size_t)j * 3 + c] = C2.at<float>(c);
+        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) F[(size_t)j * 9 + 3 * r + c] = vF12[j].template at<float>(r, c);
+        if (bMonocular) md[j] = vMedianDepth[j];
+        first[j] = std::less<KeyFrameT*>()(p2, pCur) ? 1 : 0;          // the order of map<KeyFrame*, size_t> mObservations
+    }
+    float pose1[12], Ow1[3];
+    flatten_pose(pCur->GetPose(), pose1);
+    const cv::Mat C1 = pCur->GetCameraCenter();
+    for (int c = 0; c < 3; c++) Ow1[c] = C1.at<float>(c);
+    const viorb_mapping_camera cam = mapping_camera(pCur);
+    const int pcap = n1;                                                  // a feature of pCur gets at most one new point
+    std::vector<int32_t> idx((size_t)pcap * 3 + 3); std::vector<float> pf((size_t)pcap * 8 + 8); std::vector<unsigned char> pd((size_t)pcap * 32 + 32);
+    int n_new = 0;
+    check(viorb_create_new_map_points(&cam, bMonocular ? 1 : 0, &k1[0], pCur->mDescriptors.data, &h1[0], &pCur->mvuRight[0], &pCur->mvDepth[0], &xy1[0], &node1[0], n1,
+                                      pose1, Ow1, &k2[0], &d2[0], &h2[0], &ur2[0], &dep2[0], &xy2[0], &node2[0], &n2[0], &pose2[0], &Ow2[0], &F[0], &md[0], &first[0],
+                                      J, cap, pcap, &idx[0], &pf[0], &pd[0], &n_new), "CreateNewMapPoints");
+    vNew.resize(n_new);
+    for (int p = 0; p < n_new; p++) {
+        NewMapPoint& q = vNew[p];
+        q.idx1 = (size_t)idx[3 * p]; q.neighbour = (size_t)idx[3 * p + 1]; q.idx2 = (size_t)idx[3 * p + 2];
+        q.x3D = cv::Mat(3, 1, CV_32F); q.normal = cv::Mat(3, 1, CV_32F); q.descriptor = cv::Mat(1, 32, CV_8U);
+        for (int c = 0; c < 3; c++) { q.x3D.template at<float>(c) = pf[(size_t)p * 8 + c]; q.normal.template at<float>(c) = pf[(size_t)p * 8 + 3 + c]; }
+        q.minDistance = pf[(size_t)p * 8 + 6]; q.maxDistance = pf[(size_t)p * 8 + 7];
+        std::memcpy(q.descriptor.data, &pd[(size_t)p * 32], 32);
+    }
+    return n_new;
+}
+
+// pMP->ComputeDistinctiveDescriptors(); pMP->UpdateNormalAndDepth(); for every point of the list (src/LocalMapping.cc:1175-1176,
+// 1559-1560, src/Optimizer.cc:2233), one call. Bad points and points without observations are left alone, bad key frames are left
+// out of the descriptor vote (:273-274) as in the reference. Observations are passed in the order of GetObservations(), i.e. the
+// reference's std::map<KeyFrame*, size_t> pointer order. GetReferenceKeyFrame() names mpRefKF.
+template <class KeyFrameT, class MapPointT>
+inline void update_map_points(const std::vector<MapPointT*>& vpMPs) {
+    std::map<KeyFrameT*, int> kf_index; std::vector<KeyFrameT*> kfs;
+    std::vector<int32_t> start(1, 0), okf, ofeat, ref; std::vector<float> Pw; std::vector<MapPointT*> pts;
+    for (size_t p = 0; p < vpMPs.size(); p++) {
+        MapPointT* pMP = vpMPs[p];
+        if (!pMP || pMP->isBad()) continue;
+        const std::map<KeyFrameT*, size_t> obs = pMP->GetObservations();
+        if (obs.empty()) continue;
+        KeyFrameT* pRef = pMP->GetReferenceKeyFrame();
+        int r = 0, n = 0;
+        for (typename std::map<KeyFrameT*, size_t>::const_iterator it = obs.begin(); it != obs.end(); ++it) {
+            if (it->first->isBad()) continue;
+            if (!kf_index.count(it->first)) { kf_index[it->first] = (int)kfs.size(); kfs.push_back(it->first); }
+            if (it->first == pRef) r = n;
+            okf.push_back(kf_index[it->first]); ofeat.push_back((int32_t)it->second); n++;
+        }
+        if (n == 0) continue;
+        start.push_back(start.back() + n); ref.push_back(r); pts.push_back(pMP);
+        const cv::Mat X = pMP->GetWorldPos();
+        for (int c = 0; c < 3; c++) Pw.push_back(X.at<float>(c));
+    }
+    const int np = (int)pts.size(), nk = (int)kfs.size();
+    if (np == 0) return;
+    std::vector<int64_t> base(nk, 0); std::vector<float> Ow((size_t)nk * 3);
+    int64_t rows = 0;
+    for (int k = 0; k < nk; k++) { base[k] = rows; rows += kfs[k]->N; }
+    std::vector<unsigned char> drows((size_t)std::max<int64_t>(rows, 1) * 32, 0); std::vector<int32_t> orows((size_t)std::max<int64_t>(rows, 1), 0);
+    for (int k = 0; k < nk; k++) {
+        if (kfs[k]->N) std::memcpy(&drows[(size_t)base[k] * 32], kfs[k]->mDescriptors.data, (size_t)kfs[k]->N * 32);
+        for (int i = 0; i < kfs[k]->N; i++) orows[(size_t)base[k] + i] = kfs[k]->mvKeysUn[i].octave;
+        const cv::Mat C = kfs[k]->GetCameraCenter();
+        for (int c = 0; c < 3; c++) Ow[(size_t)k * 3 + c] = C.at<float>(c);
+    }
+    const viorb_mapping_camera cam = mapping_camera(kfs[0]);
+    std::vector<unsigned char> pd((size_t)np * 32); std::vector<int32_t> best(np); std::vector<float> pf((size_t)np * 8);
+    check(viorb_map_points_update(&start[0], &okf[0], &ofeat[0], &ref[0], &Pw[0], np, &base[0], &Ow[0], nk, &drows[0], &orows[0], std::max<int64_t>(rows, 1), &cam,
+                                  &pd[0], &best[0], &pf[0]), "MapPoint::ComputeDistinctiveDescriptors / UpdateNormalAndDepth");
+    for (int p = 0; p < np; p++) {
+        cv::Mat d(1, 32, CV_8U), nrm(3, 1, CV_32F);
+        std::memcpy(d.data, &pd[(size_t)p * 32], 32);
+        for (int c = 0; c < 3; c++) nrm.at<float>(c) = pf[(size_t)p * 8 + 3 + c];
+        pts[p]->SetDescriptorNormalAndDepth(d, nrm, pf[(size_t)p * 8 + 6], pf[(size_t)p * 8 + 7]);
+    }
+}
+
+} // namespace viorb_shim
+#endif

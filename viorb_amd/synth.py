@@ -672,3 +672,122 @@ def make_local_ba_se3_problem(seed, W=8, n_fixed=3, n_points=600, stereo_frac=0.
     points0 = pts + rng.normal(0, 0.1, pts.shape)
     return dict(kfs=kfs, kfs_true=kfs_true, n_local=W, points=points0, points_true=pts, edge_idx=np.array(ei, np.int32), edge_obs=np.array(eo, np.float64),
                 intr5=np.array([fx, fy, cx, cy, bf]))
+
+
+def make_mapping_problem(seed, J=20, n1=1000, n2=1000, stereo_frac=0.0, w=752, h=480):
+    """One current key frame and J neighbour key frames over a common cloud, for map-point creation (LocalMapping::CreateNewMapPoints,
+    MapPoint::ComputeDistinctiveDescriptors / UpdateNormalAndDepth). Built so that every statement of the per-pair loop is taken:
+    baselines from far too short (the baseline test skips the neighbour) to wide, a far shell of points beyond the 0.9998 parallax
+    limit, sideways-looking neighbours and wrong partners that triangulate behind a camera, a share of key points with pixel noise
+    far above the reprojection gates, octave pairs that violate scale consistency, and `stereo_frac` of the key points with uRight /
+    depth so that both UnprojectStereo branches and the 7.8 gates run. Besides what SearchForTriangulation needs (descriptors,
+    vocabulary nodes, F12) every neighbour carries `match_gen`, a match12 written here from the truth (true partners, near misses a
+    few pixels off, wrong partners): the search's epipolar gate would remove most bad pairs before the vetting sees them.
+    Returns dict(cam, kf1, neigh[J], bounds, X). numpy only."""
+    rng = np.random.Generator(np.random.PCG64(seed + 424243))
+    f32 = np.float32
+    fx, fy, cx, cy = [f32(v) for v in (EUROC_K["fx"], EUROC_K["fy"], EUROC_K["cx"], EUROC_K["cy"])]
+    K = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], np.float64)
+    Kinv = np.linalg.inv(K)
+    mb = f32(0.11); mbf = f32(fx * mb)
+    sf = (f32(1.2) ** np.arange(8)).astype(np.float32)
+    cam = dict(intr4=np.array([fx, fy, cx, cy], np.float32), mb=mb, mbf=mbf, scale_factor=f32(1.2), sf=sf, level_sigma2=(sf * sf).astype(np.float32),
+               inv_level_sigma2=(f32(1) / (sf * sf)).astype(np.float32))
+    n_near = int(n1 * 0.8)
+    dirs = np.stack([rng.uniform(-0.9, 0.9, n1), rng.uniform(-0.55, 0.55, n1), np.ones(n1)], 1)
+    depth = np.concatenate([rng.uniform(2.0, 14.0, n_near), rng.uniform(60.0, 900.0, n1 - n_near)])
+    R1 = _rotvec_to_R(rng.normal(0, 0.03, 3)); t1 = rng.normal(0, 0.05, 3)
+    X = (R1.T @ (dirs * depth[:, None] - t1).T).T                       # cloud: every point is seen by the current key frame
+    base_desc = rng.integers(0, 256, (n1, 32), dtype=np.uint8)
+    base_node = rng.integers(0, 80, n1).astype(np.int32)
+    base_oct = rng.integers(0, 8, n1)
+    base_angle = rng.uniform(0, 360, n1)
+
+    def project(R, t, P):
+        Pc = (R @ P.T).T + t
+        z = np.where(np.abs(Pc[:, 2]) < 1e-9, 1e-9, Pc[:, 2])
+        return np.stack([fx * Pc[:, 0] / z + cx, fy * Pc[:, 1] / z + cy], 1), Pc[:, 2]
+
+    def frame(R, t, n, salt, is_cur):
+        r = np.random.Generator(np.random.PCG64(seed * 977 + salt))
+        uv, z = project(R, t, X)
+        vis = np.nonzero((z > 0.3) & (uv[:, 0] > 16) & (uv[:, 0] < w - 16) & (uv[:, 1] > 16) & (uv[:, 1] < h - 16))[0]
+        if not is_cur:
+            vis = vis[r.random(len(vis)) < 0.85][:n - n // 8]
+        nv = len(vis)
+        n_dup = 0 if is_cur else min(n - nv, nv // 8)                        # near misses: a second feature a few pixels off the true one
+        k = np.zeros(n, KP_NP); pid = np.full(n, -1, np.int64)
+        sig = np.where(r.random(nv) < 0.12, 6.0, 0.6)                        # a share far above the chi2 gates
+        octv = base_oct[vis] if is_cur else np.clip(base_oct[vis] + r.integers(-1, 2, nv), 0, 7)
+        if not is_cur:
+            bad = r.random(nv) < 0.08
+            octv = np.where(bad, (base_oct[vis] + 4) % 8, octv)              # violates scale consistency
+        k["x"][:nv] = uv[vis, 0] + r.normal(0, 1, nv) * sig; k["y"][:nv] = uv[vis, 1] + r.normal(0, 1, nv) * sig
+        k["octave"][:nv] = octv; pid[:nv] = vis
+        dup = r.choice(nv, n_dup, replace=False) if n_dup else np.zeros(0, np.int64)
+        ang = r.uniform(0, 2 * np.pi, n_dup); rad = r.uniform(2.5, 9.0, n_dup)
+        k["x"][nv:nv + n_dup] = k["x"][dup] + rad * np.cos(ang); k["y"][nv:nv + n_dup] = k["y"][dup] + rad * np.sin(ang)
+        k["octave"][nv:nv + n_dup] = k["octave"][dup]
+        near = np.full(n, -1, np.int64); near[nv:nv + n_dup] = vis[dup] if n_dup else 0
+        m = nv + n_dup
+        k["x"][m:] = r.uniform(16, w - 16, n - m); k["y"][m:] = r.uniform(16, h - 16, n - m); k["octave"][m:] = r.integers(0, 8, n - m)
+        k["angle"] = r.uniform(0, 360, n); k["angle"][:nv] = (base_angle[vis] + r.normal(0, 3, nv)) % 360
+        k["size"] = 31 * sf[k["octave"]]; k["class_id"] = -1
+        d = r.integers(0, 256, (n, 32), dtype=np.uint8); d[:nv] = base_desc[vis]; d[nv:m] = base_desc[vis[dup]] if n_dup else d[nv:m]
+        for _ in range(9):
+            bsel = r.integers(0, 256, m); d[np.arange(m), bsel >> 3] ^= (1 << (bsel & 7)).astype(np.uint8)
+        node = r.integers(0, 80, n).astype(np.int32); node[:nv] = base_node[vis]
+        if n_dup:
+            node[nv:m] = base_node[vis[dup]]
+        node[r.random(n) < 0.02] = -1
+        zt = np.full(n, -1.0); zt[:nv] = z[vis]
+        if n_dup:
+            zt[nv:m] = z[vis[dup]]
+        stereo = (r.random(n) < stereo_frac) & (zt > 0) & (zt < 40.0)
+        zn = zt * (1 + r.normal(0, 0.01, n))
+        ur = np.where(stereo, k["x"] - mbf / np.where(stereo, zn, 1.0) + r.normal(0, 0.4, n), -1.0).astype(np.float32)
+        dep = np.where(stereo, zn, -1.0).astype(np.float32)
+        hp = (r.random(n) < 0.3).astype(np.uint8)
+        # the distorted key points KeyFrame::UnprojectStereo reads: a mild radial shift of the undistorted ones
+        dx, dy = (k["x"] - cx) / fx, (k["y"] - cy) / fy
+        rr = dx * dx + dy * dy
+        xy_dist = np.stack([cx + fx * dx * (1 - 0.02 * rr), cy + fy * dy * (1 - 0.02 * rr)], 1).astype(np.float32)
+        perm = r.permutation(n)
+        Ow = (-R.T @ t).astype(np.float32)
+        return dict(kps=k[perm], desc=d[perm], node=node[perm], hp=hp[perm], ur=ur[perm], depth=dep[perm], xy_dist=np.ascontiguousarray(xy_dist[perm]),
+                    pid=pid[perm], near=near[perm], pose12=np.concatenate([R.ravel(), t]).astype(np.float32), Ow=Ow, R=R, t=t)
+
+    kf1 = frame(R1, t1, n1, 1, True)
+    of_pid1 = np.full(n1, -1, np.int64); of_pid1[kf1["pid"][kf1["pid"] >= 0]] = np.nonzero(kf1["pid"] >= 0)[0]
+    C1 = -R1.T @ t1
+    baselines = np.concatenate([[0.004, 0.03], np.geomspace(0.08, 1.6, max(J - 2, 1))])[:J]
+    neigh = []
+    for j in range(J):
+        dirn = rng.normal(0, 1, 3) * np.array([1.0, 0.4, 0.6]); dirn /= np.linalg.norm(dirn)
+        yaw = rng.normal(0, 0.06, 3)
+        if j % 5 == 4:
+            yaw = yaw + np.array([0.0, rng.choice([-1.0, 1.0]) * 0.45, 0.0])  # looks sideways: wrong partners triangulate behind a camera
+        R2 = _rotvec_to_R(yaw) @ R1
+        C2 = C1 + baselines[j] * dirn
+        t2 = -R2 @ C2
+        kf = frame(R2, t2, n2, 100 + j, False)
+        R12 = R1 @ R2.T; t12 = -R12 @ t2 + t1
+        tx = np.array([[0, -t12[2], t12[1]], [t12[2], 0, -t12[0]], [-t12[1], t12[0], 0]])
+        kf["F12"] = (Kinv.T @ tx @ R12 @ Kinv).astype(np.float32)
+        _, z2 = project(R2, t2, X[:n_near])
+        kf["median_depth"] = f32(np.median(z2[z2 > 0]))
+        kf["kf2_first"] = np.uint8(rng.integers(0, 2))
+        # match12 from the truth: true partners, near misses, wrong partners, and unmatched
+        of_pid2 = np.full(n1, -1, np.int64); sel = kf["pid"] >= 0; of_pid2[kf["pid"][sel]] = np.nonzero(sel)[0]
+        near_of = np.full(n1, -1, np.int64); sel = kf["near"] >= 0; near_of[kf["near"][sel]] = np.nonzero(sel)[0]
+        mg = np.full(n1, -1, np.int32)
+        for i1 in range(n1):
+            p = kf1["pid"][i1]
+            u = rng.random()
+            if p >= 0 and of_pid2[p] >= 0 and u < 0.8:
+                mg[i1] = near_of[p] if (near_of[p] >= 0 and u < 0.25) else of_pid2[p]
+            elif u > 0.88:
+                mg[i1] = rng.integers(0, n2)
+        kf["match_gen"] = mg
+        neigh.append(kf)
+    return dict(cam=cam, kf1=kf1, neigh=neigh, bounds=np.array([0, w, 0, h], np.float32), X=X)
