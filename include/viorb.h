@@ -745,6 +745,93 @@ int viorb_create_new_map_points(const viorb_mapping_camera* cam, int monocular, 
                                 const float* Ow2, const float* F12, const float* median_depth2, const uint8_t* kf2_first, int J,
                                 int cap, int pcap, int32_t* new_idx, float* new_pts_f, uint8_t* new_desc, int* n_new);
 
+/* ------------------------------------------------------------------------------------------------
+ * Visual-inertial initialisation — the arithmetic of LocalMapping::TryInitVIO (reference src/LocalMapping.cc:191-786) from the
+ * snapshot of the key frames to the estimate of gyro bias, scale, gravity and accelerometer bias (:279-504) and to the NavStates,
+ * poses and pre-integrations written back (:585-786), for a ragged batch of independent streams. Key frame i of stream b is row [b][i] of every array; max_kf is the row pitch. The IMU samples of all streams live in one
+ * pooled imu[total_imu][7] (gyro3 acc3 t); imu_start[b][max_kf + 1] holds int32 offsets into it: interval i = the samples between key
+ * frame i - 1 and key frame i = [imu_start[b][i], imu_start[b][i + 1]); interval 0 is empty. An interval whose offsets are reversed,
+ * negative or beyond total_imu is treated as empty, never read.
+ * These calls keep NO scratch of their own: every work array is an argument, so concurrent calls on different streams cannot race.
+ * The *_device forms only enqueue on `stream`; the host forms are single-stream, upload, run the device form and download.
+ * GlobalBundleAdjustmentNavState (:804), the bVIOInited time test (:560), the log files and all locking stay with the caller.
+ * ---------------------------------------------------------------------------------------------- */
+#define VIORB_VI_INVALID      1   /* status[b]: fewer than 4 key frames (fewer than 6 rows; fewer than 2 for the gyro bias alone), n > max_kf,
+                                     or an interval inside the set without samples / with a total dt <= 0 */
+#define VIORB_VI_DEGENERATE   2   /* status[b]: a singular value of A or C is under the reference's 1e-10 guard (:372, :481) or under 1e-7 of
+                                     the largest one — what a Gram-matrix solve in double resolves (eigenvalues of A^T A carry an absolute error
+                                     near 2^-53 |A|^2, i.e. singular values one near 1.5e-8 |A|); the 3 x 3 gyro system is singular; or gw* is
+                                     zero or parallel to [0 0 1], where the reference divides by zero (:409) */
+#define VIORB_PREINT_NO_CLAMP 1   /* flags of viorb_preintegrate_intervals*: see below */
+
+typedef struct viorb_vi_init_config {
+    double Tbc[16];                       /* ConfigParam::GetMatTbc(), row-major 4 x 4 */
+    double g;                             /* ConfigParam::GetG() */
+    double gyr_meas_cov, acc_meas_cov;    /* as in viorb_frontend_config: <= 0 selects the reference constants */
+} viorb_vi_init_config;
+
+/* Pre-integration of every (stream, interval) of a batch in one launch: preint[b][i][142] for 1 <= i < n_kf[b]; row 0, rows >= n_kf[b]
+ * and intervals without samples are the reset pre-integrator (identity dR, zeros). The first sample covers [t of key frame i - 1, its
+ * stamp], sample k runs until the next stamp, the last until key frame i's time. bg / ba [b][3]: NULL = zero.
+ * flags = 0 clamps every dt at 0 like KeyFrameInit::ComputePreInt (src/LocalMapping.cc:58-94, `std::max(0., ...)`);
+ * VIORB_PREINT_NO_CLAMP follows KeyFrame::ComputePreInt (src/KeyFrame.cc:193-260), which does not. */
+int viorb_preintegrate_intervals_device(const int32_t* n_kf, const double* kf_time, const int32_t* imu_start, const double* imu,
+                                        int64_t total_imu, const double* bg, const double* ba, double gyr_meas_cov, double acc_meas_cov,
+                                        int flags, int max_kf, int batch, double* preint, void* stream);
+/* One stream, host buffers: kf_time[n_kf], imu_start[n_kf + 1] (imu_start[n_kf] = number of samples), preint[n_kf][142]. */
+int viorb_preintegrate_intervals(int n_kf, const double* kf_time, const int32_t* imu_start, const double* imu, const double bg[3],
+                                 const double ba[3], double gyr_meas_cov, double acc_meas_cov, int flags, double* preint);
+
+/* Optimizer::OptimizeInitialGyroBias(vTwc, vImuPreInt) (src/Optimizer.cc:3138-3199; also Tracking.cc:67 after a relocalisation): one
+ * Gauss-Newton step from bg = 0 over the n_est[b] - 1 EdgeGyrBias (src/IMU/g2otypes.cpp:1327-1351) of a stream, weighted — as the
+ * reference does — with the rotation block of the pre-integration COVARIANCE. twc12[b][i] = KeyFrame::GetPoseInverse() as float
+ * Rwc(9) twc(3); preint_in[b][i][142] = the key frames' current pre-integrations. Out: bg[b][3], status[b]. */
+int viorb_optimize_initial_gyro_bias_device(const viorb_vi_init_config* cfg, const int32_t* n_est, const float* twc12,
+                                            const double* preint_in, int max_kf, int batch, double* bg, int32_t* status, void* stream);
+int viorb_optimize_initial_gyro_bias(const viorb_vi_init_config* cfg, int n, const float* twc12, const double* preint_in, double bg[3],
+                                     int32_t* status);
+
+/* Steps 1-3 of TryInitVIO (src/LocalMapping.cc:279-504) for the first n_est[b] key frames of every stream: the gyro bias as above; the
+ * re-integration of all intervals with it (no accelerometer bias, dt clamped, :285-292) into preint_bg[b][max_kf][142], which is both
+ * an output and the call's only work array (required); x = [s*, gw*] from A x = B and y = [s, dtheta_xy, ba] from C y = D, rows built
+ * and solved in double. est[b][48] = bg3 s* gw*3 s dtheta2 ba3 Rwi9 Rwi_9 gw3 w4 w2_6 (w: the singular values of A and C, descending;
+ * 44 used, the rest zero). status[b] = VIORB_OK, VIORB_VI_INVALID or VIORB_VI_DEGENERATE; est of a stream that is not OK is all zero.
+ * Streams do not influence one another. Three kernels on `stream`, no host synchronisation. */
+int viorb_vi_init_device(const viorb_vi_init_config* cfg, const int32_t* n_est, const double* kf_time, const int32_t* imu_start,
+                         const double* imu, int64_t total_imu, const float* twc12, const double* preint_in, int max_kf, int batch,
+                         double* est, int32_t* status, double* preint_bg, void* stream);
+/* One stream, host buffers (the LocalMapping thread's form); preint_bg [n_est][142] may be NULL here. */
+int viorb_vi_init(const viorb_vi_init_config* cfg, int n_est, const double* kf_time, const int32_t* imu_start, const double* imu,
+                  const float* twc12, const double* preint_in, double est[48], int32_t* status, double* preint_bg);
+
+/* Writing the estimate back (src/LocalMapping.cc:585-786) for the n_kf[b] >= n_est[b] key frames of every stream with status[b] ==
+ * VIORB_OK; the rows of other streams are left untouched. Two kernels on `stream`:
+ *   preint[b][i][142]        the final KeyFrame::ComputePreInt (:683-688, :729-735): bg AND ba of the estimate subtracted, no clamp;
+ *   navstate[b][i][22]       P = s wPc + Rwc pcb, R = Rwc Rcb, bg, ba, both deltas zero (:631-642, :721-749). V of key frame i:
+ *                            i < n_est - 1: the forward formula (:659) from preint_v[b][i + 1]; i = n_est - 1 (the newest of the
+ *                            estimate): the backward formula (:677) from preint_v[b][i] and the V, R just given to i - 1;
+ *                            n_est <= i < n_kf - 1 (key frames inserted while the estimate ran): forward (:765) from the FINAL
+ *                            preint[b][i + 1]; i = n_kf - 1 > n_est - 1: backward (:780) from the final preint[b][i]. A forward
+ *                            formula over an interval of no duration gives V = 0 (the reference divides by zero).
+ *   pose12_scaled[b][i][12]  Tcw = Rcw(9) tcw(3) of pose12 with tcw * (float)s (:691-699); may alias pose12.
+ * preint_v: the pre-integrations the velocity formulas of the estimate's key frames read. The reference reads the key frames' own at
+ * that moment (what was passed as preint_in); viorb_vi_init_device's preint_bg holds the ones re-integrated with the new gyro bias.
+ * The trailing key frames' positions are s wPc taken directly; the reference reads them back from the float pose it has just
+ * rescaled (one float rounding of the pose apart). preint must not be preint_v. */
+int viorb_vi_init_apply_device(const viorb_vi_init_config* cfg, const int32_t* n_est, const int32_t* n_kf, const double* kf_time,
+                               const int32_t* imu_start, const double* imu, int64_t total_imu, const float* twc12, const float* pose12,
+                               const double* est, const int32_t* status, const double* preint_v, int max_kf, int batch,
+                               double* navstate, float* pose12_scaled, double* preint, void* stream);
+/* One stream whose estimate is OK, host buffers: every array has n_kf rows, preint_v included (n_kf * 142 doubles are uploaded from it;
+ * only its first n_est rows are read by the kernel). */
+int viorb_vi_init_apply(const viorb_vi_init_config* cfg, int n_est, int n_kf, const double* kf_time, const int32_t* imu_start,
+                        const double* imu, const float* twc12, const float* pose12, const double est[48], const double* preint_v,
+                        double* navstate, float* pose12_scaled, double* preint);
+/* MapPoint::UpdateScale (src/MapPoint.cc:73-78) in place over points[b][np][3], min_dist[b][np], max_dist[b][np] (either distance array
+ * may be NULL): every element times (float)s of its stream, for the streams with status[b] == VIORB_OK. */
+int viorb_scale_map_points_device(float* points, float* min_dist, float* max_dist, const double* est, const int32_t* status, int np,
+                                  int batch, void* stream);
+
 /* Host-only test hooks (no GPU needed; used by the CPU test-suite to compare product host code with
  * the oracle): the flat-array formulation of DistributeOctTree that the device kernel mirrors
  * (keys packed x | y<<12 | score<<24, border-relative), and the scalar math shared with the kernels. */
@@ -771,6 +858,21 @@ int viorb_debug_map_point_update(const int32_t* obs_start, const int32_t* obs_kf
                                  const float* Pw, int p, const int64_t* kf_row_base, const float* kf_Ow, int nkf,
                                  const uint8_t* desc_rows, const int32_t* octave_rows, int64_t pool_rows,
                                  const viorb_mapping_camera* cam, uint8_t* pts_desc32, int32_t* best_obs, float* pts_f8);
+/* vi_init_core.h (the arithmetic of the initialisation kernels) compiled for the host: one EdgeGyrBias at bg = 0 (error, Jacobian and,
+ * when Hg12 is not NULL, its terms J^T W J (9) and J^T W e (3)); bg = -H^-1 g from such summed terms; the rows one key-frame triplet
+ * adds to A | B ([3][5]) and to C | D ([3][7]; twc36 = three poses, preint2 / preint3 = the pre-integrations of the second and third);
+ * the small least-squares solve for n = 4 or 6 columns (M [m][n] row-major; x [n], w [n] singular values; returns VIORB_OK or
+ * VIORB_VI_DEGENERATE); Rwi from gw*. */
+void viorb_debug_vi_init_gyro_edge(const double* Tbc16, const float* twc_i12, const float* twc_j12, const double* preint142, double* e3,
+                                   double* J9, double* Hg12);
+int viorb_debug_vi_init_gyro_solve(const double* Hg12, double* bg3);
+void viorb_debug_vi_init_rows(const double* Tbc16, const float* twc36, const double* preint2, const double* preint3, const double* Rwi9,
+                              double g, double* rows_ab15, double* rows_cd21);
+int viorb_debug_vi_init_solve(const double* M, const double* v, int m, int n, double* x, double* w);
+int viorb_debug_vi_init_rwi(const double* gwstar3, double* Rwi9);
+/* the NavState viorb_vi_init_apply writes for key frame i of one stream (twc12 [n_kf][12], preint_v / preint_final [n_kf][142]) */
+void viorb_debug_vi_init_navstate(const double* Tbc16, int i, int n_est, int n_kf, const float* twc12, const double* est48,
+                                  const double* preint_v, const double* preint_final, double* ns22);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,7 @@ KP_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("size", "f4"), ("angle", "f4"),
                      ("response", "f4"), ("octave", "i4"), ("class_id", "i4")])
 
 VIORB_OK, ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_CAPACITY, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
+VI_INVALID, VI_DEGENERATE, PREINT_NO_CLAMP = 1, 2, 1          # viorb_vi_init status codes; viorb_preintegrate_intervals flag
 
 
 class ViorbError(RuntimeError):
@@ -59,6 +60,11 @@ class MappingCamera(C.Structure):
     """viorb_mapping_camera (include/viorb.h)."""
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("mb", C.c_float), ("mbf", C.c_float),
                 ("scale_factor", C.c_float), ("nlevels", C.c_int32), ("scale_factors", C.c_float * 16), ("level_sigma2", C.c_float * 16)]
+
+
+class ViInitConfig(C.Structure):
+    """viorb_vi_init_config (include/viorb.h)."""
+    _fields_ = [("Tbc", C.c_double * 16), ("g", C.c_double), ("gyr_meas_cov", C.c_double), ("acc_meas_cov", C.c_double)]
 
 
 class TrackerConfig(C.Structure):
@@ -195,6 +201,21 @@ SIGNATURES = {
     "viorb_create_new_map_points": (i32, [vp, i32] + [vp] * 7 + [i32] + [vp] * 15 + [i32] * 3 + [vp] * 3 + [PP(i32)]),
     "viorb_debug_triangulate_pair": (i32, [vp] * 6 + [i32, vp, i32, vp]),
     "viorb_debug_map_point_update": (i32, [vp] * 5 + [i32, vp, vp, i32, vp, vp, C.c_int64] + [vp] * 4),
+    "viorb_preintegrate_intervals_device": (i32, [vp, vp, vp, vp, C.c_int64, vp, vp, C.c_double, C.c_double, i32, i32, i32, vp, vp]),
+    "viorb_preintegrate_intervals": (i32, [i32, vp, vp, vp, vp, vp, C.c_double, C.c_double, i32, vp]),
+    "viorb_optimize_initial_gyro_bias_device": (i32, [PP(ViInitConfig), vp, vp, vp, i32, i32, vp, vp, vp]),
+    "viorb_optimize_initial_gyro_bias": (i32, [PP(ViInitConfig), i32, vp, vp, vp, vp]),
+    "viorb_vi_init_device": (i32, [PP(ViInitConfig), vp, vp, vp, vp, C.c_int64, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "viorb_vi_init": (i32, [PP(ViInitConfig), i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "viorb_vi_init_apply_device": (i32, [PP(ViInitConfig)] + [vp] * 5 + [C.c_int64] + [vp] * 5 + [i32, i32] + [vp] * 4),
+    "viorb_vi_init_apply": (i32, [PP(ViInitConfig), i32, i32] + [vp] * 10),
+    "viorb_scale_map_points_device": (i32, [vp] * 5 + [i32, i32, vp]),
+    "viorb_debug_vi_init_navstate": (None, [vp, i32, i32, i32] + [vp] * 5),
+    "viorb_debug_vi_init_gyro_edge": (None, [vp] * 7),
+    "viorb_debug_vi_init_gyro_solve": (i32, [vp, vp]),
+    "viorb_debug_vi_init_rows": (None, [vp] * 5 + [C.c_double, vp, vp]),
+    "viorb_debug_vi_init_solve": (i32, [vp, vp, i32, i32, vp, vp]),
+    "viorb_debug_vi_init_rwi": (i32, [vp, vp]),
 }
 
 _lib = None

@@ -7,6 +7,8 @@
 //                           for all neighbours in one call                                              src/LocalMapping.cc:1242-1464
 //   update_map_points       MapPoint::ComputeDistinctiveDescriptors + MapPoint::UpdateNormalAndDepth for a list of points
 //                                                                                                       src/MapPoint.cc:249-314, 337-378
+//   try_init_vio            LocalMapping::TryInitVIO steps 1-3: gyro bias, scale, gravity, accelerometer bias  src/LocalMapping.cc:279-504
+//   try_init_vio_apply      the NavState / pose / map-point write-back once bVIOInited                         src/LocalMapping.cc:585-786
 //
 // KeyFrame members read: N, mvKeysUn, mvKeys, mvuRight, mvDepth, mDescriptors, mFeatVec, GetMapPoint, GetPose, GetCameraCenter, isBad,
 // fx fy cx cy mb mbf, mfScaleFactor, mnScaleLevels, mvScaleFactors, mvLevelSigma2. One accessor the reference does not have is needed
@@ -147,6 +149,95 @@ inline void update_map_points(const std::vector<MapPointT*>& vpMPs) {
         for (int c = 0; c < 3; c++) nrm.at<float>(c) = pf[(size_t)p * 8 + 3 + c];
         pts[p]->SetDescriptorNormalAndDepth(d, nrm, pf[(size_t)p * 8 + 6], pf[(size_t)p * 8 + 7]);
     }
+}
+
+// ---- LocalMapping::TryInitVIO -------------------------------------------------------------------------------------------------
+// What try_init_vio leaves for the log lines (:527-547), mnVINSInitScale, mGravityVec, mRwiInit and for try_init_vio_apply.
+struct VioInitEstimate {
+    int32_t status;                        // VIORB_OK, VIORB_VI_INVALID (too few key frames, an interval without samples), VIORB_VI_DEGENERATE
+    double est[48];                        // bg3 s* gw*3 s dtheta2 ba3 Rwi9 Rwi_9 gw3 w4 w2_6 (include/viorb.h); all zero unless status == VIORB_OK
+    std::vector<double> preint_bg;         // [N][142]: KeyFrameInit::ComputePreInt with the new gyro bias
+    std::vector<double> preint;            // [n_kf][142] after try_init_vio_apply: the final KeyFrame::ComputePreInt of every key frame
+    double scale() const { return est[7]; }
+};
+
+// kf_time, Twc, the pooled IMU samples and their offsets of a key-frame vector in map order (vpKFs[i]'s samples lie between
+// vpKFs[i - 1] and vpKFs[i]; those of vpKFs[0] are not used).
+template <class KeyFrameT>
+inline void flatten_vio_keyframes(const std::vector<KeyFrameT*>& vpKFs, std::vector<double>& t, std::vector<float>& twc12, std::vector<float>* tcw12,
+                                  std::vector<double>& imu, std::vector<int32_t>& imu_start) {
+    const size_t n = vpKFs.size();
+    t.resize(n); twc12.resize(n * 12); imu.clear(); imu_start.assign(n + 1, 0);
+    if (tcw12) tcw12->resize(n * 12);
+    for (size_t i = 0; i < n; i++) {
+        KeyFrameT* pKF = vpKFs[i];
+        t[i] = pKF->mTimeStamp;
+        flatten_pose(pKF->GetPoseInverse(), &twc12[i * 12]);                   // Rwc(9) twc(3)
+        if (tcw12) flatten_pose(pKF->GetPose(), &(*tcw12)[i * 12]);
+        if (i > 0) {
+            const auto v = pKF->GetVectorIMUData();
+            for (size_t k = 0; k < v.size(); k++) {
+                for (int c = 0; c < 3; c++) imu.push_back(v[k]._g[c]);
+                for (int c = 0; c < 3; c++) imu.push_back(v[k]._a[c]);
+                imu.push_back(v[k]._t);
+            }
+        }
+        imu_start[i + 1] = (int32_t)(imu.size() / 7);
+    }
+    if (imu.empty()) imu.resize(7, 0.0);
+}
+template <class Mat4> inline viorb_vi_init_config vio_config(const Mat4& Tbc, double g) {
+    viorb_vi_init_config c;
+    for (int r = 0; r < 4; r++) for (int k = 0; k < 4; k++) c.Tbc[4 * r + k] = Tbc(r, k);
+    c.g = g; c.gyr_meas_cov = 0; c.acc_meas_cov = 0;                            // the reference constants of src/IMU/imudata.cpp
+    return c;
+}
+
+// Steps 1-3 of TryInitVIO on vScaleGravityKF (all key frames of the map, in order) after the snapshot loop of :264-275. Tbc =
+// ConfigParam::GetEigTbc(), g = ConfigParam::GetG(). Returns true when an estimate exists (status == VIORB_OK); a GPU error throws.
+template <class KeyFrameT, class Mat4>
+inline bool try_init_vio(const std::vector<KeyFrameT*>& vScaleGravityKF, const Mat4& Tbc, double g, VioInitEstimate& out) {
+    const int N = (int)vScaleGravityKF.size();
+    out.status = VIORB_VI_INVALID; std::fill(out.est, out.est + 48, 0.0); out.preint_bg.assign((size_t)std::max(N, 1) * 142, 0.0); out.preint.clear();
+    if (N < 1) return false;
+    std::vector<double> t, imu, pre((size_t)N * 142); std::vector<float> twc; std::vector<int32_t> start;
+    flatten_vio_keyframes(vScaleGravityKF, t, twc, (std::vector<float>*)0, imu, start);
+    for (int i = 0; i < N; i++) pack_preint(vScaleGravityKF[i]->GetIMUPreInt(), &pre[(size_t)i * 142]);
+    const viorb_vi_init_config cfg = vio_config(Tbc, g);
+    check(viorb_vi_init(&cfg, N, &t[0], &start[0], &imu[0], &twc[0], &pre[0], out.est, &out.status, &out.preint_bg[0]), "TryInitVIO");
+    return out.status == VIORB_OK;
+}
+
+// The write-back of :585-786 under mMutexMapUpdate, once the caller's time test (:560) has set bVIOInited: vpAllKFs = the key frames
+// the map holds NOW, in order, whose first nEst are those try_init_vio saw. Per key frame: SetNavStatePos / Vel / Rot / BiasGyr /
+// BiasAcc / DeltaBg / DeltaBa and SetPose with the rescaled Tcw; per map point UpdateScale((float)s). The velocities of the estimate's
+// key frames read the key frames' OWN pre-integrations, as the reference does at that moment. The final pre-integrations come back in
+// est.preint ([n][142]); the reference's pKF->ComputePreInt() loops (:683-688, :729-735) may stay as they are (they read the biases
+// just set) or be replaced by loading est.preint. Vec3 / Quat / SO3T = Eigen::Vector3d, Eigen::Quaterniond, Sophus::SO3.
+template <class Vec3, class Quat, class SO3T, class KeyFrameT, class MapPointT, class Mat4>
+inline void try_init_vio_apply(const std::vector<KeyFrameT*>& vpAllKFs, int nEst, const Mat4& Tbc, double g, VioInitEstimate& est,
+                               const std::vector<MapPointT*>& vpMapPoints) {
+    const int n = (int)vpAllKFs.size();
+    if (est.status != VIORB_OK || nEst < 4 || n < nEst) throw std::runtime_error("try_init_vio_apply: no estimate to apply");
+    std::vector<double> t, imu, pv((size_t)n * 142, 0.0), ns((size_t)n * 22); std::vector<float> twc, tcw, scaled((size_t)n * 12); std::vector<int32_t> start;
+    flatten_vio_keyframes(vpAllKFs, t, twc, &tcw, imu, start);
+    for (int i = 0; i < nEst; i++) pack_preint(vpAllKFs[i]->GetIMUPreInt(), &pv[(size_t)i * 142]);   // rows >= nEst are not read
+    est.preint.assign((size_t)n * 142, 0.0);
+    const viorb_vi_init_config cfg = vio_config(Tbc, g);
+    check(viorb_vi_init_apply(&cfg, nEst, n, &t[0], &start[0], &imu[0], &twc[0], &tcw[0], est.est, &pv[0], &ns[0], &scaled[0], &est.preint[0]), "TryInitVIO write-back");
+    for (int i = 0; i < n; i++) {
+        KeyFrameT* pKF = vpAllKFs[i];
+        const double* o = &ns[(size_t)i * 22];
+        pKF->SetNavStatePos(Vec3(o[0], o[1], o[2])); pKF->SetNavStateVel(Vec3(o[3], o[4], o[5]));
+        pKF->SetNavStateRot(SO3T(Quat(o[9], o[6], o[7], o[8])));                // Eigen::Quaterniond(w, x, y, z)
+        pKF->SetNavStateBiasGyr(Vec3(o[10], o[11], o[12])); pKF->SetNavStateBiasAcc(Vec3(o[13], o[14], o[15]));
+        pKF->SetNavStateDeltaBg(Vec3(o[16], o[17], o[18])); pKF->SetNavStateDeltaBa(Vec3(o[19], o[20], o[21]));
+        cv::Mat Tcw = pKF->GetPose();                                            // row 3 and the rotation stay
+        for (int r = 0; r < 3; r++) Tcw.template at<float>(r, 3) = scaled[(size_t)i * 12 + 9 + r];
+        pKF->SetPose(Tcw);
+    }
+    const float sf = (float)est.scale();
+    for (size_t p = 0; p < vpMapPoints.size(); p++) if (vpMapPoints[p]) vpMapPoints[p]->UpdateScale(sf);
 }
 
 } // namespace viorb_shim

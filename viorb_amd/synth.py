@@ -791,3 +791,50 @@ def make_mapping_problem(seed, J=20, n1=1000, n2=1000, stereo_frac=0.0, w=752, h
         kf["match_gen"] = mg
         neigh.append(kf)
     return dict(cam=cam, kf1=kf1, neigh=neigh, bounds=np.array([0, w, 0, h], np.float32), X=X)
+
+
+def make_vi_init_problem(seed, N, kf_dt=0.25, imu_dt=0.005, scale=3.7, noise=0.0, G=9.8012, Tbc=None):
+    """A stream for the visual-inertial initialisation (LocalMapping::TryInitVIO) with its truth: N key frames kf_dt apart on a smooth
+    body trajectory with translational and rotational excitation; IMU samples every imu_dt with the true biases added (and, with
+    noise > 0, white noise of noise * 0.01 rad/s and noise * 0.1 m/s^2 per sample); key-frame camera poses Twb Tbc with positions
+    divided by `scale`; the world frame rotated so that gravity is a general vector. Tbc: use this camera-body transform instead of the
+    seed's own (streams of one batch share a configuration).
+    Returns dict(twc12 [N,12] f32 = Rwc(9) twc(3), kf_time [N], imu [total,7], imu_start [N+1] (interval i = samples between key frames
+    i - 1 and i), Tbc [4,4], g, truth = dict(s, gw, bg, ba, kf_vel [N,3] = body velocity in the world frame at the key frames))."""
+    r = np.random.default_rng(seed)
+    amp, fr, ph = r.uniform(0.3, 1.0, 3), r.uniform(0.2, 0.8, 3), r.uniform(0, 6.28, 3)
+    ramp, rfr, rph = r.uniform(0.1, 0.4, 3), r.uniform(0.2, 0.7, 3), r.uniform(0, 6.28, 3)
+    pos = lambda t: amp * np.sin(2 * np.pi * fr * t + ph)
+    acc = lambda t: -amp * (2 * np.pi * fr) ** 2 * np.sin(2 * np.pi * fr * t + ph)
+    Rw0 = _rotvec_to_R(r.normal(size=3))                      # visual world against the inertial frame
+    gw = Rw0 @ np.array([0, 0, G])
+    Rot = lambda t: Rw0 @ _rotvec_to_R(ramp * np.sin(2 * np.pi * rfr * t + rph))
+    bg, ba = r.normal(size=3) * 0.02, r.normal(size=3) * 0.1
+    own = np.eye(4)
+    own[:3, :3] = _rotvec_to_R(r.normal(size=3) * 0.5 + np.array([0, 0, 1.57])); own[:3, 3] = r.normal(size=3) * 0.05
+    Tbc = own if Tbc is None else np.asarray(Tbc, np.float64).reshape(4, 4)
+    n_imu = int(round(kf_dt / imu_dt))
+    tk = np.arange(N) * kf_dt
+    twc12 = np.zeros((N, 12), np.float32)
+    chunks, start = [], np.zeros(N + 1, np.int32)
+    for i in range(N):
+        Twb = np.eye(4); Twb[:3, :3] = Rot(tk[i]); Twb[:3, 3] = Rw0 @ pos(tk[i])
+        T = Twb @ Tbc
+        twc12[i, :9] = T[:3, :3].ravel(); twc12[i, 9:] = T[:3, 3] / scale
+        if i > 0:
+            S = np.zeros((n_imu, 7))
+            for k in range(n_imu):
+                t0 = tk[i - 1] + k * imu_dt
+                tm = t0 + imu_dt / 2
+                dR = Rot(t0).T @ Rot(t0 + imu_dt)             # the constant rate that carries R(t0) to R(t0 + imu_dt)
+                th = np.arccos(np.clip((np.trace(dR) - 1) / 2, -1, 1))
+                w = np.array([dR[2, 1] - dR[1, 2], dR[0, 2] - dR[2, 0], dR[1, 0] - dR[0, 1]]) / (2 * np.sin(th)) * th / imu_dt if th > 1e-12 else np.zeros(3)
+                a = Rot(tm).T @ (Rw0 @ acc(tm) - gw)
+                S[k, :3] = w + bg + r.normal(size=3) * noise * 0.01
+                S[k, 3:6] = a + ba + r.normal(size=3) * noise * 0.1
+                S[k, 6] = t0
+            chunks.append(S)
+        start[i + 1] = start[i] + (n_imu if i > 0 else 0)
+    imu = np.concatenate(chunks) if chunks else np.zeros((0, 7))
+    kf_vel = np.stack([Rw0 @ (amp * 2 * np.pi * fr * np.cos(2 * np.pi * fr * t + ph)) for t in tk])
+    return dict(twc12=twc12, kf_time=tk, imu=imu, imu_start=start, Tbc=Tbc, g=G, truth=dict(s=scale, gw=gw, bg=bg, ba=ba, kf_vel=kf_vel))
