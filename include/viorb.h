@@ -874,6 +874,49 @@ int viorb_debug_vi_init_rwi(const double* gwstar3, double* Rwi9);
 void viorb_debug_vi_init_navstate(const double* Tbc16, int i, int n_est, int n_kf, const float* twc12, const double* est48,
                                   const double* preint_v, const double* preint_final, double* ns22);
 
+/* Optimizer::GlobalBundleAdjustmentNavState (reference src/Optimizer.cc:50-320; called after a successful TryInitVIO,
+ * src/LocalMapping.cc:802-805, and by LoopClosing::RunGlobalBundleAdjustment, src/LoopClosing.cc:683): every key frame of the map in
+ * one solve. Vertices: a PVR (9) and an accelerometer-bias (3) block per key frame (src/IMU/g2otypes.h:16-75; NOT_UPDATE_GYRO_BIAS,
+ * src/IMU/NavState.h:8), both fixed where fixed[i] != 0 (the reference fixes mnId == 0, :91-97); np marginalised points
+ * (VertexSBAPointXYZ); a point without an edge is left out and keeps its position (:234-242, point_included[p] = 0). Factors: for
+ * every key frame i with prev[i] >= 0 (GetPrevKeyFrame) one EdgeNavStatePVR on (PVR prev, PVR i, bias prev) with information
+ * getCovPVPhi()^-1 and one EdgeNavStateBias with information I / accBiasRW2 / deltaTime (:116-172), preint[i] being the
+ * pre-integration of the interval ending at i (row ignored where prev[i] < 0); one EdgeNavStatePVRPointXYZ per observation with
+ * information invSigma2 I (:189-232). cfg->robust (bRobust): Huber sqrt(5.99) on the observations, sqrt(21.666) / sqrt(16.812) on the
+ * IMU / bias factors, each delta a float squared in double (:105-106, :174); without it chi2 is the plain sum. Solver: ONE
+ * optimize(cfg->iterations) of g2o's Levenberg with the point block eliminated (Thirdparty/g2o/g2o/core/block_solver.hpp:367-486,
+ * optimization_algorithm_levenberg.cpp:61-164) — no classification round, no erase list (:245-247). An IMU factor between two fixed key
+ * frames contributes to chi2 only. stop: pbStopFlag (:75-76, may be NULL), polled by the host-side Levenberg control before every
+ * iteration and after every trial; raised before the call, the inputs come back unchanged with info[2] = 0.
+ * kfs [nk][22] in an order with prev[i] < i, points [np][3], edge_idx [ne][2] = (point, key frame) sorted by point, edge_obs [ne][3] =
+ * u v invSigma2. Outputs: kfs_out [nk][22] (dBias from the bias vertex, :259-265; fixed rows copied), points_out [np][3],
+ * point_included [np], info = chi2 before, chi2 after, iterations, trials, final lambda, failed factorisations.
+ * VIORB_ERR_INVALID_ARG: an edge index out of range, edges not sorted by point, prev[i] >= i, invSigma2 <= 0, a singular covariance. A
+ * stereo observation (an error in the reference, :230) has no place in edge_obs: the caller rejects it. VIORB_ERR_CAPACITY: more than
+ * 2048 free key frames (a reduced system of order 24576), or a workspace that is too small; never a truncated solve.
+ * All arithmetic runs on the calling thread's current HIP device in FP64; the reduced system is dense and is factored by a blocked
+ * Cholesky over the whole device. The host form is re-entrant: concurrent callers get their own stream and arena. */
+typedef struct viorb_gba_config { int32_t iterations; int32_t robust; } viorb_gba_config;
+size_t viorb_global_ba_navstate_workspace_bytes(int nk, int np, int ne);
+int viorb_global_ba_navstate(const viorb_gba_config* cfg, const double* kfs, int nk, const int32_t* prev, const uint8_t* fixed,
+                             const double* preint, const double* points, int np, const int32_t* edge_idx, const double* edge_obs,
+                             int ne, const double gw[3], const double cam[16], const volatile int* stop, double* kfs_out,
+                             double* points_out, uint8_t* point_included, double info[6]);
+/* The same with the arrays in device memory (kfs_out / points_out are the working states and must not alias the inputs); cfg, gw, cam,
+ * stop and info are host pointers. workspace: viorb_global_ba_navstate_workspace_bytes(nk, np, ne) bytes of device memory. The call
+ * returns when the solve is done (the Levenberg control reads three doubles per trial from `stream`). */
+int viorb_global_ba_navstate_device(const viorb_gba_config* cfg, const double* kfs, int nk, const int32_t* prev, const uint8_t* fixed,
+                                    const double* preint, const double* points, int np, const int32_t* edge_idx,
+                                    const double* edge_obs, int ne, const double gw[3], const double cam[16], const volatile int* stop,
+                                    double* kfs_out, double* points_out, uint8_t* point_included, double info[6], void* workspace,
+                                    size_t workspace_bytes, void* stream);
+/* Test hook (needs a device): the blocked Cholesky of the global solve alone. A [n][n] row-major, its lower triangle is read; L [n][n]
+ * receives the factor; *ok = 0 when a pivot was not positive and finite, as the reference's LLT reports it (L untouched). */
+int viorb_debug_gba_cholesky(const double* A, int n, double* L, int32_t* ok);
+/* Test hook: accept (1) / reject (0) of every Levenberg trial of the calling thread's last global solve, in order; *n = their number. */
+int viorb_debug_gba_last_trials(uint8_t* accepted, int cap, int* n);
+
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,11 @@ class ViInitConfig(C.Structure):
     _fields_ = [("Tbc", C.c_double * 16), ("g", C.c_double), ("gyr_meas_cov", C.c_double), ("acc_meas_cov", C.c_double)]
 
 
+class GbaConfig(C.Structure):
+    """viorb_gba_config (include/viorb.h)."""
+    _fields_ = [("iterations", C.c_int32), ("robust", C.c_int32)]
+
+
 class TrackerConfig(C.Structure):
     """viorb_tracker_config (include/viorb.h)."""
     _fields_ = [("extractor", ExtractorParams), ("frontend", FrontendConfig), ("width", C.c_int32), ("height", C.c_int32), ("batch", C.c_int32),
@@ -216,6 +221,11 @@ SIGNATURES = {
     "viorb_debug_vi_init_rows": (None, [vp] * 5 + [C.c_double, vp, vp]),
     "viorb_debug_vi_init_solve": (i32, [vp, vp, i32, i32, vp, vp]),
     "viorb_debug_vi_init_rwi": (i32, [vp, vp]),
+    "viorb_global_ba_navstate_workspace_bytes": (sz, [i32, i32, i32]),
+    "viorb_global_ba_navstate": (i32, [PP(GbaConfig), vp, i32, vp, vp, vp, vp, i32, vp, vp, i32] + [vp] * 7),
+    "viorb_global_ba_navstate_device": (i32, [PP(GbaConfig), vp, i32, vp, vp, vp, vp, i32, vp, vp, i32] + [vp] * 8 + [sz, vp]),
+    "viorb_debug_gba_cholesky": (i32, [vp, i32, vp, vp]),
+    "viorb_debug_gba_last_trials": (i32, [vp, i32, PP(i32)]),
 }
 
 _lib = None

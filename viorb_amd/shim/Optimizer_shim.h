@@ -7,6 +7,8 @@
 //   local_bundle_adjustment_navstate  Optimizer::LocalBundleAdjustmentNavState(pCurKF, lLocalKeyFrames, pbStopFlag, pMap, gw, pLM)
 //                                                                                                 src/Optimizer.cc:1690-2241  -> viorb_local_ba_navstate
 //   local_bundle_adjustment           Optimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap, pLM) src/Optimizer.cc:3980-4311 -> viorb_local_ba_se3
+//   global_bundle_adjustment_navstate Optimizer::GlobalBundleAdjustmentNavState(pMap, gw, nIterations, pbStopFlag, nLoopKF, bRobust)
+//                                                                                                 src/Optimizer.cc:50-320     -> viorb_global_ba_navstate
 //
 // The window solves take `stop_mirror`: the reference's pbStopFlag is a bool*, the C ABI polls a `const volatile int*` — an int that
 // LocalMapping::InterruptBA sets next to mbAbortBA (one line there). A failure of the GPU library throws (viorb_shim::check).
@@ -17,6 +19,8 @@
 #include <list>
 #include <map>
 #include <mutex>
+#include <algorithm>
+#include <stdexcept>
 #include "viorb_tracking_shim.h"
 
 namespace viorb_shim {
@@ -198,6 +202,100 @@ inline void local_bundle_adjustment(KeyFrameT* pKF, bool* pbStopFlag, const vola
         cv::Mat Pw(3, 1, CV_32F);
         for (int c = 0; c < 3; c++) Pw.template at<float>(c) = (float)points_out[(size_t)p * 3 + c];
         pts_v[p]->SetWorldPos(Pw); pts_v[p]->UpdateNormalAndDepth();
+    }
+}
+
+// Optimizer::GlobalBundleAdjustmentNavState: every good key frame and map point of the map in one solve. Key frames go in mnId order (a
+// predecessor has the smaller id), mnId == 0 is fixed (:91-97); a predecessor that is bad or absent gives no IMU factor. Observations in
+// bad key frames or with 2 * mnId > maxKFid are skipped (:197); a stereo observation is an error in the reference (:230) and throws
+// here. A point left without an edge is not written back (:234-242, :298). nLoopKF == 0 stores the result in the key frames and points
+// (:267-272, :307-311), otherwise in mNavStateGBA / mTcwGBA / mPosGBA / mnBAGlobalForKF (:273-286, :312-317). Returns info[6] of the C
+// ABI through `info` when it is not NULL. Vec3 / Quat / SO3T / Tbc / MatTbc / stop_mirror as in local_bundle_adjustment_navstate.
+template <class Vec3, class Quat, class SO3T, class MapT, class Mat4>                                         // <Vector3d, Quaterniond, Sophus::SO3>: the rest is deduced
+inline void global_bundle_adjustment_navstate(MapT* pMap, const double gw[3], int nIterations, bool* pbStopFlag, const volatile int* stop_mirror,
+                                              const unsigned long nLoopKF, const bool bRobust, const Mat4& Tbc, const cv::Mat& MatTbc, double* info = 0) {
+    auto vpKFsAll = pMap->GetAllKeyFrames(); auto vpMP = pMap->GetAllMapPoints();
+    typedef typename std::remove_pointer<typename decltype(vpKFsAll)::value_type>::type KeyFrameT;
+    std::vector<KeyFrameT*> kfs_v;
+    for (size_t i = 0; i < vpKFsAll.size(); i++) if (!vpKFsAll[i]->isBad()) kfs_v.push_back(vpKFsAll[i]);
+    if (kfs_v.empty()) return;
+    std::sort(kfs_v.begin(), kfs_v.end(), [](const KeyFrameT* a, const KeyFrameT* b) { return a->mnId < b->mnId; });
+    const int nk = (int)kfs_v.size();
+    unsigned long maxKFid = 0;
+    std::map<const KeyFrameT*, int> kf_index;
+    for (int k = 0; k < nk; k++) { kf_index[kfs_v[k]] = k; if (kfs_v[k]->mnId * 2 + 1 > maxKFid) maxKFid = kfs_v[k]->mnId * 2 + 1; }
+    std::vector<double> kfs((size_t)nk * 22), preint((size_t)nk * 142, 0.0); std::vector<int32_t> prev(nk, -1); std::vector<unsigned char> fixed(nk, 0);
+    for (int k = 0; k < nk; k++) {
+        pack_navstate(kfs_v[k]->GetNavState(), &kfs[(size_t)k * 22]);
+        fixed[k] = kfs_v[k]->mnId == 0;
+        KeyFrameT* pKF0 = kfs_v[k]->GetPrevKeyFrame();
+        typename std::map<const KeyFrameT*, int>::const_iterator it = pKF0 ? kf_index.find(pKF0) : kf_index.end();
+        if (it == kf_index.end() || it->second >= k) continue;
+        prev[k] = it->second;
+        pack_preint(kfs_v[k]->GetIMUPreInt(), &preint[(size_t)k * 142]);
+    }
+    typedef typename std::remove_pointer<typename decltype(vpMP)::value_type>::type MapPointT;
+    std::vector<MapPointT*> pts_v;
+    for (size_t i = 0; i < vpMP.size(); i++) if (!vpMP[i]->isBad()) pts_v.push_back(vpMP[i]);
+    const int np = (int)pts_v.size();
+    std::vector<double> points((size_t)(np + 1) * 3), edge_obs; std::vector<int32_t> edge_idx;
+    for (int p = 0; p < np; p++) {
+        const cv::Mat Pw = pts_v[p]->GetWorldPos();
+        for (int c = 0; c < 3; c++) points[(size_t)p * 3 + c] = Pw.template at<float>(c);
+        const auto observations = pts_v[p]->GetObservations();
+        for (auto mit = observations.begin(); mit != observations.end(); ++mit) {
+            KeyFrameT* pKFi = mit->first;
+            if (pKFi->isBad() || 2 * pKFi->mnId > maxKFid) continue;
+            if (!(pKFi->mvuRight[mit->second] < 0)) throw std::runtime_error("GlobalBundleAdjustmentNavState: Stereo not supported");
+            // the reference looks the vertex up by id; a good observer that GetAllKeyFrames() did not return has none
+            typename std::map<const KeyFrameT*, int>::const_iterator kit = kf_index.find(pKFi);
+            if (kit == kf_index.end()) throw std::runtime_error("GlobalBundleAdjustmentNavState: an observing key frame is not in the map");
+            const cv::KeyPoint& kpUn = pKFi->mvKeysUn[mit->second];
+            edge_idx.push_back(p); edge_idx.push_back(kit->second);
+            edge_obs.push_back(kpUn.pt.x); edge_obs.push_back(kpUn.pt.y); edge_obs.push_back(pKFi->mvInvLevelSigma2[kpUn.octave]);
+        }
+    }
+    (void)pbStopFlag;                                                      // read through its int mirror (setForceStopFlag, :75-76)
+    const int ne = (int)(edge_idx.size() / 2);
+    double cam[16]; pack_camera(*kfs_v[0], Tbc, cam);
+    std::vector<double> kfs_out((size_t)nk * 22), points_out((size_t)(np + 1) * 3); std::vector<unsigned char> included(np + 1); double info_[6];
+    viorb_gba_config cfg; cfg.iterations = nIterations; cfg.robust = bRobust ? 1 : 0;
+    check(viorb_global_ba_navstate(&cfg, &kfs[0], nk, &prev[0], &fixed[0], &preint[0], &points[0], np, ne ? &edge_idx[0] : 0, ne ? &edge_obs[0] : 0, ne, gw, cam,
+                                   stop_mirror, &kfs_out[0], &points_out[0], &included[0], info_), "GlobalBundleAdjustmentNavState");
+    if (info) for (int k = 0; k < 6; k++) info[k] = info_[k];
+    for (int k = 0; k < nk; k++) {                                          // (:252-293)
+        typename std::remove_const<typename std::remove_reference<decltype(kfs_v[k]->GetNavState())>::type>::type ns;
+        const double* o = &kfs_out[(size_t)k * 22];
+        unpack_navstate<decltype(ns), Vec3, Quat, SO3T>(o, ns);
+        if (nLoopKF == 0) { kfs_v[k]->SetNavState(ns); kfs_v[k]->UpdatePoseFromNS(MatTbc); continue; }
+        kfs_v[k]->mNavStateGBA = ns;
+        // Twc = Twb * Tbc in float, then Converter::toCvMatInverse: Rcw = Rwc^T, tcw = -Rcw twc (:277-283)
+        const double qx = o[6], qy = o[7], qz = o[8], qw = o[9];
+        const float Twb[3][4] = {{(float)(1 - 2 * (qy * qy + qz * qz)), (float)(2 * (qx * qy - qz * qw)), (float)(2 * (qx * qz + qy * qw)), (float)o[0]},
+                                 {(float)(2 * (qx * qy + qz * qw)), (float)(1 - 2 * (qx * qx + qz * qz)), (float)(2 * (qy * qz - qx * qw)), (float)o[1]},
+                                 {(float)(2 * (qx * qz - qy * qw)), (float)(2 * (qy * qz + qx * qw)), (float)(1 - 2 * (qx * qx + qy * qy)), (float)o[2]}};
+        float Twc[3][4];
+        for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) {
+            float s = 0.f;
+            for (int q = 0; q < 3; q++) s += Twb[r][q] * MatTbc.template at<float>(q, c);
+            Twc[r][c] = c == 3 ? s + Twb[r][3] : s;
+        }
+        cv::Mat T(4, 4, CV_32F);
+        for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) T.template at<float>(r, c) = r == c ? 1.f : 0.f;
+        for (int r = 0; r < 3; r++) {
+            float t = 0.f;
+            for (int c = 0; c < 3; c++) { T.template at<float>(r, c) = Twc[c][r]; t += -Twc[c][r] * Twc[c][3]; }
+            T.template at<float>(r, 3) = t;
+        }
+        kfs_v[k]->mTcwGBA = T;
+        kfs_v[k]->mnBAGlobalForKF = nLoopKF;
+    }
+    for (int p = 0; p < np; p++) {                                          // (:295-318)
+        if (!included[p]) continue;
+        cv::Mat Pw(3, 1, CV_32F);
+        for (int c = 0; c < 3; c++) Pw.template at<float>(c) = (float)points_out[(size_t)p * 3 + c];
+        if (nLoopKF == 0) { pts_v[p]->SetWorldPos(Pw); pts_v[p]->UpdateNormalAndDepth(); }
+        else { pts_v[p]->mPosGBA = Pw; pts_v[p]->mnBAGlobalForKF = nLoopKF; }
     }
 }
 

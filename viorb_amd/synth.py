@@ -838,3 +838,84 @@ def make_vi_init_problem(seed, N, kf_dt=0.25, imu_dt=0.005, scale=3.7, noise=0.0
     imu = np.concatenate(chunks) if chunks else np.zeros((0, 7))
     kf_vel = np.stack([Rw0 @ (amp * 2 * np.pi * fr * np.cos(2 * np.pi * fr * t + ph)) for t in tk])
     return dict(twc12=twc12, kf_time=tk, imu=imu, imu_start=start, Tbc=Tbc, g=G, truth=dict(s=scale, gw=gw, bg=bg, ba=ba, kf_vel=kf_vel))
+
+
+def make_global_ba_problem(seed, N=21, n_points=None, revisit_frac=0.0, n_fixed=1, pix_sigma=2.0, kf_dt=0.15, imu_dt=0.005, w=752, h=480,
+                           preint_fn=None):
+    """A GlobalBundleAdjustmentNavState problem: N chronological key frames on a smooth trajectory past a point cloud (the first n_fixed
+    fixed, prev[i] = i - 1), n_points points (default 40 per key frame) each seen by a contiguous run of 3..12 key frames; a revisit_frac
+    share of them is seen again by a distant run, so that the reduced matrix is not banded. Pre-integrations: preint_fn(stream, bg, ba)
+    -> [N,142], default viorb_preintegrate_intervals (needs a device). Initial states are perturbed as make_local_ba_problem perturbs
+    them. Returns flat arrays in the layouts of include/viorb.h + the truth + the IMU stream (kf_time, imu, imu_start)."""
+    from scipy.spatial.transform import Rotation
+    rng = np.random.Generator(np.random.PCG64(seed + 70707))
+    n_points = 40 * N if n_points is None else n_points
+    cam = euroc_cam()
+    fx, fy, cx, cy = cam[:4]; Rbc, Pbc = cam[4:13].reshape(3, 3), cam[13:16]
+    n_imu = int(round(kf_dt / imu_dt))
+    R = Rbc.T.copy(); Pw = -R @ Pbc; V = rng.normal(0, 0.4, 3) * np.array([1, 1, 0.3])
+    bg, ba = rng.normal(0, 0.002, 3), rng.normal(0, 0.02, 3)
+    states, chunks, start, t = [], [], np.zeros(N + 1, np.int32), 10.0
+    kf_time = 10.0 + kf_dt * np.arange(N)
+    for k in range(N):
+        states.append(navstate(Pw, V, R, bg, ba))
+        start[k + 1] = start[k] + (n_imu if k > 0 else 0)
+        if k == N - 1:
+            break
+        omega = rng.normal(0, 0.15, 3); a_w = rng.normal(0, 0.6, 3) * np.array([1, 1, 0.3]) - 0.5 * V
+        imu = np.zeros((n_imu, 7))
+        for j in range(n_imu):
+            tj = t + imu_dt * (j + 0.3)
+            Rt = R @ _rotvec_to_R(omega * (tj - t))
+            imu[j, :3] = omega + bg + rng.normal(0, 1e-3, 3); imu[j, 3:6] = Rt.T @ (a_w - GRAVITY_CAM_WORLD) + ba + rng.normal(0, 1e-2, 3); imu[j, 6] = tj
+        chunks.append(imu)
+        Pw = Pw + V * kf_dt + 0.5 * a_w * kf_dt ** 2; V = V + a_w * kf_dt; R = R @ _rotvec_to_R(omega * kf_dt); t += kf_dt
+    kfs_true = np.stack(states)
+    stream = dict(kf_time=kf_time, imu=np.concatenate(chunks) if chunks else np.zeros((0, 7)), imu_start=start)
+    if preint_fn is None:
+        from .vi_init import PreintegrateIntervals
+        preint_fn = lambda s, g, a: PreintegrateIntervals(s, g, a, clamp=False)
+    preint = np.ascontiguousarray(preint_fn(stream, bg, ba), np.float64).reshape(N, 142)
+    poses = [cam_pose_from_navstate(s, cam) for s in kfs_true]
+    sf = np.float32(1.2) ** np.arange(8)
+    pts, edges_i, edges_o = [], [], []
+
+    def observe(pid, X, ks):
+        n = 0
+        for k in ks:
+            Pc = poses[k][0] @ X + poses[k][1]
+            if Pc[2] < 0.5: continue
+            uu, vv = fx * Pc[0] / Pc[2] + cx, fy * Pc[1] / Pc[2] + cy
+            if not (-w < uu < 2 * w and -h < vv < 2 * h): continue
+            octv = int(rng.integers(0, 8)); sg = pix_sigma * float(sf[octv]) / 2.0
+            edges_i.append((pid, k)); edges_o.append((np.float32(uu + rng.normal(0, sg)), np.float32(vv + rng.normal(0, sg)), 1.0 / float(np.float32(sf[octv]) ** 2)))
+            n += 1
+        return n
+    while len(pts) < n_points:
+        run = int(min(N, rng.integers(3, 13))); k0 = int(rng.integers(0, N - run + 1))
+        kc = k0 + run // 2
+        u0, v0, z = rng.uniform(30, w - 30), rng.uniform(30, h - 30), rng.uniform(2, 10)
+        Rcw, tcw = poses[kc]
+        X = Rcw.T @ (np.array([(u0 - cx) / fx * z, (v0 - cy) / fy * z, z]) - tcw)
+        pid = len(pts)
+        m0 = len(edges_i)
+        ks = list(range(k0, k0 + run))
+        if rng.random() < revisit_frac and N > 2 * run + 8:
+            run2 = int(rng.integers(3, 13)); far = [k for k in range(0, N - run2 + 1) if k + run2 <= k0 - 8 or k >= k0 + run + 8]
+            if far:
+                k2 = int(far[int(rng.integers(0, len(far)))]); ks = sorted(ks + list(range(k2, k2 + run2)))
+        if observe(pid, X, ks) < 2:
+            del edges_i[m0:], edges_o[m0:]
+            continue
+        pts.append(X)
+    pts = np.array(pts).reshape(-1, 3)
+    kfs0 = kfs_true.copy()
+    for i in range(n_fixed, N):
+        kfs0[i, :3] += rng.normal(0, 0.02, 3); kfs0[i, 3:6] += rng.normal(0, 0.05, 3)
+        q = Rotation.from_quat(kfs0[i, 6:10]) * Rotation.from_rotvec(rng.normal(0, 0.005, 3))
+        qq = q.as_quat(); kfs0[i, 6:10] = qq if qq[3] >= 0 else -qq
+    pts0 = pts + rng.normal(0, 0.05, pts.shape)
+    prev = np.arange(-1, N - 1, dtype=np.int32); fixed = np.zeros(N, np.uint8); fixed[:n_fixed] = 1
+    return dict(kfs=kfs0, kfs_true=kfs_true, prev=prev, fixed=fixed, preint=preint, points=np.float32(pts0).astype(np.float64), points_true=pts,
+                edge_idx=np.array(edges_i, np.int32).reshape(-1, 2), edge_obs=np.array(edges_o, np.float64).reshape(-1, 3),
+                gw=GRAVITY_CAM_WORLD.copy(), cam=cam, stream=stream, bias=(bg, ba))
