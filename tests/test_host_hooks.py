@@ -268,3 +268,81 @@ def test_cpp_tracking_shim_compiles_links_and_runs(tmp_path):
     exe = _build_tracking_shim_test(tmp_path)
     out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and out.stdout.startswith("OK"), out.stdout + out.stderr
+
+
+# ---- host forms without a device: argument errors first, then VIORB_ERR_NO_DEVICE with the shared text ----------------------------
+def _one_descriptor_inputs():
+    kp = np.zeros(1, capi.KP_DTYPE); d = np.zeros((1, 32), np.uint8); one_i = np.zeros(1, np.int32); one_b = np.zeros(1, np.uint8)
+    ur = -np.ones(1, np.float32)
+    return kp, d, one_i, one_b, ur
+
+
+def _call_match_bruteforce(L, empty):
+    kp, d, one_i, one_b, ur = _one_descriptor_inputs()
+    best, second, idx = (np.full(1, 7, np.int32) for _ in range(3))
+    rc = L.viorb_match_bruteforce(capi.ptr(d), 0 if empty else 1, capi.ptr(d), 1, capi.ptr(best), capi.ptr(second), capi.ptr(idx))
+    return rc, None
+
+
+def _call_search_by_bow(L, empty):
+    kp, d, one_i, one_b, ur = _one_descriptor_inputs()
+    match = np.full(1, 7, np.int32); nm = C.c_int(7)
+    rc = L.viorb_search_by_bow(capi.ptr(kp), capi.ptr(d), capi.ptr(one_i), capi.ptr(one_b), 0 if empty else 1, capi.ptr(kp), capi.ptr(d), capi.ptr(one_i), 1,
+                               0.7, 1, capi.ptr(match), C.byref(nm))
+    assert nm.value == 0
+    return rc, match
+
+
+def _call_search_for_triangulation(L, empty):
+    kp, d, one_i, one_b, ur = _one_descriptor_inputs()
+    match = np.full(1, 7, np.int32); nm = C.c_int(7)
+    F12, Cw, T2 = np.eye(3, dtype=np.float32), np.zeros(3, np.float32), np.eye(3, 4, dtype=np.float32)
+    intr, sf, ls2 = np.array([500, 500, 320, 240], np.float32), np.ones(8, np.float32), np.ones(8, np.float32)
+    rc = L.viorb_search_for_triangulation(capi.ptr(kp), capi.ptr(d), capi.ptr(one_b), capi.ptr(ur), capi.ptr(one_i), 1, capi.ptr(kp), capi.ptr(d), capi.ptr(one_b),
+                                          capi.ptr(ur), capi.ptr(one_i), 0 if empty else 1, capi.ptr(F12), capi.ptr(Cw), capi.ptr(T2), capi.ptr(intr),
+                                          capi.ptr(sf), capi.ptr(ls2), 8, 0, 1, capi.ptr(match), C.byref(nm))
+    assert nm.value == 0
+    return rc, match
+
+
+def _call_vocabulary_create(L, empty):
+    if empty:
+        return None, None                                      # a vocabulary has no empty form: a root and one word is the smallest
+    start, ids, word = np.array([0, 1, 1], np.int32), np.array([1], np.int32), np.array([-1, 0], np.int32)
+    desc, weight = np.zeros((2, 32), np.uint8), np.ones(2)
+    h = C.c_void_p()
+    rc = L.viorb_vocabulary_create(2, 1, capi.ptr(start), capi.ptr(ids), capi.ptr(desc), capi.ptr(word), capi.ptr(weight), C.byref(h))
+    if rc == capi.VIORB_OK:
+        L.viorb_vocabulary_destroy(h)
+    return rc, None
+
+
+@pytest.mark.parametrize("call", [_call_match_bruteforce, _call_search_by_bow, _call_search_for_triangulation, _call_vocabulary_create],
+                         ids=lambda f: f.__name__[len("_call_"):])
+def test_host_forms_refuse_without_a_device(call):
+    """The host forms of the matchers and the vocabulary: empty input returns VIORB_OK with every match -1 before anything asks for a
+    device; valid arguments of the smallest legal size (one descriptor each) give VIORB_ERR_NO_DEVICE with the shared text."""
+    L = viorb_amd.lib()
+    rc, match = call(L, True)
+    assert rc in (None, capi.VIORB_OK)
+    if match is not None:
+        assert (match == -1).all()
+    if L.viorb_device_count() > 0:
+        return
+    L.viorb_extractor_create(None, 0, 0, None)                 # another error text in the thread's buffer
+    rc, match = call(L, False)
+    assert rc == capi.ERR_NO_DEVICE
+    assert L.viorb_last_error() == b"no HIP device: libviorb_hip has no CPU fallback"
+    if match is not None:
+        assert (match == -1).all()
+
+
+def test_bow_transform_host_form_without_a_device():
+    """viorb_bow_transform has no device check of its own: without a device its first allocation fails (the vocabulary handle, which
+    cannot exist then, is not read before that)."""
+    L = viorb_amd.lib()
+    if L.viorb_device_count() > 0:
+        return
+    d = np.zeros((1, 32), np.uint8); word, node, weight = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1)
+    stand_in = np.zeros(64, np.uint8)
+    assert L.viorb_bow_transform(capi.ptr(stand_in), capi.ptr(d), 1, 4, capi.ptr(word), capi.ptr(weight), capi.ptr(node)) == capi.ERR_HIP

@@ -268,3 +268,12 @@ def ptr(a):
     if isinstance(a, np.ndarray):
         return a.ctypes.data_as(C.c_void_p)
     return C.c_void_p(a.data_ptr())
+
+
+def _torch_up(a, device=0):
+    """A numpy array as a torch tensor on cuda:device (a structured dtype as its bytes)."""
+    import torch
+    a = np.ascontiguousarray(a)
+    if a.dtype.fields is not None:
+        a = a.view(np.uint8)
+    return torch.from_numpy(a).to(torch.device("cuda", device))

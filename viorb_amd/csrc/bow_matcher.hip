@@ -303,19 +303,6 @@ struct viorb_vocabulary {
     int *child_start, *child_ids, *word_id; uint8_t* desc; double* weight;
 };
 
-namespace {
-struct BowBuf {
-    std::vector<void*> ptrs;
-    ~BowBuf() { for (void* p : ptrs) (void)hipFree(p); }
-    template <class T> bool up(T** d, const T* src, size_t n) {
-        if (hipMalloc((void**)d, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return false;
-        ptrs.push_back(*d);
-        if (src && n) return hipMemcpy(*d, src, n * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
-        return hipMemset(*d, 0, std::max<size_t>(n, 1) * sizeof(T)) == hipSuccess;
-    }
-};
-}
-
 extern "C" {
 
 int viorb_vocabulary_create(int n_nodes, int L, const int32_t* child_start, const int32_t* child_ids, const uint8_t* desc,
@@ -330,7 +317,7 @@ int viorb_vocabulary_create(int n_nodes, int L, const int32_t* child_start, cons
     for (int e = 0; e < ne; e++) VIORB_REQUIRE(child_ids[e] > 0 && child_ids[e] < n_nodes, "child id out of range");
     for (int n = 0; n < n_nodes; n++) if (child_start[n + 1] == child_start[n]) VIORB_REQUIRE(word_id[n] >= 0, "a leaf needs a word id");
     VIORB_REQUIRE(child_start[1] > 0, "the root has no children");
-    if (viorb_device_count() < 1) { set_error("no HIP device: libviorb_hip has no CPU fallback"); return VIORB_ERR_NO_DEVICE; }
+    VIORB_TRY(require_device());
     viorb_vocabulary* v = new viorb_vocabulary();
     v->n_nodes = n_nodes; v->L = L; v->n_edges = ne;
     v->child_start = v->child_ids = v->word_id = nullptr; v->desc = nullptr; v->weight = nullptr;
@@ -359,9 +346,7 @@ int viorb_bow_transform_device(const viorb_vocabulary* v, const uint8_t* desc, c
     VIORB_REQUIRE(cap >= 1 && batch >= 1 && (long long)cap * batch < (1ll << 27), "cap * batch out of range");
     BowVoc V; V.child_start = v->child_start; V.child_ids = v->child_ids; V.desc = v->desc; V.word_id = v->word_id; V.weight = v->weight; V.n_nodes = v->n_nodes; V.L = v->L;
     const long long groups = (long long)cap * batch;
-    ProfScope ps("k_bow_transform", (hipStream_t)stream);
-    hipLaunchKernelGGL(k_bow_transform, dim3((unsigned)((groups + 15) / 16)), dim3(256), 0, (hipStream_t)stream, V, desc, count, cap, batch, levelsup, word, weight, node);
-    VIORB_HIP_TRY(hipGetLastError());
+    VIORB_LAUNCH(k_bow_transform, (unsigned)((groups + 15) / 16), 256, 0, (hipStream_t)stream, V, desc, count, cap, batch, levelsup, word, weight, node);
     return VIORB_OK;
 }
 
@@ -405,10 +390,10 @@ int viorb_bow_transform(const viorb_vocabulary* v, const uint8_t* desc, int n, i
     VIORB_REQUIRE(v && n >= 0, "null vocabulary");
     if (n == 0) return VIORB_OK;
     VIORB_REQUIRE(desc && word && weight && node, "null array");
-    BowBuf B; uint8_t* d_desc; int *d_cnt, *d_word, *d_node; double* d_w;
-    if (!(B.up(&d_desc, desc, (size_t)32 * n) && B.up(&d_cnt, &n, 1) && B.up(&d_word, (const int*)nullptr, n) && B.up(&d_node, (const int*)nullptr, n) && B.up(&d_w, (const double*)nullptr, n))) {
-        set_error("device allocation / upload failed"); return VIORB_ERR_HIP;
-    }
+    DeviceBufs B;
+    uint8_t* d_desc = B.up(desc, (size_t)32 * n); int* d_cnt = B.up(&n, 1);
+    int *d_word = B.zeros<int>(n), *d_node = B.zeros<int>(n); double* d_w = B.zeros<double>(n);
+    if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
     int rc = viorb_bow_transform_device(v, d_desc, d_cnt, n, 1, levelsup, d_word, d_w, d_node, nullptr);
     if (rc != VIORB_OK) return rc;
     VIORB_HIP_TRY(hipDeviceSynchronize());
@@ -426,20 +411,14 @@ int viorb_search_by_bow(const viorb_keypoint* kf_kps, const uint8_t* kf_desc, co
     for (int i = 0; i < nf; i++) match[i] = -1;
     if (nkf == 0 || nf == 0) return VIORB_OK;
     VIORB_REQUIRE(kf_kps && kf_desc && kf_node && kf_has_point && f_kps && f_desc && f_node && match, "null array");
-    if (viorb_device_count() < 1) { set_error("no HIP device: libviorb_hip has no CPU fallback"); return VIORB_ERR_NO_DEVICE; }
+    VIORB_TRY(require_device());
     const int cap = std::max(nkf, nf);
-    BowBuf B; viorb_keypoint *d_kk, *d_fk; uint8_t *d_kd, *d_fd, *d_kh; int *d_kn, *d_fn, *d_kc, *d_fc, *d_m, *d_nm;
-    bool ok = B.up(&d_kk, (const viorb_keypoint*)nullptr, cap) && B.up(&d_fk, (const viorb_keypoint*)nullptr, cap) && B.up(&d_kd, (const uint8_t*)nullptr, (size_t)32 * cap) &&
-              B.up(&d_fd, (const uint8_t*)nullptr, (size_t)32 * cap) && B.up(&d_kh, (const uint8_t*)nullptr, cap) && B.up(&d_kn, (const int*)nullptr, cap) &&
-              B.up(&d_fn, (const int*)nullptr, cap) && B.up(&d_kc, &nkf, 1) && B.up(&d_fc, &nf, 1) && B.up(&d_m, (const int*)nullptr, cap) && B.up(&d_nm, (const int*)nullptr, 1);
-    if (!ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
-    VIORB_HIP_TRY(hipMemcpy(d_kk, kf_kps, sizeof(viorb_keypoint) * nkf, hipMemcpyHostToDevice));
-    VIORB_HIP_TRY(hipMemcpy(d_fk, f_kps, sizeof(viorb_keypoint) * nf, hipMemcpyHostToDevice));
-    VIORB_HIP_TRY(hipMemcpy(d_kd, kf_desc, (size_t)32 * nkf, hipMemcpyHostToDevice));
-    VIORB_HIP_TRY(hipMemcpy(d_fd, f_desc, (size_t)32 * nf, hipMemcpyHostToDevice));
-    VIORB_HIP_TRY(hipMemcpy(d_kh, kf_has_point, nkf, hipMemcpyHostToDevice));
-    VIORB_HIP_TRY(hipMemcpy(d_kn, kf_node, sizeof(int) * nkf, hipMemcpyHostToDevice));
-    VIORB_HIP_TRY(hipMemcpy(d_fn, f_node, sizeof(int) * nf, hipMemcpyHostToDevice));
+    DeviceBufs B;
+    viorb_keypoint *d_kk = B.up(kf_kps, nkf, cap), *d_fk = B.up(f_kps, nf, cap);
+    uint8_t *d_kd = B.up(kf_desc, (size_t)32 * nkf, (size_t)32 * cap), *d_fd = B.up(f_desc, (size_t)32 * nf, (size_t)32 * cap), *d_kh = B.up(kf_has_point, nkf, cap);
+    int *d_kn = B.up(kf_node, nkf, cap), *d_fn = B.up(f_node, nf, cap), *d_kc = B.up(&nkf, 1), *d_fc = B.up(&nf, 1);
+    int *d_m = B.zeros<int>(cap), *d_nm = B.zeros<int>(1);
+    if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
     int rc = viorb_search_by_bow_device(d_kk, d_kd, d_kn, d_kh, d_kc, d_fk, d_fd, d_fn, d_fc, cap, 1, nnratio, check_orientation, d_m, d_nm, nullptr);
     if (rc != VIORB_OK) return rc;
     VIORB_HIP_TRY(hipDeviceSynchronize());
@@ -467,9 +446,7 @@ int viorb_search_for_triangulation_device(const viorb_keypoint* k1, const uint8_
     A.cap = cap; A.sort_n = sn; A.only_stereo = only_stereo; A.check_ori = check_orientation;
     A.fx = intr4[0]; A.fy = intr4[1]; A.cx = intr4[2]; A.cy = intr4[3];
     for (int i = 0; i < 16; i++) { A.scale[i] = scale_factors2[i < nlevels ? i : nlevels - 1]; A.level_sigma2[i] = level_sigma2_2[i < nlevels ? i : nlevels - 1]; }
-    ProfScope ps("k_search_triangulation", (hipStream_t)stream);
-    hipLaunchKernelGGL(k_search_triangulation, dim3(batch), dim3(1024), lds, (hipStream_t)stream, A);
-    VIORB_HIP_TRY(hipGetLastError());
+    VIORB_LAUNCH(k_search_triangulation, batch, 1024, lds, (hipStream_t)stream, A);
     return VIORB_OK;
 }
 
@@ -484,20 +461,16 @@ int viorb_search_for_triangulation(const viorb_keypoint* k1, const uint8_t* d1, 
     for (int i = 0; i < n1; i++) match12[i] = -1;
     if (n1 == 0 || n2 == 0) return VIORB_OK;
     VIORB_REQUIRE(k1 && d1 && has_point1 && uright1 && node1 && k2 && d2 && has_point2 && uright2 && node2 && F12 && Cw1 && pose12_2 && match12, "null array");
-    if (viorb_device_count() < 1) { set_error("no HIP device: libviorb_hip has no CPU fallback"); return VIORB_ERR_NO_DEVICE; }
+    VIORB_TRY(require_device());
     const int cap = std::max(n1, n2);
-    BowBuf B; viorb_keypoint *dk1, *dk2; uint8_t *dd1, *dd2, *dh1, *dh2; float *du1, *du2, *dF, *dC, *dP; int *dn1, *dn2, *dc1, *dc2, *dm, *dnm;
-    bool ok = B.up(&dk1, (const viorb_keypoint*)nullptr, cap) && B.up(&dk2, (const viorb_keypoint*)nullptr, cap) && B.up(&dd1, (const uint8_t*)nullptr, (size_t)32 * cap) &&
-              B.up(&dd2, (const uint8_t*)nullptr, (size_t)32 * cap) && B.up(&dh1, (const uint8_t*)nullptr, cap) && B.up(&dh2, (const uint8_t*)nullptr, cap) &&
-              B.up(&du1, (const float*)nullptr, cap) && B.up(&du2, (const float*)nullptr, cap) && B.up(&dF, F12, 9) && B.up(&dC, Cw1, 3) && B.up(&dP, pose12_2, 12) &&
-              B.up(&dn1, (const int*)nullptr, cap) && B.up(&dn2, (const int*)nullptr, cap) && B.up(&dc1, &n1, 1) && B.up(&dc2, &n2, 1) &&
-              B.up(&dm, (const int*)nullptr, cap) && B.up(&dnm, (const int*)nullptr, 1);
-    if (!ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
-    VIORB_HIP_TRY(hipMemcpy(dk1, k1, sizeof(viorb_keypoint) * n1, hipMemcpyHostToDevice)); VIORB_HIP_TRY(hipMemcpy(dk2, k2, sizeof(viorb_keypoint) * n2, hipMemcpyHostToDevice));
-    VIORB_HIP_TRY(hipMemcpy(dd1, d1, (size_t)32 * n1, hipMemcpyHostToDevice)); VIORB_HIP_TRY(hipMemcpy(dd2, d2, (size_t)32 * n2, hipMemcpyHostToDevice));
-    VIORB_HIP_TRY(hipMemcpy(dh1, has_point1, n1, hipMemcpyHostToDevice)); VIORB_HIP_TRY(hipMemcpy(dh2, has_point2, n2, hipMemcpyHostToDevice));
-    VIORB_HIP_TRY(hipMemcpy(du1, uright1, sizeof(float) * n1, hipMemcpyHostToDevice)); VIORB_HIP_TRY(hipMemcpy(du2, uright2, sizeof(float) * n2, hipMemcpyHostToDevice));
-    VIORB_HIP_TRY(hipMemcpy(dn1, node1, sizeof(int) * n1, hipMemcpyHostToDevice)); VIORB_HIP_TRY(hipMemcpy(dn2, node2, sizeof(int) * n2, hipMemcpyHostToDevice));
+    DeviceBufs B;
+    viorb_keypoint *dk1 = B.up(k1, n1, cap), *dk2 = B.up(k2, n2, cap);
+    uint8_t *dd1 = B.up(d1, (size_t)32 * n1, (size_t)32 * cap), *dd2 = B.up(d2, (size_t)32 * n2, (size_t)32 * cap);
+    uint8_t *dh1 = B.up(has_point1, n1, cap), *dh2 = B.up(has_point2, n2, cap);
+    float *du1 = B.up(uright1, n1, cap), *du2 = B.up(uright2, n2, cap), *dF = B.up(F12, 9), *dC = B.up(Cw1, 3), *dP = B.up(pose12_2, 12);
+    int *dn1 = B.up(node1, n1, cap), *dn2 = B.up(node2, n2, cap), *dc1 = B.up(&n1, 1), *dc2 = B.up(&n2, 1);
+    int *dm = B.zeros<int>(cap), *dnm = B.zeros<int>(1);
+    if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
     int rc = viorb_search_for_triangulation_device(dk1, dd1, dh1, du1, dn1, dc1, dk2, dd2, dh2, du2, dn2, dc2, dF, dC, dP, intr4, scale_factors2, level_sigma2_2,
                                                    nlevels, only_stereo, check_orientation, cap, 1, dm, dnm, nullptr);
     if (rc != VIORB_OK) return rc;

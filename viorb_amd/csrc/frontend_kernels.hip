@@ -1623,7 +1623,7 @@ int viorb_frontend_create(const viorb_frontend_config* cfg, int max_batch, int c
     VIORB_REQUIRE(max_batch >= 1 && cap >= 1 && cap <= 65535, "max_batch >= 1, 1 <= cap <= 65535 (16-bit keypoint indices)");
     VIORB_REQUIRE(cfg->nlevels >= 1 && cfg->nlevels <= 16, "nlevels must be 1..16");
     VIORB_REQUIRE(cfg->max_x > cfg->min_x && cfg->max_y > cfg->min_y, "empty image bounds");
-    if (viorb_device_count() < 1) { set_error("no HIP device: libviorb_hip has no CPU fallback"); return VIORB_ERR_NO_DEVICE; }
+    VIORB_TRY(require_device());
     VIORB_HIP_TRY(hipSetDevice(device));
     viorb_frontend* h = new viorb_frontend();
     h->cfg = *cfg; h->max_batch = max_batch; h->cap = cap; h->device = device;
@@ -1712,7 +1712,7 @@ int viorb_frontend_undistort_device(viorb_frontend* h, const viorb_keypoint* kps
 
 int viorb_undistort_points(const float* xy, int n, const float* intr4, const float* dist5, float* xy_out) {
     VIORB_REQUIRE(xy && intr4 && dist5 && xy_out && n >= 0, "null argument");
-    if (viorb_device_count() < 1) { set_error("no HIP device: libviorb_hip has no CPU fallback"); return VIORB_ERR_NO_DEVICE; }
+    VIORB_TRY(require_device());
     if (n == 0) return VIORB_OK;
     std::vector<viorb_keypoint> rec((size_t)n);
     for (int i = 0; i < n; i++) { rec[i] = viorb_keypoint{}; rec[i].x = xy[2 * i]; rec[i].y = xy[2 * i + 1]; }
@@ -1741,7 +1741,7 @@ int viorb_image_bounds(int width, int height, const float* intr4, const float* d
         b[0] = std::min(mat[0], mat[4]); b[1] = std::max(mat[2], mat[6]);
         b[2] = std::min(mat[1], mat[3]); b[3] = std::max(mat[5], mat[7]);
     } else {
-        if (viorb_device_count() < 1) { set_error("no HIP device: libviorb_hip has no CPU fallback"); return VIORB_ERR_NO_DEVICE; }
+        VIORB_TRY(require_device());
         b[0] = 0.0f; b[1] = (float)width; b[2] = 0.0f; b[3] = (float)height;
     }
     return VIORB_OK;
@@ -2187,7 +2187,6 @@ struct DevBuf {
         return VIORB_OK;
     }
 };
-#define FE_TRY(x) do { int _rc = (x); if (_rc != VIORB_OK) return _rc; } while (0)
 // the host-buffer drop-ins run on the calling thread's current HIP device (hipSetDevice / torch.cuda.set_device), not on device 0
 int current_device() { int d = 0; if (hipGetDevice(&d) != hipSuccess) d = 0; return d; }
 // One front-end handle per calling thread, re-used across host drop-in calls: re-configured in place when only the camera / bounds /
@@ -2254,31 +2253,31 @@ static int search_by_projection_frame_host(const viorb_keypoint* cur_kps, const 
     for (int i = 0; i < 16; i++) c.scale_factors[i] = scale_factors[i < nlevels ? i : nlevels - 1];
     const int cap = std::max(ncur, nlast);
     viorb_frontend* h = nullptr;
-    FE_TRY(host_frontend(c, cap, &h, true));
+    VIORB_TRY(host_frontend(c, cap, &h, true));
     const int hc = h->cap;                                 // staging arrays are pitched by the (cached, possibly larger) handle capacity
     DevBuf B; viorb_keypoint *d_ck, *d_lk; uint8_t *d_cd, *d_ld, *d_lf; float *d_lp, *d_pose; int *d_cc, *d_lc, *d_cs, *d_ci, *d_m, *d_nm, *d_st;
-    FE_TRY(B.up(&d_ck, (const viorb_keypoint*)nullptr, (size_t)hc)); FE_TRY(B.up(&d_lk, (const viorb_keypoint*)nullptr, (size_t)hc));
-    FE_TRY(B.up(&d_cd, (const uint8_t*)nullptr, (size_t)hc * 32)); FE_TRY(B.up(&d_ld, (const uint8_t*)nullptr, (size_t)hc * 32));
-    FE_TRY(B.up(&d_lf, (const uint8_t*)nullptr, (size_t)hc)); FE_TRY(B.up(&d_lp, (const float*)nullptr, (size_t)hc * 3));
-    FE_TRY(B.up(&d_pose, pose12, 12)); FE_TRY(B.up(&d_cc, &ncur, 1)); FE_TRY(B.up(&d_lc, &nlast, 1));
-    FE_TRY(B.up(&d_cs, (const int*)nullptr, GRID_CELLS + 1)); FE_TRY(B.up(&d_ci, (const int*)nullptr, (size_t)hc));
-    FE_TRY(B.up(&d_m, (const int*)nullptr, (size_t)hc)); FE_TRY(B.up(&d_nm, (const int*)nullptr, 1)); FE_TRY(B.up(&d_st, (const int*)nullptr, 1));
-    FE_TRY(B.put(d_ck, cur_kps, sizeof(viorb_keypoint) * ncur)); FE_TRY(B.put(d_cd, cur_desc, (size_t)32 * ncur));
-    FE_TRY(B.put(d_lk, last_kps, sizeof(viorb_keypoint) * nlast)); FE_TRY(B.put(d_ld, last_desc, (size_t)32 * nlast));
-    FE_TRY(B.put(d_lf, last_flags, (size_t)nlast)); FE_TRY(B.put(d_lp, last_Pw, sizeof(float) * 3 * nlast));
+    VIORB_TRY(B.up(&d_ck, (const viorb_keypoint*)nullptr, (size_t)hc)); VIORB_TRY(B.up(&d_lk, (const viorb_keypoint*)nullptr, (size_t)hc));
+    VIORB_TRY(B.up(&d_cd, (const uint8_t*)nullptr, (size_t)hc * 32)); VIORB_TRY(B.up(&d_ld, (const uint8_t*)nullptr, (size_t)hc * 32));
+    VIORB_TRY(B.up(&d_lf, (const uint8_t*)nullptr, (size_t)hc)); VIORB_TRY(B.up(&d_lp, (const float*)nullptr, (size_t)hc * 3));
+    VIORB_TRY(B.up(&d_pose, pose12, 12)); VIORB_TRY(B.up(&d_cc, &ncur, 1)); VIORB_TRY(B.up(&d_lc, &nlast, 1));
+    VIORB_TRY(B.up(&d_cs, (const int*)nullptr, GRID_CELLS + 1)); VIORB_TRY(B.up(&d_ci, (const int*)nullptr, (size_t)hc));
+    VIORB_TRY(B.up(&d_m, (const int*)nullptr, (size_t)hc)); VIORB_TRY(B.up(&d_nm, (const int*)nullptr, 1)); VIORB_TRY(B.up(&d_st, (const int*)nullptr, 1));
+    VIORB_TRY(B.put(d_ck, cur_kps, sizeof(viorb_keypoint) * ncur)); VIORB_TRY(B.put(d_cd, cur_desc, (size_t)32 * ncur));
+    VIORB_TRY(B.put(d_lk, last_kps, sizeof(viorb_keypoint) * nlast)); VIORB_TRY(B.put(d_ld, last_desc, (size_t)32 * nlast));
+    VIORB_TRY(B.put(d_lf, last_flags, (size_t)nlast)); VIORB_TRY(B.put(d_lp, last_Pw, sizeof(float) * 3 * nlast));
     float *d_ur = nullptr, *d_lpose = nullptr;
-    if (cur_uright) { FE_TRY(B.up(&d_ur, (const float*)nullptr, (size_t)hc)); FE_TRY(B.up(&d_lpose, last_pose12, 12)); FE_TRY(B.put(d_ur, cur_uright, sizeof(float) * ncur)); }
-    FE_TRY(B.flush());
-    FE_TRY(viorb_frontend_grid_device(h, d_ck, d_cc, 1, d_cs, d_ci, nullptr));
+    if (cur_uright) { VIORB_TRY(B.up(&d_ur, (const float*)nullptr, (size_t)hc)); VIORB_TRY(B.up(&d_lpose, last_pose12, 12)); VIORB_TRY(B.put(d_ur, cur_uright, sizeof(float) * ncur)); }
+    VIORB_TRY(B.flush());
+    VIORB_TRY(viorb_frontend_grid_device(h, d_ck, d_cc, 1, d_cs, d_ci, nullptr));
     if (cur_uright) {
-        FE_TRY(viorb_frontend_search_projection_stereo_device(h, d_ck, d_cd, d_cc, d_ur, d_cs, d_ci, d_pose, d_lpose, d_lk, d_lc, d_lf, d_lp, d_ld, th, bf, mb,
+        VIORB_TRY(viorb_frontend_search_projection_stereo_device(h, d_ck, d_cd, d_cc, d_ur, d_cs, d_ci, d_pose, d_lpose, d_lk, d_lc, d_lf, d_lp, d_ld, th, bf, mb,
                                                               0, 1, d_m, d_nm, d_st, nullptr));
     } else {
-        FE_TRY(viorb_frontend_search_projection_device(h, d_ck, d_cd, d_cc, d_cs, d_ci, d_pose, d_lk, d_lc, d_lf, d_lp, d_ld, th, 1, d_m, d_nm, d_st, nullptr));
+        VIORB_TRY(viorb_frontend_search_projection_device(h, d_ck, d_cd, d_cc, d_cs, d_ci, d_pose, d_lk, d_lc, d_lf, d_lp, d_ld, th, 1, d_m, d_nm, d_st, nullptr));
     }
     int st = 0;
     B.down(cur_match, d_m, sizeof(int) * ncur); B.down(nmatches, d_nm, sizeof(int)); B.down(&st, d_st, sizeof(int));
-    FE_TRY(B.fetch());
+    VIORB_TRY(B.fetch());
     if (st != VIORB_OK) { set_error("SearchByProjection(Frame, Frame): device status %d", st); return st; }
     return VIORB_OK;
 }
@@ -2317,19 +2316,19 @@ int viorb_fuse(const viorb_keypoint* kps, const uint8_t* desc, const float* urig
     c.nlevels = nlevels;
     for (int i = 0; i < 16; i++) { c.scale_factors[i] = scale_factors[i < nlevels ? i : nlevels - 1]; c.inv_level_sigma2[i] = inv_level_sigma2[i < nlevels ? i : nlevels - 1]; }
     viorb_frontend* h = nullptr;
-    FE_TRY(host_frontend(c, n, &h, true));
+    VIORB_TRY(host_frontend(c, n, &h, true));
     const size_t hc = (size_t)h->cap;
     DevBuf B; viorb_keypoint* d_k; uint8_t *d_d, *d_pv, *d_pd; float *d_ur, *d_pose, *d_pf; int *d_c, *d_cs, *d_ci, *d_pc, *d_bi, *d_nf;
-    FE_TRY(B.up(&d_k, (const viorb_keypoint*)nullptr, hc)); FE_TRY(B.up(&d_d, (const uint8_t*)nullptr, hc * 32)); FE_TRY(B.up(&d_ur, (const float*)nullptr, hc));
-    FE_TRY(B.put(d_k, kps, sizeof(viorb_keypoint) * n)); FE_TRY(B.put(d_d, desc, (size_t)32 * n)); FE_TRY(B.put(d_ur, uright, sizeof(float) * n));
-    FE_TRY(B.up(&d_pose, pose12, 12)); FE_TRY(B.up(&d_c, &n, 1)); FE_TRY(B.up(&d_cs, (const int*)nullptr, GRID_CELLS + 1)); FE_TRY(B.up(&d_ci, (const int*)nullptr, hc));
-    FE_TRY(B.up(&d_pf, pts_f, (size_t)npts * 8)); FE_TRY(B.up(&d_pv, pts_valid, (size_t)npts)); FE_TRY(B.up(&d_pd, pts_desc, (size_t)npts * 32));
-    FE_TRY(B.up(&d_pc, &npts, 1)); FE_TRY(B.up(&d_bi, (const int*)nullptr, (size_t)npts)); FE_TRY(B.up(&d_nf, (const int*)nullptr, 1));
-    FE_TRY(B.flush());
-    FE_TRY(viorb_frontend_grid_device(h, d_k, d_c, 1, d_cs, d_ci, nullptr));
-    FE_TRY(viorb_frontend_fuse_device(h, d_k, d_d, d_ur, d_c, d_cs, d_ci, d_pose, d_pf, d_pv, d_pd, d_pc, npts, th, intr5[4], 1, d_bi, d_nf, nullptr));
+    VIORB_TRY(B.up(&d_k, (const viorb_keypoint*)nullptr, hc)); VIORB_TRY(B.up(&d_d, (const uint8_t*)nullptr, hc * 32)); VIORB_TRY(B.up(&d_ur, (const float*)nullptr, hc));
+    VIORB_TRY(B.put(d_k, kps, sizeof(viorb_keypoint) * n)); VIORB_TRY(B.put(d_d, desc, (size_t)32 * n)); VIORB_TRY(B.put(d_ur, uright, sizeof(float) * n));
+    VIORB_TRY(B.up(&d_pose, pose12, 12)); VIORB_TRY(B.up(&d_c, &n, 1)); VIORB_TRY(B.up(&d_cs, (const int*)nullptr, GRID_CELLS + 1)); VIORB_TRY(B.up(&d_ci, (const int*)nullptr, hc));
+    VIORB_TRY(B.up(&d_pf, pts_f, (size_t)npts * 8)); VIORB_TRY(B.up(&d_pv, pts_valid, (size_t)npts)); VIORB_TRY(B.up(&d_pd, pts_desc, (size_t)npts * 32));
+    VIORB_TRY(B.up(&d_pc, &npts, 1)); VIORB_TRY(B.up(&d_bi, (const int*)nullptr, (size_t)npts)); VIORB_TRY(B.up(&d_nf, (const int*)nullptr, 1));
+    VIORB_TRY(B.flush());
+    VIORB_TRY(viorb_frontend_grid_device(h, d_k, d_c, 1, d_cs, d_ci, nullptr));
+    VIORB_TRY(viorb_frontend_fuse_device(h, d_k, d_d, d_ur, d_c, d_cs, d_ci, d_pose, d_pf, d_pv, d_pd, d_pc, npts, th, intr5[4], 1, d_bi, d_nf, nullptr));
     B.down(best_idx, d_bi, sizeof(int) * npts); B.down(nfused, d_nf, sizeof(int));
-    FE_TRY(B.fetch());
+    VIORB_TRY(B.fetch());
     return VIORB_OK;
 }
 
@@ -2352,31 +2351,31 @@ static int search_by_projection_points_host(const viorb_keypoint* cur_kps, const
     c.nlevels = nlevels;
     for (int i = 0; i < 16; i++) c.scale_factors[i] = scale_factors[i < nlevels ? i : nlevels - 1];
     viorb_frontend* h = nullptr;
-    FE_TRY(host_frontend(c, ncur, &h, true));
+    VIORB_TRY(host_frontend(c, ncur, &h, true));
     const size_t hc = (size_t)h->cap;
     DevBuf B; viorb_keypoint* d_k; uint8_t *d_d, *d_pfl, *d_pd, *d_own; float *d_pose, *d_pf, *d_fr = nullptr, *d_ur = nullptr, *d_xr = nullptr; int *d_c, *d_cs, *d_ci, *d_pc, *d_m, *d_nm, *d_st;
-    FE_TRY(B.up(&d_k, (const viorb_keypoint*)nullptr, hc)); FE_TRY(B.up(&d_d, (const uint8_t*)nullptr, hc * 32)); FE_TRY(B.up(&d_own, (const uint8_t*)nullptr, hc));
-    if (cur_uright) FE_TRY(B.up(&d_ur, (const float*)nullptr, hc));
-    FE_TRY(B.put(d_k, cur_kps, sizeof(viorb_keypoint) * ncur)); FE_TRY(B.put(d_d, cur_desc, (size_t)32 * ncur)); FE_TRY(B.put(d_own, cur_owner_obs, (size_t)ncur));
-    if (cur_uright) FE_TRY(B.put(d_ur, cur_uright, sizeof(float) * ncur));
-    FE_TRY(B.up(&d_pose, pose12, 12)); FE_TRY(B.up(&d_c, &ncur, 1)); FE_TRY(B.up(&d_cs, (const int*)nullptr, GRID_CELLS + 1)); FE_TRY(B.up(&d_ci, (const int*)nullptr, hc));
-    FE_TRY(B.up(&d_pf, pts_f, (size_t)npts * 8)); FE_TRY(B.up(&d_pfl, pts_flags, (size_t)npts)); FE_TRY(B.up(&d_pd, pts_desc, (size_t)npts * 32));
-    FE_TRY(B.up(&d_pc, &npts, 1)); FE_TRY(B.up(&d_m, (const int*)nullptr, hc)); FE_TRY(B.up(&d_nm, (const int*)nullptr, 1)); FE_TRY(B.up(&d_st, (const int*)nullptr, 1));
-    if (frustum5) FE_TRY(B.up(&d_fr, (const float*)nullptr, (size_t)npts * 5));
-    if (proj_xr) FE_TRY(B.up(&d_xr, (const float*)nullptr, (size_t)npts));
-    FE_TRY(B.flush());
-    FE_TRY(viorb_frontend_grid_device(h, d_k, d_c, 1, d_cs, d_ci, nullptr));
+    VIORB_TRY(B.up(&d_k, (const viorb_keypoint*)nullptr, hc)); VIORB_TRY(B.up(&d_d, (const uint8_t*)nullptr, hc * 32)); VIORB_TRY(B.up(&d_own, (const uint8_t*)nullptr, hc));
+    if (cur_uright) VIORB_TRY(B.up(&d_ur, (const float*)nullptr, hc));
+    VIORB_TRY(B.put(d_k, cur_kps, sizeof(viorb_keypoint) * ncur)); VIORB_TRY(B.put(d_d, cur_desc, (size_t)32 * ncur)); VIORB_TRY(B.put(d_own, cur_owner_obs, (size_t)ncur));
+    if (cur_uright) VIORB_TRY(B.put(d_ur, cur_uright, sizeof(float) * ncur));
+    VIORB_TRY(B.up(&d_pose, pose12, 12)); VIORB_TRY(B.up(&d_c, &ncur, 1)); VIORB_TRY(B.up(&d_cs, (const int*)nullptr, GRID_CELLS + 1)); VIORB_TRY(B.up(&d_ci, (const int*)nullptr, hc));
+    VIORB_TRY(B.up(&d_pf, pts_f, (size_t)npts * 8)); VIORB_TRY(B.up(&d_pfl, pts_flags, (size_t)npts)); VIORB_TRY(B.up(&d_pd, pts_desc, (size_t)npts * 32));
+    VIORB_TRY(B.up(&d_pc, &npts, 1)); VIORB_TRY(B.up(&d_m, (const int*)nullptr, hc)); VIORB_TRY(B.up(&d_nm, (const int*)nullptr, 1)); VIORB_TRY(B.up(&d_st, (const int*)nullptr, 1));
+    if (frustum5) VIORB_TRY(B.up(&d_fr, (const float*)nullptr, (size_t)npts * 5));
+    if (proj_xr) VIORB_TRY(B.up(&d_xr, (const float*)nullptr, (size_t)npts));
+    VIORB_TRY(B.flush());
+    VIORB_TRY(viorb_frontend_grid_device(h, d_k, d_c, 1, d_cs, d_ci, nullptr));
     if (cur_uright)
-        FE_TRY(viorb_frontend_search_local_points_stereo_device(h, d_k, d_d, d_c, d_ur, bf, d_cs, d_ci, d_pose, d_pf, d_pfl, d_pd, d_pc, npts, th, nnratio, d_own, 1, d_m,
+        VIORB_TRY(viorb_frontend_search_local_points_stereo_device(h, d_k, d_d, d_c, d_ur, bf, d_cs, d_ci, d_pose, d_pf, d_pfl, d_pd, d_pc, npts, th, nnratio, d_own, 1, d_m,
                                                                 d_nm, d_fr, d_xr, d_st, nullptr));
     else
-    FE_TRY(viorb_frontend_search_local_points_device(h, d_k, d_d, d_c, d_cs, d_ci, d_pose, d_pf, d_pfl, d_pd, d_pc, npts, th, nnratio, d_own, 1, d_m, d_nm, d_fr, d_st,
+    VIORB_TRY(viorb_frontend_search_local_points_device(h, d_k, d_d, d_c, d_cs, d_ci, d_pose, d_pf, d_pfl, d_pd, d_pc, npts, th, nnratio, d_own, 1, d_m, d_nm, d_fr, d_st,
                                                      nullptr));
     int st = 0;
     B.down(match, d_m, sizeof(int) * ncur); B.down(nmatches, d_nm, sizeof(int)); B.down(&st, d_st, sizeof(int));
     if (frustum5) B.down(frustum5, d_fr, sizeof(float) * 5 * (size_t)npts);
     if (proj_xr && d_xr) B.down(proj_xr, d_xr, sizeof(float) * (size_t)npts);
-    FE_TRY(B.fetch());
+    VIORB_TRY(B.fetch());
     if (st != VIORB_OK) { set_error("SearchByProjection(Frame, MapPoints): device status %d", st); return st; }
     return VIORB_OK;
 }
@@ -2403,16 +2402,16 @@ int viorb_preintegrate(const double* imu, int n_imu, const double bg[3], const d
     viorb_frontend_config c = default_cfg();
     for (int i = 0; i < 9; i += 4) c.cam[4 + i] = 1;
     viorb_frontend* h = nullptr;
-    FE_TRY(host_frontend(c, 64, &h));
+    VIORB_TRY(host_frontend(c, 64, &h));
     double ns[22]; memset(ns, 0, sizeof(ns)); ns[9] = 1; for (int k = 0; k < 3; k++) { ns[10 + k] = bg[k]; ns[13 + k] = ba[k]; }
     DevBuf B; double *d_imu, *d_tl, *d_tc, *d_ns, *d_pre, *d_cur; float* d_pose;
-    FE_TRY(B.up(&d_imu, imu, (size_t)n_imu * 7)); FE_TRY(B.up(&d_tl, &t_last, 1)); FE_TRY(B.up(&d_tc, &t_cur, 1));
-    FE_TRY(B.up(&d_ns, ns, 22)); FE_TRY(B.up(&d_pre, (const double*)nullptr, 142)); FE_TRY(B.up(&d_cur, (const double*)nullptr, 22));
-    FE_TRY(B.up(&d_pose, (const float*)nullptr, 12));
-    FE_TRY(B.flush());
-    FE_TRY(viorb_frontend_imu_predict_device(h, d_imu, n_imu, d_tl, d_tc, d_ns, 1, d_pre, d_cur, d_pose, nullptr));
+    VIORB_TRY(B.up(&d_imu, imu, (size_t)n_imu * 7)); VIORB_TRY(B.up(&d_tl, &t_last, 1)); VIORB_TRY(B.up(&d_tc, &t_cur, 1));
+    VIORB_TRY(B.up(&d_ns, ns, 22)); VIORB_TRY(B.up(&d_pre, (const double*)nullptr, 142)); VIORB_TRY(B.up(&d_cur, (const double*)nullptr, 22));
+    VIORB_TRY(B.up(&d_pose, (const float*)nullptr, 12));
+    VIORB_TRY(B.flush());
+    VIORB_TRY(viorb_frontend_imu_predict_device(h, d_imu, n_imu, d_tl, d_tc, d_ns, 1, d_pre, d_cur, d_pose, nullptr));
     B.down(preint142, d_pre, 142 * sizeof(double));
-    FE_TRY(B.fetch());
+    VIORB_TRY(B.fetch());
     return VIORB_OK;
 }
 
@@ -2429,25 +2428,25 @@ int viorb_pose_opt_vi(int variant, int compute_marg, const double cur_ns[22], co
     for (int i = 0; i < 3; i++) c.gravity[i] = gw[i];
     const int cap = std::max(std::max(n_cur, n_last), 1);
     viorb_frontend* h = nullptr;
-    FE_TRY(host_frontend(c, cap, &h));
+    VIORB_TRY(host_frontend(c, cap, &h));
     DevBuf B; double *d_cur, *d_last, *d_prior, *d_mci, *d_pre, *d_oc, *d_ol, *d_out, *d_outl, *d_marg, *d_info; int *d_nc, *d_nl; uint8_t *d_fc, *d_fl;
     double zero22[22] = {0}, zero144[144] = {0};
-    FE_TRY(B.up(&d_cur, cur_ns, 22)); FE_TRY(B.up(&d_last, last_ns, 22)); FE_TRY(B.up(&d_prior, prior_ns ? prior_ns : zero22, 22));
-    FE_TRY(B.up(&d_mci, marg_cov_inv144 ? marg_cov_inv144 : zero144, 144)); FE_TRY(B.up(&d_pre, preint, 142));
-    FE_TRY(B.up(&d_oc, obs_cur, (size_t)n_cur * 6)); FE_TRY(B.up(&d_ol, obs_last, (size_t)n_last * 6));
-    FE_TRY(B.up(&d_out, (const double*)nullptr, 22)); FE_TRY(B.up(&d_outl, (const double*)nullptr, 22));
-    FE_TRY(B.up(&d_marg, (const double*)nullptr, 144)); FE_TRY(B.up(&d_info, (const double*)nullptr, 4));
-    FE_TRY(B.up(&d_nc, &n_cur, 1)); FE_TRY(B.up(&d_nl, &n_last, 1));
-    FE_TRY(B.up(&d_fc, (const uint8_t*)nullptr, cap)); FE_TRY(B.up(&d_fl, (const uint8_t*)nullptr, cap));
-    FE_TRY(B.flush());
-    FE_TRY(viorb_frontend_pose_opt_device(h, variant, compute_marg, d_cur, d_last, d_prior, d_mci, d_pre, d_oc, d_nc, d_ol, d_nl, 1,
+    VIORB_TRY(B.up(&d_cur, cur_ns, 22)); VIORB_TRY(B.up(&d_last, last_ns, 22)); VIORB_TRY(B.up(&d_prior, prior_ns ? prior_ns : zero22, 22));
+    VIORB_TRY(B.up(&d_mci, marg_cov_inv144 ? marg_cov_inv144 : zero144, 144)); VIORB_TRY(B.up(&d_pre, preint, 142));
+    VIORB_TRY(B.up(&d_oc, obs_cur, (size_t)n_cur * 6)); VIORB_TRY(B.up(&d_ol, obs_last, (size_t)n_last * 6));
+    VIORB_TRY(B.up(&d_out, (const double*)nullptr, 22)); VIORB_TRY(B.up(&d_outl, (const double*)nullptr, 22));
+    VIORB_TRY(B.up(&d_marg, (const double*)nullptr, 144)); VIORB_TRY(B.up(&d_info, (const double*)nullptr, 4));
+    VIORB_TRY(B.up(&d_nc, &n_cur, 1)); VIORB_TRY(B.up(&d_nl, &n_last, 1));
+    VIORB_TRY(B.up(&d_fc, (const uint8_t*)nullptr, cap)); VIORB_TRY(B.up(&d_fl, (const uint8_t*)nullptr, cap));
+    VIORB_TRY(B.flush());
+    VIORB_TRY(viorb_frontend_pose_opt_device(h, variant, compute_marg, d_cur, d_last, d_prior, d_mci, d_pre, d_oc, d_nc, d_ol, d_nl, 1,
                                           d_out, d_outl, d_fc, d_fl, d_marg, d_info, nullptr));
     B.down(out_ns, d_out, 22 * sizeof(double)); B.down(out_last_ns, d_outl, 22 * sizeof(double));
     if (n_cur) B.down(outlier_cur, d_fc, n_cur);
     if (n_last && outlier_last && variant) B.down(outlier_last, d_fl, n_last);
     if (compute_marg && marg_out144) B.down(marg_out144, d_marg, 144 * sizeof(double));
     B.down(info, d_info, 4 * sizeof(double));
-    FE_TRY(B.fetch());
+    VIORB_TRY(B.fetch());
     return VIORB_OK;
 }
 
@@ -2458,15 +2457,15 @@ int viorb_pose_opt_se3(const float pose12[12], const float intr5[5], const doubl
     c.fx = intr5[0]; c.fy = intr5[1]; c.cx = intr5[2]; c.cy = intr5[3];
     const int cap = std::max(n, 1);
     viorb_frontend* h = nullptr;
-    FE_TRY(host_frontend(c, cap, &h));
+    VIORB_TRY(host_frontend(c, cap, &h));
     DevBuf B; float *d_p, *d_o; double *d_obs, *d_info; int* d_n; uint8_t* d_f;
-    FE_TRY(B.up(&d_p, pose12, 12)); FE_TRY(B.up(&d_o, (const float*)nullptr, 12)); FE_TRY(B.up(&d_obs, obs7, (size_t)n * 7));
-    FE_TRY(B.up(&d_info, (const double*)nullptr, 4)); FE_TRY(B.up(&d_n, &n, 1)); FE_TRY(B.up(&d_f, (const uint8_t*)nullptr, (size_t)cap));
-    FE_TRY(B.flush());
-    FE_TRY(viorb_frontend_pose_opt_se3_device(h, d_p, d_obs, d_n, (double)intr5[4], 1, d_o, d_f, d_info, nullptr));
+    VIORB_TRY(B.up(&d_p, pose12, 12)); VIORB_TRY(B.up(&d_o, (const float*)nullptr, 12)); VIORB_TRY(B.up(&d_obs, obs7, (size_t)n * 7));
+    VIORB_TRY(B.up(&d_info, (const double*)nullptr, 4)); VIORB_TRY(B.up(&d_n, &n, 1)); VIORB_TRY(B.up(&d_f, (const uint8_t*)nullptr, (size_t)cap));
+    VIORB_TRY(B.flush());
+    VIORB_TRY(viorb_frontend_pose_opt_se3_device(h, d_p, d_obs, d_n, (double)intr5[4], 1, d_o, d_f, d_info, nullptr));
     B.down(out_pose12, d_o, 12 * sizeof(float)); if (n) B.down(outlier, d_f, n);
     B.down(info, d_info, 4 * sizeof(double));
-    FE_TRY(B.fetch());
+    VIORB_TRY(B.fetch());
     return VIORB_OK;
 }
 

@@ -22,7 +22,6 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <vector>
 #include "viorb_common.h"
 #include "global_ba_core.h"
@@ -552,27 +551,10 @@ __global__ __launch_bounds__(256) void k_gba_update(GbaDev D, double lambda) {
 }
 
 namespace {
-// A solve borrows a context (stream, arena, page-locked scalars) from a pool of its own, so that concurrent callers run on different
-// streams and no call pays hipMalloc / hipFree once its arena has grown to the problem's size.
-struct GbaCtx { hipStream_t st = nullptr; void* arena = nullptr; size_t bytes = 0; double* pinned = nullptr; int device = 0; };
-std::mutex g_gba_mu;
-std::vector<GbaCtx*> g_gba_free;
-struct GbaLease {
-    GbaCtx* c = nullptr;
-    // an error path may leave work queued on the stream: nothing of it may still run when the next caller takes the context
-    ~GbaLease() { if (c) { (void)hipStreamSynchronize(c->st); std::lock_guard<std::mutex> lk(g_gba_mu); g_gba_free.push_back(c); } }
-    bool ready() {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return false;
-        {
-            std::lock_guard<std::mutex> lk(g_gba_mu);
-            for (size_t i = 0; i < g_gba_free.size(); i++) if (g_gba_free[i]->device == dev) { c = g_gba_free[i]; g_gba_free.erase(g_gba_free.begin() + i); break; }
-        }
-        if (c) return true;
-        c = new GbaCtx(); c->device = dev;
-        if (hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) != hipSuccess || hipHostMalloc(reinterpret_cast<void**>(&c->pinned), 16 * sizeof(double)) != hipSuccess) { delete c; c = nullptr; return false; }
-        return true;
-    }
+// The host form's lease of a stream context. An error path may leave work queued on the stream: nothing of it may still run when the
+// next borrower takes the context, so the stream is drained before the context goes back. The arena grows to exactly what is asked for.
+struct GbaArena : StreamCtxLease {
+    ~GbaArena() { if (c) (void)hipStreamSynchronize(c->st); }
     bool reserve(size_t bytes) {
         if (c->bytes >= bytes) return true;
         if (c->arena) (void)hipFree(c->arena);
@@ -584,22 +566,11 @@ struct GbaLease {
 };
 // accept (1) / reject (0) of every trial of the calling thread's last solve, for viorb_debug_gba_last_trials
 thread_local std::vector<uint8_t> g_gba_trials;
-bool gba_no_device() {
-    if (viorb_device_count() >= 1) return false;
-    set_error("no HIP device: libviorb_hip has no CPU fallback");
-    return true;
-}
 
-// lays the work arrays out in a workspace; S (the only array whose size depends on the number of free key frames) comes last
-struct GbaLayout {
-    size_t off = 0;
-    uint8_t* base;
-    explicit GbaLayout(void* b) : base(static_cast<uint8_t*>(b)) {}
-    template <class T> void take(T** p, size_t n) { off = (off + 255) & ~(size_t)255; if (p) *p = reinterpret_cast<T*>(base + off); off += (n ? n : 1) * sizeof(T); }
-};
-// returns the bytes up to S (head) and in all; nfree < 0: only the head is laid out
+// Lays the work arrays out in a workspace; S (the only array whose size depends on the number of free key frames) comes last.
+// Returns the bytes up to S (head) and in all; nfree < 0: only the head is laid out
 size_t gba_layout(GbaDev& D, void* base, int nk, int np, int ne, int nfree, size_t* head_bytes) {
-    GbaLayout L(base);
+    WorkspaceLayout L(base);
     L.take(&D.scal, GBA_S_N); L.take(&D.status, GBA_ST_N);
     L.take(&D.pt_start, (size_t)np + 1); L.take(&D.kf_cur, nk);           // cleared together with scal / status: see gba_run
     const size_t clear_bytes = L.off;
@@ -612,36 +583,38 @@ size_t gba_layout(GbaDev& D, void* base, int nk, int np, int ne, int nfree, size
     L.take(&D.rhs, (size_t)gba_ld(12 * nk)); L.take(&D.xp, (size_t)gba_ld(12 * nk));
     L.take(static_cast<double**>(nullptr), 0);
     if (head_bytes) *head_bytes = clear_bytes;
-    const size_t head = (L.off + 255) & ~(size_t)255;
+    const size_t head = L.end();
     if (nfree < 0) return head;
     const size_t ld = gba_ld(12 * nfree);
     D.S = reinterpret_cast<double*>(static_cast<uint8_t*>(base) + head);
     return head + ld * ld * sizeof(double);
 }
 
-#define GBA_LAUNCH(kernel, grid, block, ...) do { ProfScope ps_(#kernel, st); hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, __VA_ARGS__); } while (0)
 inline unsigned gba_blocks(size_t n, unsigned per) { return (unsigned)std::max<size_t>(1, (n + per - 1) / per); }
 
 // the factorisation chain + both substitutions; S and rhs hold the system, xp receives the solution
-void gba_factor_solve(const GbaDev& D, hipStream_t st, bool solve) {
+int gba_factor_solve(const GbaDev& D, hipStream_t st, bool solve) {
     const int T = D.ld / GBA_NB;
     for (int kb = 0; kb < T; kb++) {
-        GBA_LAUNCH(k_gba_potrf, 1, 64, D, kb);
-        GBA_LAUNCH(k_gba_trsm, T - kb, 64, D, kb, T);
-        if (kb + 1 < T) GBA_LAUNCH(k_gba_syrk, dim3(T - kb - 1, T - kb), 256, D, kb, T - kb - 1);
+        VIORB_LAUNCH(k_gba_potrf, 1, 64, 0, st, D, kb);
+        VIORB_LAUNCH(k_gba_trsm, T - kb, 64, 0, st, D, kb, T);
+        if (kb + 1 < T) VIORB_LAUNCH(k_gba_syrk, dim3(T - kb - 1, T - kb), 256, 0, st, D, kb, T - kb - 1);
     }
-    if (solve) for (int kb = T - 1; kb >= 0; kb--) GBA_LAUNCH(k_gba_bwd, gba_blocks((size_t)kb * GBA_NB, 256), 256, D, kb);
+    if (solve) for (int kb = T - 1; kb >= 0; kb--) VIORB_LAUNCH(k_gba_bwd, gba_blocks((size_t)kb * GBA_NB, 256), 256, 0, st, D, kb);
+    return VIORB_OK;
 }
 
-void gba_errors(const GbaDev& D, hipStream_t st) {
-    if (D.ne) GBA_LAUNCH(k_gba_errors, gba_blocks(D.ne, 256), 256, D);
-    GBA_LAUNCH(k_gba_imu_errors, gba_blocks(D.nk, 256), 256, D);
+int gba_errors(const GbaDev& D, hipStream_t st) {
+    if (D.ne) VIORB_LAUNCH(k_gba_errors, gba_blocks(D.ne, 256), 256, 0, st, D);
+    VIORB_LAUNCH(k_gba_imu_errors, gba_blocks(D.nk, 256), 256, 0, st, D);
+    return VIORB_OK;
 }
-void gba_linearise(const GbaDev& D, hipStream_t st) {
-    if (D.ne) GBA_LAUNCH(k_gba_lin_edges, gba_blocks(D.ne, 256), 256, D);
-    if (D.np) GBA_LAUNCH(k_gba_hll, gba_blocks(D.np, 256), 256, D);
-    GBA_LAUNCH(k_gba_hpp, D.nk, 256, D);
-    GBA_LAUNCH(k_gba_imu, D.nk, 64, D);
+int gba_linearise(const GbaDev& D, hipStream_t st) {
+    if (D.ne) VIORB_LAUNCH(k_gba_lin_edges, gba_blocks(D.ne, 256), 256, 0, st, D);
+    if (D.np) VIORB_LAUNCH(k_gba_hll, gba_blocks(D.np, 256), 256, 0, st, D);
+    VIORB_LAUNCH(k_gba_hpp, D.nk, 256, 0, st, D);
+    VIORB_LAUNCH(k_gba_imu, D.nk, 64, 0, st, D);
+    return VIORB_OK;
 }
 
 // The solve proper on device-resident inputs. `pinned`: 16 page-locked doubles. kf / pt (the working states) are kfs_out / points_out.
@@ -651,8 +624,8 @@ int gba_run(const viorb_gba_config* cfg, GbaDev& D, void* workspace, size_t work
     const size_t head = gba_layout(D, workspace, D.nk, D.np, D.ne, -1, &clear_bytes);
     if (head > workspace_bytes) { set_error("global BA: workspace of %zu bytes, %zu needed", workspace_bytes, head); return VIORB_ERR_CAPACITY; }
     VIORB_HIP_TRY(hipMemsetAsync(workspace, 0, clear_bytes, st));
-    GBA_LAUNCH(k_gba_setup, 1, 256, D);
-    if (D.ne) GBA_LAUNCH(k_gba_edges_scan, gba_blocks(D.ne, 256), 256, D);
+    VIORB_LAUNCH(k_gba_setup, 1, 256, 0, st, D);
+    if (D.ne) VIORB_LAUNCH(k_gba_edges_scan, gba_blocks(D.ne, 256), 256, 0, st, D);
     VIORB_HIP_TRY(hipMemcpyAsync(pinned, D.status, GBA_ST_N * sizeof(int), hipMemcpyDeviceToHost, st));
     VIORB_HIP_TRY(hipStreamSynchronize(st));
     const int* hst = reinterpret_cast<const int*>(pinned);
@@ -666,9 +639,9 @@ int gba_run(const viorb_gba_config* cfg, GbaDev& D, void* workspace, size_t work
     const size_t total = gba_layout(D, workspace, D.nk, D.np, D.ne, D.nfree, nullptr);
     if (total > workspace_bytes) { set_error("global BA: workspace of %zu bytes, %zu needed", workspace_bytes, total); return VIORB_ERR_CAPACITY; }
     if (D.ne) {
-        GBA_LAUNCH(k_gba_kf_offsets, 1, 64, D);
-        GBA_LAUNCH(k_gba_kf_fill, gba_blocks(D.ne, 256), 256, D);
-        GBA_LAUNCH(k_gba_kf_sort, D.nk, 256, D);
+        VIORB_LAUNCH(k_gba_kf_offsets, 1, 64, 0, st, D);
+        VIORB_LAUNCH(k_gba_kf_fill, gba_blocks(D.ne, 256), 256, 0, st, D);
+        VIORB_LAUNCH(k_gba_kf_sort, D.nk, 256, 0, st, D);
     } else VIORB_HIP_TRY(hipMemsetAsync(D.kf_start, 0, ((size_t)D.nk + 1) * sizeof(int), st));
 
     auto stopped = [&]() { return stop && *stop; };
@@ -678,9 +651,9 @@ int gba_run(const viorb_gba_config* cfg, GbaDev& D, void* workspace, size_t work
         return VIORB_OK;
     };
     const size_t S_bytes = (size_t)D.ld * D.ld * sizeof(double);
-    gba_errors(D, st);
-    gba_linearise(D, st);
-    GBA_LAUNCH(k_gba_max_diag, gba_blocks((size_t)D.n + 3 * (size_t)D.np, 256 * 8), 256, D);
+    VIORB_TRY(gba_errors(D, st));
+    VIORB_TRY(gba_linearise(D, st));
+    VIORB_LAUNCH(k_gba_max_diag, gba_blocks((size_t)D.n + 3 * (size_t)D.np, 256 * 8), 256, 0, st, D);
     if (int rc = read_scal()) return rc;
     gba_lm L; L.cur = pinned[GBA_S_CHI]; L.lambda = 1e-5 * pinned[GBA_S_MAXDIAG]; L.ni = 2;
     const double chi_before = L.cur;
@@ -689,8 +662,8 @@ int gba_run(const viorb_gba_config* cfg, GbaDev& D, void* workspace, size_t work
     bool stale = false;
     for (int it = 0; it < cfg->iterations && !stopped(); it++) {
         if (it > 0) {                                      // err[] is that of the accepted trial = the current state
-            if (stale) { gba_errors(D, st); stale = false; }   // unless the last trial was rejected and restored
-            gba_linearise(D, st);
+            if (stale) { VIORB_TRY(gba_errors(D, st)); stale = false; }   // unless the last trial was rejected and restored
+            VIORB_TRY(gba_linearise(D, st));
         }
         const double ini = L.cur;
         VIORB_HIP_TRY(hipMemcpyAsync(D.kf_bak, D.kf, (size_t)D.nk * 22 * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -699,13 +672,13 @@ int gba_run(const viorb_gba_config* cfg, GbaDev& D, void* workspace, size_t work
         do {
             VIORB_HIP_TRY(hipMemsetAsync(D.scal, 0, 3 * sizeof(double), st));
             VIORB_HIP_TRY(hipMemsetAsync(D.S, 0, S_bytes, st));
-            if (D.np) GBA_LAUNCH(k_gba_dinv, gba_blocks(D.np, 256), 256, D, L.lambda);
-            GBA_LAUNCH(k_gba_init_reduced, D.nk + gba_blocks(D.ld, 256), 256, D, L.lambda);
-            if (D.np && D.ne) GBA_LAUNCH(k_gba_schur, D.np, 64, D);
-            gba_factor_solve(D, st, true);
-            if (D.np) GBA_LAUNCH(k_gba_backsub, gba_blocks(D.np, 256), 256, D);
-            GBA_LAUNCH(k_gba_update, gba_blocks(std::max(D.nk, D.np), 256), 256, D, L.lambda);
-            gba_errors(D, st);
+            if (D.np) VIORB_LAUNCH(k_gba_dinv, gba_blocks(D.np, 256), 256, 0, st, D, L.lambda);
+            VIORB_LAUNCH(k_gba_init_reduced, D.nk + gba_blocks(D.ld, 256), 256, 0, st, D, L.lambda);
+            if (D.np && D.ne) VIORB_LAUNCH(k_gba_schur, D.np, 64, 0, st, D);
+            VIORB_TRY(gba_factor_solve(D, st, true));
+            if (D.np) VIORB_LAUNCH(k_gba_backsub, gba_blocks(D.np, 256), 256, 0, st, D);
+            VIORB_LAUNCH(k_gba_update, gba_blocks(std::max(D.nk, D.np), 256), 256, 0, st, D, L.lambda);
+            VIORB_TRY(gba_errors(D, st));
             if (int rc = read_scal()) return rc;
             const bool ok = pinned[GBA_S_FAIL] == 0.0;
             if (!ok) nfail++;
@@ -753,7 +726,7 @@ extern "C" int viorb_global_ba_navstate_device(const viorb_gba_config* cfg, cons
     if (int rc = gba_check_config(cfg, nk, np, ne)) return rc;
     VIORB_REQUIRE(kfs && prev && fixed && preint && gw && cam && kfs_out && info && workspace, "NULL argument");
     VIORB_REQUIRE((np == 0 || (points && points_out && point_included)) && (ne == 0 || (edge_idx && edge_obs && np > 0)), "NULL point or edge array");
-    if (gba_no_device()) return VIORB_ERR_NO_DEVICE;
+    VIORB_TRY(require_device());
     hipStream_t st = (hipStream_t)stream;
     for (int k = 0; k < 6; k++) info[k] = 0;
     g_gba_trials.clear();
@@ -802,24 +775,24 @@ extern "C" int viorb_global_ba_navstate(const viorb_gba_config* cfg, const doubl
         for (int k = 0; k < ne; k++) point_included[edge_idx[2 * k]] = 1;
         return VIORB_OK;
     }
-    if (gba_no_device()) return VIORB_ERR_NO_DEVICE;
-    GbaLease lease;
+    VIORB_TRY(require_device());
+    GbaArena lease;
     if (!lease.ready()) { set_error("global BA: no stream"); return VIORB_ERR_HIP; }
     hipStream_t st = lease.c->st;
     // arena = inputs | states | workspace
     GbaDev D{};
-    GbaLayout in(nullptr);
+    WorkspaceLayout in(nullptr);
     double *d_kf, *d_pt, *d_preint, *d_obs; int32_t *d_prev, *d_eidx; uint8_t *d_fixed, *d_inc;
-    auto lay = [&](GbaLayout& L) {
+    auto lay = [&](WorkspaceLayout& L) {
         L.take(&d_kf, (size_t)nk * 22); L.take(&d_pt, (size_t)np * 3); L.take(&d_preint, (size_t)nk * 142); L.take(&d_obs, (size_t)ne * 3);
         L.take(&d_prev, nk); L.take(&d_eidx, (size_t)ne * 2); L.take(&d_fixed, nk); L.take(&d_inc, np);
         L.take(static_cast<double**>(nullptr), 0);
     };
     lay(in);
-    const size_t in_bytes = (in.off + 255) & ~(size_t)255;
+    const size_t in_bytes = in.end();
     const size_t ws_bytes = gba_layout(D, nullptr, nk, np, ne, nfree, nullptr);
     if (!lease.reserve(in_bytes + ws_bytes)) { set_error("global BA: hipMalloc of %zu bytes failed", in_bytes + ws_bytes); return VIORB_ERR_HIP; }
-    GbaLayout at(lease.c->arena);
+    WorkspaceLayout at(lease.c->arena);
     lay(at);
     void* ws = static_cast<uint8_t*>(lease.c->arena) + in_bytes;
     VIORB_HIP_TRY(hipMemcpyAsync(d_kf, kfs, (size_t)nk * 22 * sizeof(double), hipMemcpyHostToDevice, st));
@@ -837,7 +810,7 @@ extern "C" int viorb_global_ba_navstate(const viorb_gba_config* cfg, const doubl
     for (int k = 0; k < 16; k++) D.cam[k] = cam[k];
     for (int k = 0; k < 3; k++) D.gw[k] = gw[k];
     const int rc = gba_run(cfg, D, ws, ws_bytes, stop, lease.c->pinned, info, st);
-    if (rc != VIORB_OK) { (void)hipStreamSynchronize(st); return rc; }
+    if (rc != VIORB_OK) return rc;
     VIORB_HIP_TRY(hipMemcpyAsync(kfs_out, d_kf, (size_t)nk * 22 * sizeof(double), hipMemcpyDeviceToHost, st));
     if (np) {
         VIORB_HIP_TRY(hipMemcpyAsync(points_out, d_pt, (size_t)np * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -851,8 +824,8 @@ extern "C" int viorb_global_ba_navstate(const viorb_gba_config* cfg, const doubl
 // triangle zero); *ok = 0 when a pivot was not positive and finite (L is then left untouched).
 extern "C" int viorb_debug_gba_cholesky(const double* A, int n, double* L, int32_t* ok) {
     VIORB_REQUIRE(A && L && ok && n >= 1 && n <= 12 * GBA_MAX_FREE_KF, "A, L, ok; 1 <= n <= 24576");
-    if (gba_no_device()) return VIORB_ERR_NO_DEVICE;
-    GbaLease lease;
+    VIORB_TRY(require_device());
+    GbaArena lease;
     if (!lease.ready()) { set_error("global BA: no stream"); return VIORB_ERR_HIP; }
     hipStream_t st = lease.c->st;
     const size_t ld = gba_ld(n), S_bytes = ld * ld * sizeof(double);
@@ -863,7 +836,7 @@ extern "C" int viorb_debug_gba_cholesky(const double* A, int n, double* L, int32
     VIORB_HIP_TRY(hipMemcpy2DAsync(D.S, ld * sizeof(double), A, (size_t)n * sizeof(double), (size_t)n * sizeof(double), n, hipMemcpyHostToDevice, st));
     std::vector<double> ones(ld - n, 1.0);
     if (ld > (size_t)n) VIORB_HIP_TRY(hipMemcpy2DAsync(D.S + (size_t)n * ld + n, (ld + 1) * sizeof(double), ones.data(), sizeof(double), sizeof(double), ld - n, hipMemcpyHostToDevice, st));
-    gba_factor_solve(D, st, false);
+    VIORB_TRY(gba_factor_solve(D, st, false));
     VIORB_HIP_TRY(hipMemcpyAsync(lease.c->pinned, D.scal, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
     VIORB_HIP_TRY(hipStreamSynchronize(st));
     *ok = lease.c->pinned[GBA_S_FAIL] == 0.0;

@@ -59,12 +59,6 @@ __global__ __launch_bounds__(BF_THREADS) void k_match_bruteforce(const uint8_t* 
     }
 }
 
-struct BfBuf {
-    std::vector<void*> p;
-    ~BfBuf() { for (void* x : p) (void)hipFree(x); }
-    template <class T> bool get(T** out, size_t n) { void* d = nullptr; if (hipMalloc(&d, sizeof(T) * (n ? n : 1)) != hipSuccess) return false; p.push_back(d); *out = (T*)d; return true; }
-};
-
 } // namespace viorb
 
 using namespace viorb;
@@ -75,10 +69,8 @@ int viorb_match_bruteforce_device(const uint8_t* q_desc, const int32_t* nq, int 
                                   int batch, int32_t* best, int32_t* second, int32_t* idx, void* stream) {
     VIORB_REQUIRE(q_desc && nq && c_desc && nc && best && second && idx, "null array");
     VIORB_REQUIRE(qcap >= 1 && ccap >= 1 && batch >= 1 && batch <= 65535, "qcap, ccap >= 1, 1 <= batch <= 65535");
-    ProfScope ps("k_match_bruteforce", (hipStream_t)stream);
-    hipLaunchKernelGGL(k_match_bruteforce, dim3((qcap + BF_THREADS - 1) / BF_THREADS, batch), dim3(BF_THREADS), 0, (hipStream_t)stream,
-                       q_desc, nq, qcap, c_desc, nc, ccap, best, second, idx);
-    VIORB_HIP_TRY(hipGetLastError());
+    VIORB_LAUNCH(k_match_bruteforce, dim3((qcap + BF_THREADS - 1) / BF_THREADS, batch), BF_THREADS, 0, (hipStream_t)stream,
+                 q_desc, nq, qcap, c_desc, nc, ccap, best, second, idx);
     return VIORB_OK;
 }
 
@@ -86,15 +78,12 @@ int viorb_match_bruteforce(const uint8_t* q, int nq, const uint8_t* c, int nc, i
     VIORB_REQUIRE(nq >= 0 && nc >= 0, "negative count");
     if (nq == 0) return VIORB_OK;
     VIORB_REQUIRE(q && best && second && idx && (c || nc == 0), "null array");
-    if (viorb_device_count() < 1) { set_error("no HIP device: libviorb_hip has no CPU fallback"); return VIORB_ERR_NO_DEVICE; }
-    BfBuf B; uint8_t *dq, *dc; int *dn, *db, *ds, *di;
-    if (!(B.get(&dq, (size_t)32 * nq) && B.get(&dc, (size_t)32 * (nc ? nc : 1)) && B.get(&dn, 2) && B.get(&db, nq) && B.get(&ds, nq) && B.get(&di, nq))) {
-        set_error("device allocation failed"); return VIORB_ERR_HIP;
-    }
+    VIORB_TRY(require_device());
     const int cnt[2] = {nq, nc};
-    VIORB_HIP_TRY(hipMemcpy(dq, q, (size_t)32 * nq, hipMemcpyHostToDevice));
-    if (nc) VIORB_HIP_TRY(hipMemcpy(dc, c, (size_t)32 * nc, hipMemcpyHostToDevice));
-    VIORB_HIP_TRY(hipMemcpy(dn, cnt, sizeof(cnt), hipMemcpyHostToDevice));
+    DeviceBufs B;
+    uint8_t *dq = B.up(q, (size_t)32 * nq), *dc = B.up(c, (size_t)32 * nc, 32);
+    int *dn = B.up(cnt, 2), *db = B.zeros<int>(nq), *ds = B.zeros<int>(nq), *di = B.zeros<int>(nq);
+    if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
     int rc = viorb_match_bruteforce_device(dq, dn, nq, dc, dn + 1, nc ? nc : 1, 1, db, ds, di, nullptr);
     if (rc != VIORB_OK) return rc;
     VIORB_HIP_TRY(hipDeviceSynchronize());

@@ -22,7 +22,6 @@
 #include <cmath>
 #include <cstdlib>
 #include <limits>
-#include <mutex>
 #include "viorb_common.h"
 #include "vio_core.h"
 
@@ -1138,16 +1137,6 @@ __global__ void k_bab_gate(const BaDev* __restrict__ Dv, uint8_t* const* __restr
 using namespace viorb;
 
 namespace {
-// A solve borrows a context (a HIP stream + a device arena) from a small pool, so that concurrent callers (the LocalMapping threads
-// of several SLAM instances) run on different streams and no call pays hipMalloc / hipFree, which synchronise the whole device.
-struct BaCtx {
-    hipStream_t st = nullptr; void* arena = nullptr; size_t bytes = 0;
-    double* pinned = nullptr;           // 64 doubles of page-locked host memory for the LM scalars
-    uint8_t* stage = nullptr; size_t stage_bytes = 0;       // page-locked staging copy of a window's inputs (lives until the context's next window)
-    int device = 0;
-};
-std::mutex g_ctx_mu;
-std::vector<BaCtx*> g_ctx_free;
 std::atomic<int> g_lba_device{-1};
 // The device the window solves run on: viorb_local_ba_set_device(), else the calling thread's current HIP device (what
 // torch.cuda.set_device(LOCAL_RANK) / hipSetDevice selected), so that under torchrun every rank's windows land on its own GPU.
@@ -1156,28 +1145,6 @@ static int lba_device() {
     if (d < 0 && hipGetDevice(&d) != hipSuccess) d = 0;
     return d;
 }
-struct BaCtxLease {
-    BaCtx* c = nullptr;
-    BaCtxLease() {}
-    ~BaCtxLease() { if (c) { std::lock_guard<std::mutex> lk(g_ctx_mu); g_ctx_free.push_back(c); } }
-    bool ready() {                     // the calling thread has selected the device (hipSetDevice(lba_device()))
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return false;
-        if (!c) {
-            std::lock_guard<std::mutex> lk(g_ctx_mu);
-            for (size_t i = 0; i < g_ctx_free.size(); i++)
-                if (g_ctx_free[i]->device == dev) { c = g_ctx_free[i]; g_ctx_free.erase(g_ctx_free.begin() + i); break; }
-        }
-        if (!c) {
-            c = new BaCtx();
-            c->device = dev;
-            if (hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) != hipSuccess || hipHostMalloc(reinterpret_cast<void**>(&c->pinned), 64 * sizeof(double)) != hipSuccess) {
-                delete c; c = nullptr; return false;
-            }
-        }
-        return true;
-    }
-};
 // alloc() lays the arrays out in a host mirror (inputs copied, work arrays zero); commit() uploads the mirror into the context's
 // arena in one copy and patches the recorded pointers.
 struct BaBuf {
@@ -1211,7 +1178,7 @@ struct BaBuf {
         *d = nullptr;
         return true;
     }
-    bool commit(BaCtx* c) {
+    bool commit(StreamCtx* c) {
         const size_t in_bytes = (mirror.size() + 255) & ~(size_t)255, zero_bytes = (work_bytes + 255) & ~(size_t)255, total = in_bytes + zero_bytes + raw_bytes;
         if (c->bytes < total) {
             if (c->arena) (void)hipFree(c->arena);
@@ -1276,7 +1243,7 @@ static hipError_t ba_wait(hipStream_t st, BaSolve* const* S = nullptr, int n = 0
 // calls; a batch keeps several windows in flight from one host thread (several host threads slow each other down inside the HIP runtime).
 enum { BA_WAIT = 0, BA_DONE = 1, BA_PIN_ABORT = 56 };              // pinned[56]: the mirrored stop flag (a 64-bit word; 0..39 LM scalars, 48 the batch's done counter)
 struct BaSolve {
-    BaCtxLease lease;
+    StreamCtxLease lease;         // of the calling thread's current device: the caller has selected it (hipSetDevice(lba_device()))
     BaDev D; hipStream_t st = nullptr; double* h = nullptr;       // h: 64 page-locked doubles (0..7 scal, 8..39 ctl)
     int model = 0; const volatile int* stop = nullptr; uint8_t* d_erase = nullptr;
     double* kfs_out = nullptr; double* points_out = nullptr; uint8_t* erase = nullptr; double* info = nullptr;
@@ -1538,7 +1505,7 @@ static int ba_prepare_navstate(BaSolve& S, const double* kfs, int nk, int n_loca
     VIORB_REQUIRE(kfs && preint && points && edge_idx && edge_obs && gw && cam && kfs_out && points_out && erase && info, "null array");
     VIORB_REQUIRE(n_local >= 1 && n_local <= 20 && nk >= n_local && npts >= 1 && ne >= 1, "1 <= n_local <= 20 key frames, at least one point and edge");
     VIORB_REQUIRE(prev_kf == -1 || (prev_kf >= n_local && prev_kf < nk), "prev_kf must index a fixed key frame or be -1");
-    if (viorb_device_count() < 1) { set_error("no HIP device: libviorb_hip has no CPU fallback"); return VIORB_ERR_NO_DEVICE; }
+    VIORB_TRY(require_device());
     for (int i = 0; i < 6; i++) info[i] = 0;
     for (int i = 0; i < n_local * 22; i++) kfs_out[i] = kfs[i];
     for (int i = 0; i < npts * 3; i++) points_out[i] = points[i];
@@ -1564,7 +1531,7 @@ static int ba_prepare_navstate(BaSolve& S, const double* kfs, int nk, int n_loca
     for (int i = 0; i < n_local; i++) if (!host_inverse9(preint + (size_t)i * 142 + 60, &info_pvr[(size_t)i * 81])) { set_error("singular IMU covariance"); return VIORB_ERR_INVALID_ARG; }
 
     VIORB_HIP_TRY(hipSetDevice(lba_device()));
-    BaCtxLease& lease = S.lease;
+    StreamCtxLease& lease = S.lease;
     if (!lease.ready()) { set_error("could not create a HIP stream"); return VIORB_ERR_HIP; }
     BaBuf B; BaDev& D = S.D;
     D.W = n_local; D.NK = nk; D.NP = npts; D.NE = ne; D.np = 12 * n_local; D.prev_kf = prev_kf; D.acc_bias_rw2 = 5e-3 * 5e-3;
@@ -1610,7 +1577,7 @@ extern "C" int viorb_local_ba_navstate(const double* kfs, int nk, int n_local, i
 // takes the next LM decision and enqueues the next batch of kernels. prepare(i, S) fills window i's solve and returns its status.
 template <class Prepare, class SetStatus>
 static int ba_run_batch(int n, int max_in_flight, Prepare prepare, SetStatus set_status) {
-    if (viorb_device_count() < 1) { set_error("no HIP device: libviorb_hip has no CPU fallback"); return VIORB_ERR_NO_DEVICE; }
+    VIORB_TRY(require_device());
     if (max_in_flight <= 0) max_in_flight = 16;
     VIORB_HIP_TRY(hipSetDevice(lba_device()));
     std::vector<std::unique_ptr<BaSolve>> live(std::min(max_in_flight, std::max(n, 1)));
@@ -1657,7 +1624,7 @@ static int ba_run_batch(int n, int max_in_flight, Prepare prepare, SetStatus set
 // Lock-step batch of NavState windows (kernels k_bab_*): returns the first error; every window's status through set_status.
 template <class Win, class Prepare>
 static int ba_run_lockstep(Win* w, int n, int max_in_flight, Prepare prepare) {
-    if (viorb_device_count() < 1) { set_error("no HIP device: libviorb_hip has no CPU fallback"); return VIORB_ERR_NO_DEVICE; }
+    VIORB_TRY(require_device());
     VIORB_HIP_TRY(hipSetDevice(lba_device()));
     int first_error = VIORB_OK;
     // windows advanced together (max_in_flight of the batch entry points; default 128): every solver step is one launch over the group
@@ -1849,7 +1816,7 @@ static int ba_prepare_se3(BaSolve& S, const double* kfs, int nk, int n_local, co
                           double* points_out, uint8_t* erase, double info[6]) {
     VIORB_REQUIRE(kfs && points && edge_idx && edge_obs && intr5 && kfs_out && points_out && erase && info, "null array");
     VIORB_REQUIRE(n_local >= 1 && n_local <= 40 && nk >= n_local && npts >= 1 && ne >= 1, "1 <= n_local <= 40 key frames, at least one point and edge");
-    if (viorb_device_count() < 1) { set_error("no HIP device: libviorb_hip has no CPU fallback"); return VIORB_ERR_NO_DEVICE; }
+    VIORB_TRY(require_device());
     for (int i = 0; i < 6; i++) info[i] = 0;
     for (int i = 0; i < n_local * 7; i++) kfs_out[i] = kfs[i];
     for (int i = 0; i < npts * 3; i++) points_out[i] = points[i];
@@ -1870,7 +1837,7 @@ static int ba_prepare_se3(BaSolve& S, const double* kfs, int nk, int n_local, co
     { std::vector<int> pos(kf_start.begin(), kf_start.end() - 1); for (int k = 0; k < ne; k++) if (e_kf[k] < n_local) kf_list[pos[e_kf[k]]++] = k; }
     const size_t pr_bound = ba_pairs_bound(e_kf, pt_start, npts, n_local);
     VIORB_HIP_TRY(hipSetDevice(lba_device()));
-    BaCtxLease& lease = S.lease;
+    StreamCtxLease& lease = S.lease;
     if (!lease.ready()) { set_error("could not create a HIP stream"); return VIORB_ERR_HIP; }
     BaBuf B; BaDev& D = S.D;
     D.W = n_local; D.NK = nk; D.NP = npts; D.NE = ne; D.np = 6 * n_local; D.prev_kf = -1; D.acc_bias_rw2 = 0;

@@ -261,37 +261,19 @@ __global__ __launch_bounds__(256) void k_append_new_points(ChainArgs A) {
 using namespace viorb;
 
 namespace {
-struct MapBuf {                                              // host-form helper: device allocations freed on return
-    std::vector<void*> ptrs;
-    ~MapBuf() { for (void* p : ptrs) (void)hipFree(p); }
-    bool ok = true;
-    // n_alloc zeroed elements, the first n_src of them copied from src
-    template <class T> T* up(const T* src, size_t n_src, size_t n_alloc) {
-        T* d = nullptr;
-        n_alloc = std::max<size_t>(std::max(n_alloc, n_src), 1);
-        if (!ok || hipMalloc((void**)&d, n_alloc * sizeof(T)) != hipSuccess) { ok = false; return nullptr; }
-        ptrs.push_back(d);
-        if (hipMemset(d, 0, n_alloc * sizeof(T)) != hipSuccess) ok = false;
-        if (ok && src && n_src && hipMemcpy(d, src, n_src * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) ok = false;
-        return d;
-    }
-};
-bool no_device() {
-    if (viorb_device_count() >= 1) return false;
-    set_error("no HIP device: libviorb_hip has no CPU fallback");
-    return true;
-}
 bool cam_ok(const viorb_mapping_camera* c) { return c && c->nlevels >= 1 && c->nlevels <= 16 && c->fx != 0 && c->fy != 0; }
 
-size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-struct ChainLayout { size_t k2, d2, hp2, ur2, node2, F12, T2, n2, match12, nmatch, accept, reason, Pw, total; };
-ChainLayout chain_layout(int cap, int batch) {
-    ChainLayout L; size_t o = 0; const size_t n = (size_t)cap * batch;
-    auto take = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return at; };
-    L.k2 = take(n * sizeof(viorb_keypoint)); L.d2 = take(n * 32); L.hp2 = take(n); L.ur2 = take(n * 4); L.node2 = take(n * 4);
-    L.F12 = take((size_t)batch * 36); L.T2 = take((size_t)batch * 48); L.n2 = take((size_t)batch * 4); L.match12 = take(n * 4);
-    L.nmatch = take((size_t)batch * 4); L.accept = take(n); L.reason = take(n); L.Pw = take(n * 12);
-    L.total = o;
+// the chain's work arrays in the caller's workspace
+struct ChainLayout {
+    viorb_keypoint* k2; uint8_t *d2, *hp2; float* ur2; int* node2; float *F12, *T2; int *n2, *match12, *nmatch; uint8_t *accept, *reason; float* Pw;
+    size_t total;
+};
+ChainLayout chain_layout(void* base, int cap, int batch) {
+    ChainLayout L; WorkspaceLayout W(base); const size_t n = (size_t)cap * batch;
+    W.take(&L.k2, n); W.take(&L.d2, n * 32); W.take(&L.hp2, n); W.take(&L.ur2, n); W.take(&L.node2, n);
+    W.take(&L.F12, (size_t)batch * 9); W.take(&L.T2, (size_t)batch * 12); W.take(&L.n2, batch); W.take(&L.match12, n);
+    W.take(&L.nmatch, batch); W.take(&L.accept, n); W.take(&L.reason, n); W.take(&L.Pw, n * 3);
+    L.total = W.end();
     return L;
 }
 
@@ -303,9 +285,7 @@ int launch_triangulate(const MapCam& c, const viorb_keypoint* k1, const float* x
     A.c = c; A.k1 = k1; A.k2 = k2; A.xy1 = xy1; A.xy2 = xy2; A.ur1 = ur1; A.ur2 = ur2; A.dep1 = dep1; A.dep2 = dep2; A.T1 = T1; A.T2 = T2;
     A.Ow1 = Ow1; A.Ow2 = Ow2; A.n1 = n1; A.match12 = match12; A.accept = accept; A.reason = reason; A.Pw = Pw;
     A.cap = cap; A.stride2 = stride2; A.off2 = off2;
-    ProfScope ps("k_triangulate_pairs", st);
-    hipLaunchKernelGGL(k_triangulate_pairs, dim3((cap + 255) / 256, batch), dim3(256), 0, st, A);
-    VIORB_HIP_TRY(hipGetLastError());
+    VIORB_LAUNCH(k_triangulate_pairs, dim3((cap + 255) / 256, batch), 256, 0, st, A);
     return VIORB_OK;
 }
 } // namespace
@@ -321,7 +301,7 @@ int viorb_triangulate_pairs_device(const viorb_mapping_camera* cam, const viorb_
     VIORB_REQUIRE(k1 && keys_dist_xy1 && uright1 && depth1 && n1 && pose12_1 && Ow1 && k2 && keys_dist_xy2 && uright2 && depth2 && pose12_2 && Ow2 &&
                   match12 && accept && Pw && reason, "null array");
     VIORB_REQUIRE(cap >= 1 && batch >= 1 && batch <= 65535, "cap >= 1, 1 <= batch <= 65535");
-    if (no_device()) return VIORB_ERR_NO_DEVICE;
+    VIORB_TRY(require_device());
     return launch_triangulate(make_cam(*cam), k1, keys_dist_xy1, uright1, depth1, n1, pose12_1, Ow1, k2, keys_dist_xy2, uright2, depth2, pose12_2,
                               Ow2, 1, 0, match12, cap, batch, accept, Pw, reason, (hipStream_t)stream);
 }
@@ -337,16 +317,16 @@ int viorb_triangulate_pairs(const viorb_mapping_camera* cam, const viorb_keypoin
     VIORB_REQUIRE(k1 && keys_dist_xy1 && uright1 && depth1 && pose12_1 && Ow1 && pose12_2 && Ow2 && match12 && accept && Pw && reason &&
                   (n2 == 0 || (k2 && keys_dist_xy2 && uright2 && depth2)), "null array");
     for (int i = 0; i < n1; i++) VIORB_REQUIRE(match12[i] < n2, "match12[i1] >= n2");
-    if (no_device()) return VIORB_ERR_NO_DEVICE;
+    VIORB_TRY(require_device());
     const size_t cap = (size_t)std::max(n1, std::max(n2, 1));
-    MapBuf B;
+    DeviceBufs B;
     viorb_keypoint* dk1 = B.up(k1, n1, cap); viorb_keypoint* dk2 = B.up(k2, n2, cap);
     float *dx1 = B.up(keys_dist_xy1, 2 * (size_t)n1, 2 * cap), *dx2 = B.up(keys_dist_xy2, 2 * (size_t)n2, 2 * cap);
     float *du1 = B.up(uright1, n1, cap), *du2 = B.up(uright2, n2, cap), *dz1 = B.up(depth1, n1, cap), *dz2 = B.up(depth2, n2, cap);
     float *dT1 = B.up(pose12_1, 12, 12), *dT2 = B.up(pose12_2, 12, 12), *dO1 = B.up(Ow1, 3, 3), *dO2 = B.up(Ow2, 3, 3);
-    float* dP = B.up((const float*)nullptr, 0, 3 * cap);
+    float* dP = B.zeros<float>(3 * cap);
     int *dn1 = B.up(&n1, 1, 1), *dm = B.up(match12, n1, cap);
-    uint8_t *da = B.up((const uint8_t*)nullptr, 0, cap), *dr = B.up((const uint8_t*)nullptr, 0, cap);
+    uint8_t *da = B.zeros<uint8_t>(cap), *dr = B.zeros<uint8_t>(cap);
     if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
     const int rc = viorb_triangulate_pairs_device(cam, dk1, dx1, du1, dz1, dn1, dT1, dO1, dk2, dx2, du2, dz2, dT2, dO2, dm, (int)cap, 1, da, dP, dr, nullptr);
     if (rc != VIORB_OK) return rc;
@@ -366,7 +346,7 @@ int viorb_map_points_update_device(const int32_t* obs_start, const int32_t* obs_
     if (npts == 0) return VIORB_OK;
     VIORB_REQUIRE(obs_start && obs_kf && obs_feat && ref_obs && Pw && kf_row_base && kf_Ow && desc_rows && octave_rows && pts_desc && best_obs && pts_f,
                   "null array");
-    if (no_device()) return VIORB_ERR_NO_DEVICE;
+    VIORB_TRY(require_device());
     MpuArgs A;
     A.obs_start = obs_start; A.obs_kf = obs_kf; A.obs_feat = obs_feat; A.ref_obs = ref_obs; A.Pw = Pw;
     A.kf_row_base = reinterpret_cast<const long long*>(kf_row_base); A.kf_Ow = kf_Ow; A.nkf = nkf; A.desc_rows = desc_rows; A.octave_rows = octave_rows;
@@ -374,9 +354,7 @@ int viorb_map_points_update_device(const int32_t* obs_start, const int32_t* obs_
     const MapCam c = make_cam(*cam);
     for (int i = 0; i < 16; i++) A.sf[i] = c.sf[i];
     A.pts_desc = pts_desc; A.best_obs = best_obs; A.pts_f = pts_f;
-    ProfScope ps("k_map_point_update", (hipStream_t)stream);
-    hipLaunchKernelGGL(k_map_point_update, dim3(npts), dim3(64), 0, (hipStream_t)stream, A);
-    VIORB_HIP_TRY(hipGetLastError());
+    VIORB_LAUNCH(k_map_point_update, npts, 64, 0, (hipStream_t)stream, A);
     return VIORB_OK;
 }
 
@@ -391,14 +369,14 @@ int viorb_map_points_update(const int32_t* obs_start, const int32_t* obs_kf, con
                   "null array");
     VIORB_REQUIRE(obs_start[0] == 0, "obs_start[0] must be 0");
     for (int p = 0; p < npts; p++) VIORB_REQUIRE(obs_start[p + 1] >= obs_start[p], "obs_start must not decrease");
-    if (no_device()) return VIORB_ERR_NO_DEVICE;
+    VIORB_TRY(require_device());
     const size_t ne = (size_t)obs_start[npts];
-    MapBuf B;
-    int *ds = B.up(obs_start, (size_t)npts + 1, 0), *dk = B.up(obs_kf, ne, 0), *df = B.up(obs_feat, ne, 0), *dr = B.up(ref_obs, npts, 0);
-    float *dP = B.up(Pw, 3 * (size_t)npts, 0), *dO = B.up(kf_Ow, 3 * (size_t)nkf, 0), *dpf = B.up((const float*)nullptr, 0, 8 * (size_t)npts);
-    int64_t* db = B.up(kf_row_base, nkf, 0);
-    uint8_t *dd = B.up(desc_rows, 32 * (size_t)pool_rows, 0), *dpd = B.up((const uint8_t*)nullptr, 0, 32 * (size_t)npts);
-    int *doc = B.up(octave_rows, (size_t)pool_rows, 0), *dbo = B.up((const int*)nullptr, 0, npts);
+    DeviceBufs B;
+    int *ds = B.up(obs_start, (size_t)npts + 1), *dk = B.up(obs_kf, ne), *df = B.up(obs_feat, ne), *dr = B.up(ref_obs, npts);
+    float *dP = B.up(Pw, 3 * (size_t)npts), *dO = B.up(kf_Ow, 3 * (size_t)nkf), *dpf = B.zeros<float>(8 * (size_t)npts);
+    int64_t* db = B.up(kf_row_base, nkf);
+    uint8_t *dd = B.up(desc_rows, 32 * (size_t)pool_rows), *dpd = B.zeros<uint8_t>(32 * (size_t)npts);
+    int *doc = B.up(octave_rows, (size_t)pool_rows), *dbo = B.zeros<int>(npts);
     if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
     const int rc = viorb_map_points_update_device(ds, dk, df, dr, dP, npts, db, dO, nkf, dd, doc, pool_rows, cam, dpd, dbo, dpf, nullptr);
     if (rc != VIORB_OK) return rc;
@@ -411,7 +389,7 @@ int viorb_map_points_update(const int32_t* obs_start, const int32_t* obs_kf, con
 
 size_t viorb_create_new_map_points_workspace_bytes(int cap, int batch) {
     if (cap < 1 || batch < 1) return 0;
-    return chain_layout(cap, batch).total;
+    return chain_layout(nullptr, cap, batch).total;
 }
 
 int viorb_create_new_map_points_device(const viorb_mapping_camera* cam, int monocular, const viorb_keypoint* k1, const uint8_t* d1,
@@ -429,38 +407,31 @@ int viorb_create_new_map_points_device(const viorb_mapping_camera* cam, int mono
                   new_desc && n_new && status && workspace, "null array");
     VIORB_REQUIRE(J >= 1 && 0 <= j_begin && j_begin <= j_end && j_end <= J, "0 <= j_begin <= j_end <= J");
     VIORB_REQUIRE(cap >= 1 && cap <= 16384 && batch >= 1 && batch <= 65535 && pcap >= 1, "1 <= cap <= 16384, 1 <= batch <= 65535, pcap >= 1");
-    const ChainLayout L = chain_layout(cap, batch);
+    const ChainLayout L = chain_layout(workspace, cap, batch);
     VIORB_REQUIRE(workspace_bytes >= L.total && ((uintptr_t)workspace & 255) == 0, "workspace smaller than viorb_create_new_map_points_workspace_bytes or not 256-byte aligned");
-    if (no_device()) return VIORB_ERR_NO_DEVICE;
+    VIORB_TRY(require_device());
     hipStream_t st = (hipStream_t)stream;
-    unsigned char* W = static_cast<unsigned char*>(workspace);
     ChainArgs A;
     A.c = make_cam(*cam); A.monocular = monocular;
     A.k1 = k1; A.k2 = k2; A.d1 = d1; A.d2 = d2; A.hp2 = has_point2; A.hp1 = has_point1; A.ur2 = uright2; A.Ow1 = Ow1; A.Ow2 = Ow2; A.T2 = pose12_2;
     A.F12 = F12; A.median_depth2 = median_depth2; A.node2 = node2; A.n2 = n2; A.n_neigh = n_neigh; A.kf2_first = kf2_first;
     A.J = J; A.cap = cap; A.pcap = pcap;
-    A.s_k2 = reinterpret_cast<viorb_keypoint*>(W + L.k2); A.s_d2 = W + L.d2; A.s_hp2 = W + L.hp2; A.s_ur2 = reinterpret_cast<float*>(W + L.ur2);
-    A.s_F12 = reinterpret_cast<float*>(W + L.F12); A.s_T2 = reinterpret_cast<float*>(W + L.T2); A.s_node2 = reinterpret_cast<int*>(W + L.node2);
-    A.s_n2 = reinterpret_cast<int*>(W + L.n2);
-    int* w_match = reinterpret_cast<int*>(W + L.match12); int* w_nmatch = reinterpret_cast<int*>(W + L.nmatch);
-    uint8_t* w_accept = W + L.accept; uint8_t* w_reason = W + L.reason; float* w_Pw = reinterpret_cast<float*>(W + L.Pw);
-    A.match12 = w_match; A.accept = w_accept; A.Pw = w_Pw;
+    A.s_k2 = L.k2; A.s_d2 = L.d2; A.s_hp2 = L.hp2; A.s_ur2 = L.ur2; A.s_F12 = L.F12; A.s_T2 = L.T2; A.s_node2 = L.node2; A.s_n2 = L.n2;
+    A.match12 = L.match12; A.accept = L.accept; A.Pw = L.Pw;
     A.new_idx = new_idx; A.n_new = n_new; A.status = status; A.new_pts_f = new_pts_f; A.new_desc = new_desc;
     const float intr4[4] = {cam->fx, cam->fy, cam->cx, cam->cy};
     for (int j = j_begin; j < j_end; j++) {
         A.j = j;
-        { ProfScope ps("k_stage_neighbour", st); hipLaunchKernelGGL(k_stage_neighbour, dim3(batch), dim3(256), 0, st, A); }
-        VIORB_HIP_TRY(hipGetLastError());
+        VIORB_LAUNCH(k_stage_neighbour, batch, 256, 0, st, A);
         // ORBmatcher matcher(0.6, false); SearchForTriangulation(.., false) (src/LocalMapping.cc:1245, 1296)
         int rc = viorb_search_for_triangulation_device(k1, d1, has_point1, uright1, node1, n1, A.s_k2, A.s_d2, A.s_hp2, A.s_ur2, A.s_node2, A.s_n2, A.s_F12,
-                                                       Ow1, A.s_T2, intr4, cam->scale_factors, cam->level_sigma2, cam->nlevels, 0, 0, cap, batch, w_match,
-                                                       w_nmatch, stream);
+                                                       Ow1, A.s_T2, intr4, cam->scale_factors, cam->level_sigma2, cam->nlevels, 0, 0, cap, batch, L.match12,
+                                                       L.nmatch, stream);
         if (rc != VIORB_OK) return rc;
         rc = launch_triangulate(A.c, k1, keys_dist_xy1, uright1, depth1, n1, pose12_1, Ow1, k2, keys_dist_xy2, uright2, depth2, pose12_2, Ow2, J, j,
-                                w_match, cap, batch, w_accept, w_Pw, w_reason, st);
+                                L.match12, cap, batch, L.accept, L.Pw, L.reason, st);
         if (rc != VIORB_OK) return rc;
-        { ProfScope ps("k_append_new_points", st); hipLaunchKernelGGL(k_append_new_points, dim3(batch), dim3(256), 0, st, A); }
-        VIORB_HIP_TRY(hipGetLastError());
+        VIORB_LAUNCH(k_append_new_points, batch, 256, 0, st, A);
     }
     return VIORB_OK;
 }
@@ -479,22 +450,22 @@ int viorb_create_new_map_points(const viorb_mapping_camera* cam, int monocular, 
     VIORB_REQUIRE(k1 && d1 && has_point1 && uright1 && depth1 && keys_dist_xy1 && node1 && pose12_1 && Ow1 && k2 && d2 && has_point2 && uright2 && depth2 &&
                   keys_dist_xy2 && node2 && n2 && pose12_2 && Ow2 && F12 && median_depth2 && kf2_first && new_idx && new_pts_f && new_desc, "null array");
     for (int j = 0; j < J; j++) VIORB_REQUIRE(n2[j] >= 0 && n2[j] <= cap, "n2[j] out of 0..cap");
-    if (no_device()) return VIORB_ERR_NO_DEVICE;
+    VIORB_TRY(require_device());
     const size_t c = (size_t)cap, jc = (size_t)J * cap;
-    MapBuf B;
-    viorb_keypoint *dk1 = B.up(k1, n1, c), *dk2 = B.up(k2, jc, 0);
-    uint8_t *dd1 = B.up(d1, 32 * (size_t)n1, 32 * c), *dh1 = B.up(has_point1, n1, c), *dd2 = B.up(d2, 32 * jc, 0), *dh2 = B.up(has_point2, jc, 0);
+    DeviceBufs B;
+    viorb_keypoint *dk1 = B.up(k1, n1, c), *dk2 = B.up(k2, jc);
+    uint8_t *dd1 = B.up(d1, 32 * (size_t)n1, 32 * c), *dh1 = B.up(has_point1, n1, c), *dd2 = B.up(d2, 32 * jc), *dh2 = B.up(has_point2, jc);
     float *du1 = B.up(uright1, n1, c), *dz1 = B.up(depth1, n1, c), *dx1 = B.up(keys_dist_xy1, 2 * (size_t)n1, 2 * c);
-    float *du2 = B.up(uright2, jc, 0), *dz2 = B.up(depth2, jc, 0), *dx2 = B.up(keys_dist_xy2, 2 * jc, 0);
-    int *dnode1 = B.up(node1, n1, c), *dnode2 = B.up(node2, jc, 0), *dn1 = B.up(&n1, 1, 1), *dn2 = B.up(n2, J, 0), *dnn = B.up(&J, 1, 1);
-    float *dT1 = B.up(pose12_1, 12, 0), *dO1 = B.up(Ow1, 3, 0), *dT2 = B.up(pose12_2, 12 * (size_t)J, 0), *dO2 = B.up(Ow2, 3 * (size_t)J, 0);
-    float *dF = B.up(F12, 9 * (size_t)J, 0), *dmd = B.up(median_depth2, J, 0);
-    uint8_t* dkf = B.up(kf2_first, J, 0);
-    int *didx = B.up((const int*)nullptr, 0, 3 * (size_t)pcap), *dnew = B.up((const int*)nullptr, 0, 1), *dst = B.up((const int*)nullptr, 0, 1);
-    float* dpf = B.up((const float*)nullptr, 0, 8 * (size_t)pcap);
-    uint8_t* dpd = B.up((const uint8_t*)nullptr, 0, 32 * (size_t)pcap);
+    float *du2 = B.up(uright2, jc), *dz2 = B.up(depth2, jc), *dx2 = B.up(keys_dist_xy2, 2 * jc);
+    int *dnode1 = B.up(node1, n1, c), *dnode2 = B.up(node2, jc), *dn1 = B.up(&n1, 1, 1), *dn2 = B.up(n2, J), *dnn = B.up(&J, 1, 1);
+    float *dT1 = B.up(pose12_1, 12), *dO1 = B.up(Ow1, 3), *dT2 = B.up(pose12_2, 12 * (size_t)J), *dO2 = B.up(Ow2, 3 * (size_t)J);
+    float *dF = B.up(F12, 9 * (size_t)J), *dmd = B.up(median_depth2, J);
+    uint8_t* dkf = B.up(kf2_first, J);
+    int *didx = B.zeros<int>(3 * (size_t)pcap), *dnew = B.zeros<int>(1), *dst = B.zeros<int>(1);
+    float* dpf = B.zeros<float>(8 * (size_t)pcap);
+    uint8_t* dpd = B.zeros<uint8_t>(32 * (size_t)pcap);
     const size_t wb = viorb_create_new_map_points_workspace_bytes(cap, 1);
-    unsigned char* dw = B.up((const unsigned char*)nullptr, 0, wb);
+    unsigned char* dw = B.zeros<unsigned char>(wb);
     if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
     const int rc = viorb_create_new_map_points_device(cam, monocular, dk1, dd1, dh1, du1, dz1, dx1, dnode1, dn1, dT1, dO1, dk2, dd2, dh2, du2, dz2, dx2, dnode2,
                                                       dn2, dT2, dO2, dF, dmd, dkf, dnn, J, 0, J, cap, 1, pcap, didx, dpf, dpd, dnew, dst, dw, wb, nullptr);

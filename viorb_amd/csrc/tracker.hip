@@ -111,21 +111,6 @@ __global__ void k_track_merge_status(const int* __restrict__ a, const int* __res
     out[b] = s;
 }
 
-struct DevArena {
-    std::vector<void*> ptrs;
-    hipError_t err = hipSuccess;
-    template <class T> T* get(size_t n) {
-        void* p = nullptr;
-        if (err != hipSuccess) return nullptr;
-        err = hipMalloc(&p, sizeof(T) * (n ? n : 1));
-        if (err != hipSuccess) return nullptr;
-        (void)hipMemset(p, 0, sizeof(T) * (n ? n : 1));
-        ptrs.push_back(p);
-        return (T*)p;
-    }
-    void release() { for (void* p : ptrs) (void)hipFree(p); ptrs.clear(); }
-};
-
 } // namespace viorb
 
 using namespace viorb;
@@ -141,7 +126,7 @@ struct viorb_tracker {
     std::deque<hipEvent_t> in_flight; std::vector<hipEvent_t> ev_pool;
     long long k = 0, rolls = 0;
     int cur_slot = 0;
-    DevArena mem;
+    DeviceBufs mem;
     // last frame
     viorb_keypoint* last_kps; uint8_t* last_desc; int* last_count; uint8_t* last_flags; float* last_Pw; float* last_pts_f; int* last_self;
     double *last_ns, *prior_ns, *marg_cov_inv, *t_last;
@@ -159,19 +144,18 @@ struct viorb_tracker {
     double enqueue_s = 0, throttle_s = 0; long long steps = 0;
 };
 
-#define TR_TRY(x) do { int _rc = (x); if (_rc != VIORB_OK) return _rc; } while (0)
 
 static int tracker_roll(viorb_tracker* h, const viorb_keypoint* kps, const uint8_t* desc, const int* count, const double* ns_src, const double* t_src,
                         const double* marg_src, const double* synth_pose12, hipStream_t st) {
     const bool tlm = h->cfg.track_local_map > 0;
-    TR_TRY(viorb_frontend_roll_device(h->fe, kps, desc, count, h->last_kps, h->last_desc, h->last_count, tlm ? h->last_pts_f : nullptr, h->last_flags,
+    VIORB_TRY(viorb_frontend_roll_device(h->fe, kps, desc, count, h->last_kps, h->last_desc, h->last_count, tlm ? h->last_pts_f : nullptr, h->last_flags,
                                       tlm ? h->loc_pts_f : nullptr, tlm ? h->loc_desc : nullptr, tlm ? h->loc_flags : nullptr, h->cfg.local_frames,
                                       (tlm && h->rolls > 0) ? 1 : 0, ns_src, h->last_ns, h->prior_ns, t_src, h->t_last, marg_src,
                                       marg_src ? h->marg_cov_inv : nullptr, h->B, st));
     if (synth_pose12) {
-        TR_TRY(viorb_synth_plane_points_device(h->fe, h->last_kps, h->last_count, synth_pose12, h->cfg.synth_plane_z0, h->B, h->last_Pw, h->last_flags,
+        VIORB_TRY(viorb_synth_plane_points_device(h->fe, h->last_kps, h->last_count, synth_pose12, h->cfg.synth_plane_z0, h->B, h->last_Pw, h->last_flags,
                                                h->last_self, st));
-        if (tlm) TR_TRY(viorb_synth_local_points_device(h->fe, h->last_kps, h->last_count, synth_pose12, h->last_Pw, h->B, h->last_pts_f, st));
+        if (tlm) VIORB_TRY(viorb_synth_local_points_device(h->fe, h->last_kps, h->last_count, synth_pose12, h->last_Pw, h->B, h->last_pts_f, st));
     }
     h->rolls++;
     return VIORB_OK;
@@ -183,26 +167,26 @@ int viorb_tracker_create(const viorb_tracker_config* cfg, viorb_tracker** out) {
     VIORB_REQUIRE(cfg && out, "null cfg/out");
     VIORB_REQUIRE(cfg->batch >= 1 && cfg->width > 0 && cfg->height > 0, "batch >= 1, width, height > 0");
     VIORB_REQUIRE(cfg->track_local_map <= 0 || (cfg->local_frames >= 1 && cfg->local_frames <= 8), "1 <= local_frames <= 8");
-    if (viorb_device_count() < 1) { set_error("no HIP device: libviorb_hip has no CPU fallback"); return VIORB_ERR_NO_DEVICE; }
+    VIORB_TRY(require_device());
     VIORB_HIP_TRY(hipSetDevice(cfg->device));
     viorb_tracker* h = new viorb_tracker();
     struct Guard { viorb_tracker* h; ~Guard() { if (h) viorb_tracker_destroy(h); } } guard{h};
     h->cfg = *cfg; h->B = cfg->batch; h->device = cfg->device; h->nlevels = cfg->extractor.nlevels;
-    for (int i = 0; i < 2; i++) TR_TRY(viorb_extractor_create(&cfg->extractor, cfg->batch, cfg->device, &h->ex[i]));
-    TR_TRY(viorb_extractor_max_keypoints_for(h->ex[0], cfg->width, cfg->height, &h->cap));      // the pitch of the extractor's results for this image size
+    for (int i = 0; i < 2; i++) VIORB_TRY(viorb_extractor_create(&cfg->extractor, cfg->batch, cfg->device, &h->ex[i]));
+    VIORB_TRY(viorb_extractor_max_keypoints_for(h->ex[0], cfg->width, cfg->height, &h->cap));      // the pitch of the extractor's results for this image size
     viorb_frontend_config fc = cfg->frontend;
     float sf[16], is2[16];
-    TR_TRY(viorb_extractor_tables(h->ex[0], sf, nullptr, nullptr, is2, nullptr));
+    VIORB_TRY(viorb_extractor_tables(h->ex[0], sf, nullptr, nullptr, is2, nullptr));
     for (int i = 0; i < 16; i++) { fc.scale_factors[i] = sf[i < h->nlevels ? i : h->nlevels - 1]; fc.inv_level_sigma2[i] = is2[i < h->nlevels ? i : h->nlevels - 1]; }
     fc.nlevels = h->nlevels;
     {   // Frame::ComputeImageBounds (src/Frame.cc:616-644): the four undistorted corners when the camera is distorted
         const float intr4[4] = {fc.fx, fc.fy, fc.cx, fc.cy};
         float b4[4];
-        TR_TRY(viorb_image_bounds(cfg->width, cfg->height, intr4, fc.dist_coef, b4));
+        VIORB_TRY(viorb_image_bounds(cfg->width, cfg->height, intr4, fc.dist_coef, b4));
         fc.min_x = b4[0]; fc.max_x = b4[1]; fc.min_y = b4[2]; fc.max_y = b4[3];
     }
     h->undistort = fc.dist_coef[0] != 0.0f;
-    TR_TRY(viorb_frontend_create(&fc, cfg->batch, h->cap, cfg->device, &h->fe));
+    VIORB_TRY(viorb_frontend_create(&fc, cfg->batch, h->cap, cfg->device, &h->fe));
     {
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);                  // hi = numerically lowest = highest priority
@@ -215,25 +199,25 @@ int viorb_tracker_create(const viorb_tracker_config* cfg, viorb_tracker** out) {
     VIORB_HIP_TRY(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
     for (int i = 0; i < 2; i++) { VIORB_HIP_TRY(hipEventCreateWithFlags(&h->ev_ex[i], hipEventDisableTiming)); VIORB_HIP_TRY(hipEventCreateWithFlags(&h->ev_tr[i], hipEventDisableTiming)); }
     const size_t B = (size_t)h->B, cap = (size_t)h->cap, R = (size_t)(cfg->track_local_map > 0 ? cfg->local_frames : 1);
-    DevArena& M = h->mem;
-    h->last_kps = M.get<viorb_keypoint>(B * cap); h->last_desc = M.get<uint8_t>(B * cap * 32); h->last_count = M.get<int>(B);
-    h->last_flags = M.get<uint8_t>(B * cap); h->last_Pw = M.get<float>(B * cap * 3); h->last_pts_f = M.get<float>(B * cap * 8); h->last_self = M.get<int>(B * cap);
-    h->last_ns = M.get<double>(B * 22); h->prior_ns = M.get<double>(B * 22); h->marg_cov_inv = M.get<double>(B * 144); h->t_last = M.get<double>(B);
-    h->loc_pts_f = M.get<float>(B * R * cap * 8); h->loc_flags = M.get<uint8_t>(B * R * cap); h->loc_desc = M.get<uint8_t>(B * R * cap * 32); h->loc_count = M.get<int>(B);
-    h->cell_start = M.get<int>(B * (64 * 48 + 1)); h->cell_idx = M.get<int>(B * cap); h->preint = M.get<double>(B * 142); h->cur_ns = M.get<double>(B * 22);
-    h->pose12 = M.get<float>(B * 12); h->pose12_b = M.get<float>(B * 12); h->cur_match = M.get<int>(B * cap); h->nmatches = M.get<int>(B);
-    h->status_s1 = M.get<int>(B); h->status_s2 = M.get<int>(B); h->status = M.get<int>(B);
-    h->obs_cur = M.get<double>(B * cap * 6); h->obs_last = M.get<double>(B * cap * 6); h->obs_cur2 = M.get<double>(B * cap * 6);
-    h->idx_cur = M.get<int>(B * cap); h->idx_last = M.get<int>(B * cap); h->idx_cur2 = M.get<int>(B * cap);
-    h->n_cur = M.get<int>(B); h->n_last = M.get<int>(B); h->n_cur2 = M.get<int>(B);
-    h->out_ns = M.get<double>(B * 22); h->out_last_ns = M.get<double>(B * 22); h->out_ns2 = M.get<double>(B * 22); h->ns1 = M.get<double>(B * 22);
-    h->final_ns = M.get<double>(B * 22); h->final_marg = M.get<double>(B * 144); h->marg_out = M.get<double>(B * 144);
-    h->info = M.get<double>(B * 4); h->info2 = M.get<double>(B * 4);
-    h->outlier_cur = M.get<uint8_t>(B * cap); h->outlier_last = M.get<uint8_t>(B * cap); h->outlier_cur2 = M.get<uint8_t>(B * cap); h->owner_obs = M.get<uint8_t>(B * cap);
-    h->skip1 = M.get<uint8_t>(B); h->skip2 = M.get<uint8_t>(B); h->variant = M.get<uint8_t>(B);
-    if (h->undistort) h->kps_un = M.get<viorb_keypoint>(B * cap);
-    h->n_map = M.get<int>(B); h->loc_match = M.get<int>(B * cap); h->n_loc = M.get<int>(B); h->state = M.get<int>(B); h->inliers = M.get<int>(B);
-    if (M.err != hipSuccess) { set_error("device allocation failed: %s", hipGetErrorString(M.err)); return VIORB_ERR_HIP; }
+    DeviceBufs& M = h->mem;
+    h->last_kps = M.zeros<viorb_keypoint>(B * cap); h->last_desc = M.zeros<uint8_t>(B * cap * 32); h->last_count = M.zeros<int>(B);
+    h->last_flags = M.zeros<uint8_t>(B * cap); h->last_Pw = M.zeros<float>(B * cap * 3); h->last_pts_f = M.zeros<float>(B * cap * 8); h->last_self = M.zeros<int>(B * cap);
+    h->last_ns = M.zeros<double>(B * 22); h->prior_ns = M.zeros<double>(B * 22); h->marg_cov_inv = M.zeros<double>(B * 144); h->t_last = M.zeros<double>(B);
+    h->loc_pts_f = M.zeros<float>(B * R * cap * 8); h->loc_flags = M.zeros<uint8_t>(B * R * cap); h->loc_desc = M.zeros<uint8_t>(B * R * cap * 32); h->loc_count = M.zeros<int>(B);
+    h->cell_start = M.zeros<int>(B * (64 * 48 + 1)); h->cell_idx = M.zeros<int>(B * cap); h->preint = M.zeros<double>(B * 142); h->cur_ns = M.zeros<double>(B * 22);
+    h->pose12 = M.zeros<float>(B * 12); h->pose12_b = M.zeros<float>(B * 12); h->cur_match = M.zeros<int>(B * cap); h->nmatches = M.zeros<int>(B);
+    h->status_s1 = M.zeros<int>(B); h->status_s2 = M.zeros<int>(B); h->status = M.zeros<int>(B);
+    h->obs_cur = M.zeros<double>(B * cap * 6); h->obs_last = M.zeros<double>(B * cap * 6); h->obs_cur2 = M.zeros<double>(B * cap * 6);
+    h->idx_cur = M.zeros<int>(B * cap); h->idx_last = M.zeros<int>(B * cap); h->idx_cur2 = M.zeros<int>(B * cap);
+    h->n_cur = M.zeros<int>(B); h->n_last = M.zeros<int>(B); h->n_cur2 = M.zeros<int>(B);
+    h->out_ns = M.zeros<double>(B * 22); h->out_last_ns = M.zeros<double>(B * 22); h->out_ns2 = M.zeros<double>(B * 22); h->ns1 = M.zeros<double>(B * 22);
+    h->final_ns = M.zeros<double>(B * 22); h->final_marg = M.zeros<double>(B * 144); h->marg_out = M.zeros<double>(B * 144);
+    h->info = M.zeros<double>(B * 4); h->info2 = M.zeros<double>(B * 4);
+    h->outlier_cur = M.zeros<uint8_t>(B * cap); h->outlier_last = M.zeros<uint8_t>(B * cap); h->outlier_cur2 = M.zeros<uint8_t>(B * cap); h->owner_obs = M.zeros<uint8_t>(B * cap);
+    h->skip1 = M.zeros<uint8_t>(B); h->skip2 = M.zeros<uint8_t>(B); h->variant = M.zeros<uint8_t>(B);
+    if (h->undistort) h->kps_un = M.zeros<viorb_keypoint>(B * cap);
+    h->n_map = M.zeros<int>(B); h->loc_match = M.zeros<int>(B * cap); h->n_loc = M.zeros<int>(B); h->state = M.zeros<int>(B); h->inliers = M.zeros<int>(B);
+    if (!M.ok) { set_error("device allocation failed: %s", hipGetErrorString(hipGetLastError())); return VIORB_ERR_HIP; }
     {
         std::vector<int> lc(B, (int)(R * cap));
         VIORB_HIP_TRY(hipMemcpy(h->loc_count, lc.data(), sizeof(int) * B, hipMemcpyHostToDevice));
@@ -279,12 +263,12 @@ int viorb_tracker_bootstrap(viorb_tracker* h, const uint8_t* d_images, int strid
     VIORB_HIP_TRY(hipStreamSynchronize((hipStream_t)caller_stream));
     VIORB_HIP_TRY(hipStreamSynchronize(h->s_ex)); if (h->s_ex2) VIORB_HIP_TRY(hipStreamSynchronize(h->s_ex2)); VIORB_HIP_TRY(hipStreamSynchronize(h->s_tr));
     h->rolls = 0; h->k = 0; h->ev_tr_valid[0] = h->ev_tr_valid[1] = false; h->cur_slot = 0;
-    TR_TRY(viorb_extract_batch_device(h->ex[0], d_images, h->B, h->cfg.width, h->cfg.height, stride, image_pitch_bytes, h->s_tr));
+    VIORB_TRY(viorb_extract_batch_device(h->ex[0], d_images, h->B, h->cfg.width, h->cfg.height, stride, image_pitch_bytes, h->s_tr));
     const viorb_keypoint* kps; const uint8_t* desc; const int32_t* count; const int32_t* st; int cap;
-    TR_TRY(viorb_extractor_results_device(h->ex[0], &kps, &desc, &count, &st, &cap));
-    if (h->undistort) { TR_TRY(viorb_frontend_undistort_device(h->fe, kps, count, h->B, h->kps_un, h->s_tr)); kps = h->kps_un; }
+    VIORB_TRY(viorb_extractor_results_device(h->ex[0], &kps, &desc, &count, &st, &cap));
+    if (h->undistort) { VIORB_TRY(viorb_frontend_undistort_device(h->fe, kps, count, h->B, h->kps_un, h->s_tr)); kps = h->kps_un; }
     VIORB_HIP_TRY(hipMemcpyAsync(h->marg_cov_inv, d_marg_cov_inv, sizeof(double) * 144 * h->B, hipMemcpyDeviceToDevice, h->s_tr));
-    TR_TRY(tracker_roll(h, kps, desc, count, d_ns0, d_t0, nullptr, d_synth_pose12, h->s_tr));
+    VIORB_TRY(tracker_roll(h, kps, desc, count, d_ns0, d_t0, nullptr, d_synth_pose12, h->s_tr));
     VIORB_HIP_TRY(hipStreamSynchronize(h->s_tr));
     return VIORB_OK;
 }
@@ -342,26 +326,26 @@ int viorb_tracker_step(viorb_tracker* h, const viorb_tracker_inputs* in, void* c
     VIORB_HIP_TRY(hipStreamWaitEvent(h->s_tr, h->ev_in, 0));
     if (h->ev_tr_valid[slot]) VIORB_HIP_TRY(hipStreamWaitEvent(sx, h->ev_tr[slot], 0));     // this handle's previous results have been consumed
     if (ev_upload) VIORB_HIP_TRY(hipStreamWaitEvent(sx, ev_upload, 0));
-    TR_TRY(viorb_extract_batch_device(ex, d_images, B, h->cfg.width, h->cfg.height, in->image_stride, in->image_pitch_bytes, sx));
+    VIORB_TRY(viorb_extract_batch_device(ex, d_images, B, h->cfg.width, h->cfg.height, in->image_stride, in->image_pitch_bytes, sx));
     VIORB_HIP_TRY(hipEventRecord(h->ev_ex[slot], sx));
     hipStream_t st = h->s_tr;
     // ---- what does not need the new frame's keypoints: IMU pre-integration + prediction, the last frame's own observations
-    TR_TRY(viorb_frontend_imu_predict_device(h->fe, in->d_imu, in->n_imu, h->t_last, in->d_t_cur, h->last_ns, B, h->preint, h->cur_ns, h->pose12, st));
-    TR_TRY(viorb_frontend_build_observations_device(h->fe, h->last_kps, h->last_count, h->last_self, h->last_Pw, B, h->obs_last, h->idx_last, h->n_last, st));
+    VIORB_TRY(viorb_frontend_imu_predict_device(h->fe, in->d_imu, in->n_imu, h->t_last, in->d_t_cur, h->last_ns, B, h->preint, h->cur_ns, h->pose12, st));
+    VIORB_TRY(viorb_frontend_build_observations_device(h->fe, h->last_kps, h->last_count, h->last_self, h->last_Pw, B, h->obs_last, h->idx_last, h->n_last, st));
     VIORB_HIP_TRY(hipStreamWaitEvent(st, h->ev_ex[slot], 0));
     const viorb_keypoint* kps; const uint8_t* desc; const int32_t* count; const int32_t* ex_status; int cap;
-    TR_TRY(viorb_extractor_results_device(ex, &kps, &desc, &count, &ex_status, &cap));
+    VIORB_TRY(viorb_extractor_results_device(ex, &kps, &desc, &count, &ex_status, &cap));
     h->cur_slot = slot;
     // Frame::UndistortKeyPoints (Frame.cc:171): grid, searches, edges and the frame handed on all read mvKeysUn
-    if (h->undistort) { TR_TRY(viorb_frontend_undistort_device(h->fe, kps, count, B, h->kps_un, st)); kps = h->kps_un; }
+    if (h->undistort) { VIORB_TRY(viorb_frontend_undistort_device(h->fe, kps, count, B, h->kps_un, st)); kps = h->kps_un; }
     // ---- TrackWithIMU
-    TR_TRY(viorb_frontend_grid_device(h->fe, kps, count, B, h->cell_start, h->cell_idx, st));
-    TR_TRY(viorb_frontend_search_projection_device(h->fe, kps, desc, count, h->cell_start, h->cell_idx, h->pose12, h->last_kps, h->last_count, h->last_flags,
+    VIORB_TRY(viorb_frontend_grid_device(h->fe, kps, count, B, h->cell_start, h->cell_idx, st));
+    VIORB_TRY(viorb_frontend_search_projection_device(h->fe, kps, desc, count, h->cell_start, h->cell_idx, h->pose12, h->last_kps, h->last_count, h->last_flags,
                                                    h->last_Pw, h->last_desc, h->cfg.th_projection, B, h->cur_match, h->nmatches, h->status_s1, st));
-    TR_TRY(viorb_frontend_search_projection_retry_device(h->fe, kps, desc, count, h->cell_start, h->cell_idx, h->pose12, h->last_kps, h->last_count,
+    VIORB_TRY(viorb_frontend_search_projection_retry_device(h->fe, kps, desc, count, h->cell_start, h->cell_idx, h->pose12, h->last_kps, h->last_count,
                                                          h->last_flags, h->last_Pw, h->last_desc, 2 * h->cfg.th_projection, 20, B, h->cur_match, h->nmatches,
                                                          h->status_s1, st));
-    TR_TRY(viorb_frontend_build_observations_device(h->fe, kps, count, h->cur_match, h->last_Pw, B, h->obs_cur, h->idx_cur, h->n_cur, st));
+    VIORB_TRY(viorb_frontend_build_observations_device(h->fe, kps, count, h->cur_match, h->last_Pw, B, h->obs_cur, h->idx_cur, h->n_cur, st));
     if (match_only) {
         // "ORB extract + match" (BASELINE north_star's single-stream figure): no pose solve; state = VIORB_TRACK_OK, the NavState handed on is the
         // IMU prediction (what Tracking does while vision is lost, src/Tracking.cc:1036-1114), the prior information stays
@@ -369,24 +353,24 @@ int viorb_tracker_step(viorb_tracker* h, const viorb_tracker_inputs* in, void* c
         VIORB_HIP_TRY(hipMemcpyAsync(h->final_ns, h->cur_ns, sizeof(double) * 22 * B, hipMemcpyDeviceToDevice, st));
         hipLaunchKernelGGL(k_track_merge_status, dim3((B + 255) / 256), dim3(256), 0, st, ex_status, h->status_s1, (const int32_t*)nullptr, B, h->status);
         VIORB_HIP_TRY(hipGetLastError());
-        TR_TRY(tracker_roll(h, kps, desc, count, in->d_reset_ns ? in->d_reset_ns : h->final_ns, in->d_t_next_last ? in->d_t_next_last : in->d_t_cur, nullptr,
+        VIORB_TRY(tracker_roll(h, kps, desc, count, in->d_reset_ns ? in->d_reset_ns : h->final_ns, in->d_t_next_last ? in->d_t_next_last : in->d_t_cur, nullptr,
                             in->d_synth_pose12, st));
     } else {
     hipLaunchKernelGGL(k_track_gate0, dim3((B + 255) / 256), dim3(256), 0, st, h->nmatches, B, h->skip1, in->d_map_updated, h->variant);
-    TR_TRY(viorb_frontend_pose_opt_select_device(h->fe, h->variant, h->skip1, marg && !tlm, h->cur_ns, h->last_ns, h->prior_ns, h->marg_cov_inv, h->preint,
+    VIORB_TRY(viorb_frontend_pose_opt_select_device(h->fe, h->variant, h->skip1, marg && !tlm, h->cur_ns, h->last_ns, h->prior_ns, h->marg_cov_inv, h->preint,
                                                  h->obs_cur, h->n_cur, h->obs_last, h->n_last, B, h->out_ns, h->out_last_ns, h->outlier_cur,
                                                  h->outlier_last, h->marg_out, h->info, st));
-    TR_TRY(viorb_frontend_discard_outliers_device(h->fe, h->cur_match, h->idx_cur, h->outlier_cur, h->n_cur, h->last_flags, B, h->owner_obs, h->n_map, st));
+    VIORB_TRY(viorb_frontend_discard_outliers_device(h->fe, h->cur_match, h->idx_cur, h->outlier_cur, h->n_cur, h->last_flags, B, h->owner_obs, h->n_map, st));
     hipLaunchKernelGGL(k_track_gate1, dim3(B), dim3(64), 0, st, h->nmatches, h->n_map, h->cur_ns, h->out_ns, B, h->state, h->ns1, h->skip2);
     if (tlm) {
         // ---- TrackLocalMapWithIMU
-        TR_TRY(viorb_frontend_pose_from_navstate_device(h->fe, h->ns1, B, h->pose12_b, st));
-        TR_TRY(viorb_frontend_search_local_points_device(h->fe, kps, desc, count, h->cell_start, h->cell_idx, h->pose12_b, h->loc_pts_f, h->loc_flags, h->loc_desc,
+        VIORB_TRY(viorb_frontend_pose_from_navstate_device(h->fe, h->ns1, B, h->pose12_b, st));
+        VIORB_TRY(viorb_frontend_search_local_points_device(h->fe, kps, desc, count, h->cell_start, h->cell_idx, h->pose12_b, h->loc_pts_f, h->loc_flags, h->loc_desc,
                                                          h->loc_count, h->cfg.local_frames * h->cap, 1.0f, 0.8f, h->owner_obs, B, h->loc_match, h->n_loc, nullptr,
                                                          h->status_s2, st));
-        TR_TRY(viorb_frontend_build_observations2_device(h->fe, kps, count, h->cur_match, h->last_Pw, h->loc_match, h->loc_pts_f, h->cfg.local_frames * h->cap, B,
+        VIORB_TRY(viorb_frontend_build_observations2_device(h->fe, kps, count, h->cur_match, h->last_Pw, h->loc_match, h->loc_pts_f, h->cfg.local_frames * h->cap, B,
                                                          h->obs_cur2, h->idx_cur2, h->n_cur2, st));
-        TR_TRY(viorb_frontend_pose_opt_select_device(h->fe, h->variant, h->skip2, marg, h->ns1, h->last_ns, h->prior_ns, h->marg_cov_inv, h->preint, h->obs_cur2,
+        VIORB_TRY(viorb_frontend_pose_opt_select_device(h->fe, h->variant, h->skip2, marg, h->ns1, h->last_ns, h->prior_ns, h->marg_cov_inv, h->preint, h->obs_cur2,
                                                      h->n_cur2, h->obs_last, h->n_last, B, h->out_ns2, h->out_last_ns, h->outlier_cur2, h->outlier_last,
                                                      h->marg_out, h->info2, st));
         hipLaunchKernelGGL(k_track_count_inliers, dim3(B), dim3(256), 0, st, h->outlier_cur2, h->idx_cur2, h->n_cur2, h->cur_match, h->last_flags, h->loc_match,
@@ -397,7 +381,7 @@ int viorb_tracker_step(viorb_tracker* h, const viorb_tracker_inputs* in, void* c
     hipLaunchKernelGGL(k_track_merge_status, dim3((B + 255) / 256), dim3(256), 0, st, ex_status, h->status_s1, tlm ? h->status_s2 : nullptr, B, h->status);
     VIORB_HIP_TRY(hipGetLastError());
     // ---- mLastFrame = Frame(mCurrentFrame)
-    TR_TRY(tracker_roll(h, kps, desc, count, h->final_ns, in->d_t_next_last ? in->d_t_next_last : in->d_t_cur, h->final_marg, in->d_synth_pose12, st));
+    VIORB_TRY(tracker_roll(h, kps, desc, count, h->final_ns, in->d_t_next_last ? in->d_t_next_last : in->d_t_cur, h->final_marg, in->d_synth_pose12, st));
     }
     VIORB_HIP_TRY(hipEventRecord(h->ev_tr[slot], st));
     h->ev_tr_valid[slot] = true;

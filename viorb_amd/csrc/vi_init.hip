@@ -299,25 +299,6 @@ __global__ __launch_bounds__(256) void k_scale_map_points(float* points, float* 
 using namespace viorb;
 
 namespace {
-struct ViBuf {                                               // host-form helper: device allocations freed on return
-    std::vector<void*> ptrs;
-    ~ViBuf() { for (void* p : ptrs) (void)hipFree(p); }
-    bool ok = true;
-    template <class T> T* up(const T* src, size_t n_src, size_t n_alloc) {
-        T* d = nullptr;
-        n_alloc = std::max<size_t>(std::max(n_alloc, n_src), 1);
-        if (!ok || hipMalloc((void**)&d, n_alloc * sizeof(T)) != hipSuccess) { ok = false; return nullptr; }
-        ptrs.push_back(d);
-        if (hipMemset(d, 0, n_alloc * sizeof(T)) != hipSuccess) ok = false;
-        if (ok && src && n_src && hipMemcpy(d, src, n_src * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) ok = false;
-        return d;
-    }
-};
-bool vi_no_device() {
-    if (viorb_device_count() >= 1) return false;
-    set_error("no HIP device: libviorb_hip has no CPU fallback");
-    return true;
-}
 double gyr_or_default(double v) { return v > 0 ? v : 2.0e-3 * 2.0e-3 * 200; }           // reference src/IMU/imudata.cpp:36-37
 double acc_or_default(double v) { return v > 0 ? v : 8.0e-3 * 8.0e-3 * 200; }
 
@@ -330,9 +311,7 @@ int launch_preint(const int32_t* n_kf, const double* kf_time, const int32_t* imu
     A.ba_stride = ba_stride; A.gyr_cov = gyr_or_default(gyr); A.acc_cov = acc_or_default(acc); A.clamp = (flags & VIORB_PREINT_NO_CLAMP) ? 0 : 1;
     A.max_kf = max_kf; A.batch = batch; A.preint = preint;
     const long long waves = (long long)batch * max_kf;
-    ProfScope ps("k_preint_intervals", st);
-    hipLaunchKernelGGL(k_preint_intervals, dim3((unsigned)((waves + PI_WAVES - 1) / PI_WAVES)), dim3(64 * PI_WAVES), 0, st, A);
-    VIORB_HIP_TRY(hipGetLastError());
+    VIORB_LAUNCH(k_preint_intervals, (unsigned)((waves + PI_WAVES - 1) / PI_WAVES), 64 * PI_WAVES, 0, st, A);
     return VIORB_OK;
 }
 ViArgs vi_args(const viorb_vi_init_config* cfg, const int32_t* n_est, const float* twc12, const double* preint, int max_kf, int min_n, double* bg,
@@ -353,7 +332,7 @@ int viorb_preintegrate_intervals_device(const int32_t* n_kf, const double* kf_ti
     VIORB_REQUIRE(n_kf && kf_time && imu_start && preint && (imu || total_imu == 0), "null array");
     VIORB_REQUIRE(shape_ok(max_kf, batch) && total_imu >= 0, "1 <= max_kf <= 4096, 1 <= batch <= 2^20, total_imu >= 0");
     VIORB_REQUIRE((flags & ~VIORB_PREINT_NO_CLAMP) == 0, "unknown flag");
-    if (vi_no_device()) return VIORB_ERR_NO_DEVICE;
+    VIORB_TRY(require_device());
     return launch_preint(n_kf, kf_time, imu_start, imu, total_imu, bg, 3, ba, 3, gyr_meas_cov, acc_meas_cov, flags, max_kf, batch, preint, (hipStream_t)stream);
 }
 
@@ -362,11 +341,11 @@ int viorb_preintegrate_intervals(int n_kf, const double* kf_time, const int32_t*
     VIORB_REQUIRE(n_kf >= 1 && n_kf <= 4096 && kf_time && imu_start && preint, "1 <= n_kf <= 4096, arrays not null");
     const int32_t total = imu_start[n_kf];
     VIORB_REQUIRE(total >= 0 && (imu || total == 0), "imu_start[n_kf] = number of samples");
-    if (vi_no_device()) return VIORB_ERR_NO_DEVICE;
-    ViBuf B;
-    int32_t* dn = B.up(&n_kf, 1, 1); double* dt = B.up(kf_time, n_kf, n_kf); int32_t* ds = B.up(imu_start, (size_t)n_kf + 1, 0);
-    double* di = B.up(imu, (size_t)total * 7, 0); double* dbg = bg ? B.up(bg, 3, 3) : nullptr; double* dba = ba ? B.up(ba, 3, 3) : nullptr;
-    double* dp = B.up((const double*)nullptr, 0, (size_t)n_kf * 142);
+    VIORB_TRY(require_device());
+    DeviceBufs B;
+    int32_t* dn = B.up(&n_kf, 1, 1); double* dt = B.up(kf_time, n_kf, n_kf); int32_t* ds = B.up(imu_start, (size_t)n_kf + 1);
+    double* di = B.up(imu, (size_t)total * 7); double* dbg = bg ? B.up(bg, 3, 3) : nullptr; double* dba = ba ? B.up(ba, 3, 3) : nullptr;
+    double* dp = B.zeros<double>((size_t)n_kf * 142);
     if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
     const int rc = viorb_preintegrate_intervals_device(dn, dt, ds, di, total, dbg, dba, gyr_meas_cov, acc_meas_cov, flags, n_kf, 1, dp, nullptr);
     if (rc != VIORB_OK) return rc;
@@ -379,19 +358,17 @@ int viorb_optimize_initial_gyro_bias_device(const viorb_vi_init_config* cfg, con
                                             int max_kf, int batch, double* bg, int32_t* status, void* stream) {
     VIORB_REQUIRE(cfg && n_est && twc12 && preint_in && bg && status, "null argument");
     VIORB_REQUIRE(shape_ok(max_kf, batch), "1 <= max_kf <= 4096, 1 <= batch <= 2^20");
-    if (vi_no_device()) return VIORB_ERR_NO_DEVICE;
-    ProfScope ps("k_vi_gyro_bias", (hipStream_t)stream);
-    hipLaunchKernelGGL(k_vi_gyro_bias, dim3(batch), dim3(64), 0, (hipStream_t)stream, vi_args(cfg, n_est, twc12, preint_in, max_kf, 2, bg, 3, nullptr, status));
-    VIORB_HIP_TRY(hipGetLastError());
+    VIORB_TRY(require_device());
+    VIORB_LAUNCH(k_vi_gyro_bias, batch, 64, 0, (hipStream_t)stream, vi_args(cfg, n_est, twc12, preint_in, max_kf, 2, bg, 3, nullptr, status));
     return VIORB_OK;
 }
 
 int viorb_optimize_initial_gyro_bias(const viorb_vi_init_config* cfg, int n, const float* twc12, const double* preint_in, double bg[3], int32_t* status) {
     VIORB_REQUIRE(cfg && twc12 && preint_in && bg && status && n >= 1 && n <= 4096, "null argument or n outside 1..4096");
-    if (vi_no_device()) return VIORB_ERR_NO_DEVICE;
-    ViBuf B;
-    int32_t* dn = B.up(&n, 1, 1); float* dT = B.up(twc12, (size_t)n * 12, 0); double* dP = B.up(preint_in, (size_t)n * 142, 0);
-    double* db = B.up((const double*)nullptr, 0, 3); int32_t* ds = B.up((const int32_t*)nullptr, 0, 1);
+    VIORB_TRY(require_device());
+    DeviceBufs B;
+    int32_t* dn = B.up(&n, 1, 1); float* dT = B.up(twc12, (size_t)n * 12); double* dP = B.up(preint_in, (size_t)n * 142);
+    double* db = B.zeros<double>(3); int32_t* ds = B.zeros<int32_t>(1);
     if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
     const int rc = viorb_optimize_initial_gyro_bias_device(cfg, dn, dT, dP, n, 1, db, ds, nullptr);
     if (rc != VIORB_OK) return rc;
@@ -407,20 +384,15 @@ int viorb_vi_init_device(const viorb_vi_init_config* cfg, const int32_t* n_est, 
     VIORB_REQUIRE(cfg && n_est && kf_time && imu_start && twc12 && preint_in && est && status && (imu || total_imu == 0), "null argument");
     VIORB_REQUIRE(preint_bg, "preint_bg: the re-integration is an output and the call's only work array");
     VIORB_REQUIRE(shape_ok(max_kf, batch) && total_imu >= 0, "1 <= max_kf <= 4096, 1 <= batch <= 2^20, total_imu >= 0");
-    if (vi_no_device()) return VIORB_ERR_NO_DEVICE;
+    VIORB_TRY(require_device());
     hipStream_t st = (hipStream_t)stream;
-    {   // step 1: bg into est[b][0..2], INVALID for n_est < 4
-        ProfScope ps("k_vi_gyro_bias", st);
-        hipLaunchKernelGGL(k_vi_gyro_bias, dim3(batch), dim3(64), 0, st, vi_args(cfg, n_est, twc12, preint_in, max_kf, 4, est, VI_EST_DOUBLES, est, status));
-        VIORB_HIP_TRY(hipGetLastError());
-    }
+    // step 1: bg into est[b][0..2], INVALID for n_est < 4
+    VIORB_LAUNCH(k_vi_gyro_bias, batch, 64, 0, st, vi_args(cfg, n_est, twc12, preint_in, max_kf, 4, est, VI_EST_DOUBLES, est, status));
     // KeyFrameInit::ComputePreInt with the new gyro bias: no accelerometer bias, dt clamped (src/LocalMapping.cc:58-94, 285-292)
     const int rc = launch_preint(n_est, kf_time, imu_start, imu, total_imu, est, VI_EST_DOUBLES, nullptr, 0, cfg->gyr_meas_cov, cfg->acc_meas_cov, 0, max_kf,
                                  batch, preint_bg, st);
     if (rc != VIORB_OK) return rc;
-    ProfScope ps("k_vi_solve", st);
-    hipLaunchKernelGGL(k_vi_solve, dim3(batch), dim3(64), 0, st, vi_args(cfg, n_est, twc12, preint_bg, max_kf, 4, est, VI_EST_DOUBLES, est, status));
-    VIORB_HIP_TRY(hipGetLastError());
+    VIORB_LAUNCH(k_vi_solve, batch, 64, 0, st, vi_args(cfg, n_est, twc12, preint_bg, max_kf, 4, est, VI_EST_DOUBLES, est, status));
     return VIORB_OK;
 }
 
@@ -429,12 +401,12 @@ int viorb_vi_init(const viorb_vi_init_config* cfg, int n_est, const double* kf_t
     VIORB_REQUIRE(cfg && kf_time && imu_start && twc12 && preint_in && est && status && n_est >= 1 && n_est <= 4096, "null argument or n_est outside 1..4096");
     const int32_t total = imu_start[n_est];
     VIORB_REQUIRE(total >= 0 && (imu || total == 0), "imu_start[n_est] = number of samples");
-    if (vi_no_device()) return VIORB_ERR_NO_DEVICE;
-    ViBuf B;
-    int32_t* dn = B.up(&n_est, 1, 1); double* dt = B.up(kf_time, n_est, 0); int32_t* ds = B.up(imu_start, (size_t)n_est + 1, 0);
-    double* di = B.up(imu, (size_t)total * 7, 0); float* dT = B.up(twc12, (size_t)n_est * 12, 0); double* dP = B.up(preint_in, (size_t)n_est * 142, 0);
-    double* de = B.up((const double*)nullptr, 0, VI_EST_DOUBLES); int32_t* dst = B.up((const int32_t*)nullptr, 0, 1);
-    double* dq = B.up((const double*)nullptr, 0, (size_t)n_est * 142);
+    VIORB_TRY(require_device());
+    DeviceBufs B;
+    int32_t* dn = B.up(&n_est, 1, 1); double* dt = B.up(kf_time, n_est); int32_t* ds = B.up(imu_start, (size_t)n_est + 1);
+    double* di = B.up(imu, (size_t)total * 7); float* dT = B.up(twc12, (size_t)n_est * 12); double* dP = B.up(preint_in, (size_t)n_est * 142);
+    double* de = B.zeros<double>(VI_EST_DOUBLES); int32_t* dst = B.zeros<int32_t>(1);
+    double* dq = B.zeros<double>((size_t)n_est * 142);
     if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
     const int rc = viorb_vi_init_device(cfg, dn, dt, ds, di, total, dT, dP, n_est, 1, de, dst, dq, nullptr);
     if (rc != VIORB_OK) return rc;
@@ -452,7 +424,7 @@ int viorb_vi_init_apply_device(const viorb_vi_init_config* cfg, const int32_t* n
                   (imu || total_imu == 0), "null argument");
     VIORB_REQUIRE(preint != preint_v, "preint (out) must not be the array the velocities are read from");
     VIORB_REQUIRE(shape_ok(max_kf, batch) && total_imu >= 0, "1 <= max_kf <= 4096, 1 <= batch <= 2^20, total_imu >= 0");
-    if (vi_no_device()) return VIORB_ERR_NO_DEVICE;
+    VIORB_TRY(require_device());
     hipStream_t st = (hipStream_t)stream;
     // KeyFrame::ComputePreInt with the new biases, no clamp (src/LocalMapping.cc:683-688, 729-735), for the streams that are OK
     const int rc = launch_preint(n_kf, kf_time, imu_start, imu, total_imu, est + VI_BG, VI_EST_DOUBLES, est + VI_BA, VI_EST_DOUBLES, cfg->gyr_meas_cov,
@@ -461,9 +433,7 @@ int viorb_vi_init_apply_device(const viorb_vi_init_config* cfg, const int32_t* n
     ApplyArgs A;
     A.X = vi_extrinsics(cfg->Tbc); A.n_est = n_est; A.n_kf = n_kf; A.twc12 = twc12; A.pose12 = pose12; A.est = est; A.status = status; A.preint_v = preint_v;
     A.preint_final = preint; A.max_kf = max_kf; A.navstate = navstate; A.pose12_scaled = pose12_scaled;
-    ProfScope ps("k_vi_apply", st);
-    hipLaunchKernelGGL(k_vi_apply, dim3(batch), dim3(64), 0, st, A);
-    VIORB_HIP_TRY(hipGetLastError());
+    VIORB_LAUNCH(k_vi_apply, batch, 64, 0, st, A);
     return VIORB_OK;
 }
 
@@ -474,13 +444,13 @@ int viorb_vi_init_apply(const viorb_vi_init_config* cfg, int n_est, int n_kf, co
     VIORB_REQUIRE(n_est >= 4 && n_kf >= n_est && n_kf <= 4096, "4 <= n_est <= n_kf <= 4096");
     const int32_t total = imu_start[n_kf];
     VIORB_REQUIRE(total >= 0 && (imu || total == 0), "imu_start[n_kf] = number of samples");
-    if (vi_no_device()) return VIORB_ERR_NO_DEVICE;
-    ViBuf B;
+    VIORB_TRY(require_device());
+    DeviceBufs B;
     const int32_t ok = VIORB_OK;
-    int32_t *dne = B.up(&n_est, 1, 1), *dnk = B.up(&n_kf, 1, 1), *dst = B.up(&ok, 1, 1), *ds = B.up(imu_start, (size_t)n_kf + 1, 0);
-    double *dt = B.up(kf_time, n_kf, 0), *di = B.up(imu, (size_t)total * 7, 0), *de = B.up(est, VI_EST_DOUBLES, 0), *dv = B.up(preint_v, (size_t)n_kf * 142, 0);
-    float *dT = B.up(twc12, (size_t)n_kf * 12, 0), *dp = B.up(pose12, (size_t)n_kf * 12, 0), *dq = B.up((const float*)nullptr, 0, (size_t)n_kf * 12);
-    double *dn = B.up((const double*)nullptr, 0, (size_t)n_kf * 22), *dr = B.up((const double*)nullptr, 0, (size_t)n_kf * 142);
+    int32_t *dne = B.up(&n_est, 1, 1), *dnk = B.up(&n_kf, 1, 1), *dst = B.up(&ok, 1, 1), *ds = B.up(imu_start, (size_t)n_kf + 1);
+    double *dt = B.up(kf_time, n_kf), *di = B.up(imu, (size_t)total * 7), *de = B.up(est, VI_EST_DOUBLES), *dv = B.up(preint_v, (size_t)n_kf * 142);
+    float *dT = B.up(twc12, (size_t)n_kf * 12), *dp = B.up(pose12, (size_t)n_kf * 12), *dq = B.zeros<float>((size_t)n_kf * 12);
+    double *dn = B.zeros<double>((size_t)n_kf * 22), *dr = B.zeros<double>((size_t)n_kf * 142);
     if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
     const int rc = viorb_vi_init_apply_device(cfg, dne, dnk, dt, ds, di, total, dT, dp, de, dst, dv, n_kf, 1, dn, dq, dr, nullptr);
     if (rc != VIORB_OK) return rc;
@@ -494,12 +464,10 @@ int viorb_vi_init_apply(const viorb_vi_init_config* cfg, int n_est, int n_kf, co
 int viorb_scale_map_points_device(float* points, float* min_dist, float* max_dist, const double* est, const int32_t* status, int np, int batch, void* stream) {
     VIORB_REQUIRE(points && est && status, "null argument");
     VIORB_REQUIRE(np >= 0 && batch >= 1 && batch <= 65535, "np >= 0, 1 <= batch <= 65535");
-    if (vi_no_device()) return VIORB_ERR_NO_DEVICE;
+    VIORB_TRY(require_device());
     if (np == 0) return VIORB_OK;
     const int blocks = std::max(1, std::min(64, (3 * np / 4 + 255) / 256));
-    ProfScope ps("k_scale_map_points", (hipStream_t)stream);
-    hipLaunchKernelGGL(k_scale_map_points, dim3(blocks, batch), dim3(256), 0, (hipStream_t)stream, points, min_dist, max_dist, est, status, np);
-    VIORB_HIP_TRY(hipGetLastError());
+    VIORB_LAUNCH(k_scale_map_points, dim3(blocks, batch), 256, 0, (hipStream_t)stream, points, min_dist, max_dist, est, status, np);
     return VIORB_OK;
 }
 

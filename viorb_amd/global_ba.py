@@ -5,7 +5,7 @@ invSigma2, gw [3], cam [16]."""
 import ctypes as C
 import numpy as np
 from . import capi
-from .capi import lib, check, ptr
+from .capi import lib, check, ptr, _torch_up as up
 
 _f64 = lambda a: np.ascontiguousarray(a, np.float64)
 _i32 = lambda a: np.ascontiguousarray(a, np.int32)
@@ -48,7 +48,6 @@ def GlobalBundleAdjustmentNavStateDevice(kfs, prev, fixed, preint, points, edge_
     form); the results come back as numpy arrays."""
     import torch
     dev = torch.device("cuda", 0)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     kfs = _f64(kfs).reshape(-1, 22); points = _f64(points).reshape(-1, 3); ei = _i32(edge_idx).reshape(-1, 2)
     t = dict(kfs=up(kfs), prev=up(_i32(prev)), fixed=up(np.ascontiguousarray(fixed, np.uint8)), preint=up(_f64(preint).reshape(-1, 142)),
              points=up(points if len(points) else np.zeros((1, 3))), ei=up(ei if len(ei) else np.zeros((1, 2), np.int32)),

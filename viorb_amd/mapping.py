@@ -5,7 +5,7 @@ median_depth and kf2_first. The camera is a dict(intr4, mb, mbf, scale_factor, s
 import ctypes as C
 import numpy as np
 from . import capi
-from .capi import lib, check, ptr
+from .capi import lib, check, ptr, _torch_up as _up
 
 _u8 = lambda a: np.ascontiguousarray(a, np.uint8)
 _f32 = lambda a: np.ascontiguousarray(a, np.float32)
@@ -40,14 +40,6 @@ def TriangulatePairs(cam, kf1, kf2, match12):
 def _dev():
     import torch
     return torch, torch.device("cuda", 0)
-
-
-def _up(a):
-    torch, dev = _dev()
-    a = np.ascontiguousarray(a)
-    if a.dtype.fields is not None:
-        a = a.view(np.uint8)
-    return torch.from_numpy(a).to(dev)
 
 
 def _stack(arrs, cap, dtype, tail=()):

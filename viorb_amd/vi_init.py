@@ -5,7 +5,7 @@ dict(Tbc [4,4], g) with optional gyr_meas_cov / acc_meas_cov."""
 import ctypes as C
 import numpy as np
 from . import capi
-from .capi import lib, check, ptr
+from .capi import lib, check, ptr, _torch_up as _up
 
 EST = dict(bg=slice(0, 3), sstar=3, gwstar=slice(4, 7), s=7, dtheta=slice(8, 10), ba=slice(10, 13), Rwi=slice(13, 22), Rwi_=slice(22, 31),
            gw=slice(31, 34), w=slice(34, 38), w2=slice(38, 44))
@@ -54,11 +54,6 @@ def pack_streams(streams, n_kf=None, max_kf=None):
 def _dev():
     import torch
     return torch, torch.device("cuda", 0)
-
-
-def _up(a):
-    torch, dev = _dev()
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
 def PreintegrateIntervals(stream, bg=None, ba=None, clamp=True, gyr_meas_cov=0.0, acc_meas_cov=0.0):
