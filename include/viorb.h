@@ -916,6 +916,76 @@ int viorb_debug_gba_cholesky(const double* A, int n, double* L, int32_t* ok);
 /* Test hook: accept (1) / reject (0) of every Levenberg trial of the calling thread's last global solve, in order; *n = their number. */
 int viorb_debug_gba_last_trials(uint8_t* accepted, int cap, int* n);
 
+/* ---- Place recognition: BowVector, ORBVocabulary::score and KeyFrameDatabase (reference src/KeyFrameDatabase.cc:40-309) ------------
+ * The question relocalisation (src/Tracking.cc:2134) and loop detection (src/LoopClosing.cc:148-165) begin with: which stored key frames
+ * look like this one? Integer, float-compare and ordered-sum arithmetic only: every output equals the reference's bit for bit.
+ *
+ * BowVector::addWeight + normalize(L1) (Thirdparty/DBoW2/DBoW2/BowVector.cpp:36-85) from the outputs of viorb_bow_transform_device
+ * ([b*cap + i], count[b]): features with weight > 0 only, the weights of one word summed in feature order, the norm summed over the
+ * words in ascending order from 0.0, every value divided by it. Per frame: ascending bow_word[b*cap + j] and bow_val[b*cap + j] for
+ * j < bow_count[b] (0 when every word is stopped). cap (host form: n) above VIORB_BOW_VECTOR_MAX_FEATURES is refused with
+ * VIORB_ERR_CAPACITY; nothing is ever truncated. */
+#define VIORB_BOW_VECTOR_MAX_FEATURES 8192
+int viorb_bow_vector_device(const int32_t* word, const double* weight, const int32_t* count, int cap, int batch, int32_t* bow_word,
+                            double* bow_val, int32_t* bow_count, void* stream);
+int viorb_bow_vector(const int32_t* word, const double* weight, int n, int32_t* bow_word, double* bow_val, int* bow_count);
+
+/* ORBVocabulary::score = L1Scoring::score (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68) for a list of pairs: score[p] of vector
+ * pair_a[p] of set a (a_word / a_val [i*a_cap + j], a_count[i]; the first argument of score) and vector pair_b[p] of set b. The host
+ * form takes the number of vectors na / nb and checks counts, ascending words and pair indices. */
+int viorb_bow_score_device(const int32_t* a_word, const double* a_val, const int32_t* a_count, int a_cap, const int32_t* b_word,
+                           const double* b_val, const int32_t* b_count, int b_cap, const int32_t* pair_a, const int32_t* pair_b,
+                           int n_pairs, double* score, void* stream);
+int viorb_bow_score(const int32_t* a_word, const double* a_val, const int32_t* a_count, int a_cap, int na, const int32_t* b_word,
+                    const double* b_val, const int32_t* b_count, int b_cap, int nb, const int32_t* pair_a, const int32_t* pair_b,
+                    int n_pairs, double* score);
+
+/* The key-frame database. One handle per map, and one stream at a time per handle: the calls on a handle are ordered by the caller,
+ * and work enqueued on one stream must be complete before the handle is used with another. Key frames live in slots numbered in add
+ * order (never reused); on the device they are offsets, words[] (int32), vals[] (double) and alive[], words and values apart because
+ * the first query pass reads words only. n_words = the vocabulary's size; the hints size the first allocation (made by the first add;
+ * later ones grow geometrically with a device-to-device copy on the caller's stream).
+ *   add_device: appends n key frames straight from viorb_bow_vector_device's outputs ([i*cap + j], bow_count[i]); *first_slot_out
+ *     (may be NULL) = the first new slot, written only when the call succeeds. It does not wait for the device unless the arena has
+ *     to grow (the host keeps an upper bound of the fill, n*cap per call). add: the host form for one key frame; words ascending strictly and < n_words, values finite and > 0.
+ *   erase: KeyFrameDatabase::erase; the slot stays, counts no common word and is never a candidate. clear: as a new database.
+ *   size: slots handed out and slots alive. create / erase / clear / size need no device. */
+typedef struct viorb_kfdb viorb_kfdb;   /* opaque */
+#define VIORB_KFDB_LOOP  0   /* DetectLoopCandidates(pKF, minScore), src/KeyFrameDatabase.cc:76-197 */
+#define VIORB_KFDB_RELOC 1   /* DetectRelocalizationCandidates(F), :199-309 */
+int viorb_kfdb_create(int n_words, int kf_capacity_hint, int entry_capacity_hint, viorb_kfdb** out);
+int viorb_kfdb_destroy(viorb_kfdb* db);
+int viorb_kfdb_add_device(viorb_kfdb* db, const int32_t* bow_word, const double* bow_val, const int32_t* bow_count, int cap, int n,
+                          int* first_slot_out, void* stream);
+int viorb_kfdb_add(viorb_kfdb* db, const int32_t* words, const double* vals, int n_entries, int* slot);
+int viorb_kfdb_erase(viorb_kfdb* db, int slot);
+int viorb_kfdb_clear(viorb_kfdb* db);
+int viorb_kfdb_size(const viorb_kfdb* db, int* n_slots, int* n_alive);
+/* n_q query vectors (q_word / q_val [q*q_cap + j], q_count[q]) against the database in one call. Loop mode: min_score[q], and
+ * excl_start [n_q + 1] / excl_slot = the CSR of pKF->GetConnectedKeyFrames() as slots; all three unused (NULL) in relocalisation mode.
+ * The device form wants excl_slot non-NULL in loop mode even when every list is empty (any device pointer: it is not read then). The
+ * query only enqueues work: new key frames and erasures since the last query reach alive[] by memsets on the same stream.
+ * covis10[slot*10 + k] = GetBestCovisibilityKeyFrames(10) of every slot in order, padded with -1. Outputs: cand[q*cand_cap + j] the
+ * candidate slots in the reference's output order and n_cand[q] their number — n_cand[q] > cand_cap reports an overflow (only the first
+ * cand_cap were written; the host form then returns VIORB_ERR_CAPACITY); stats[q*4 ..] = key frames sharing a word, maxCommonWords,
+ * key frames scored, entries of lScoreAndMatch; common_out / score_out [q*n_slots + s] (may be NULL) = mnLoopWords / mLoopScore
+ * (mnRelocWords / mRelocScore): the common-word count (0 for a dead or excluded slot) and the float score, -1 where not scored.
+ * A neighbour adds to a group's accScore only if it was scored in this query, in both modes (deviation 10).
+ * workspace: viorb_kfdb_query_workspace_bytes(db, n_q) bytes of device memory, 256-byte aligned, sized after the last add. */
+size_t viorb_kfdb_query_workspace_bytes(const viorb_kfdb* db, int n_q);
+int viorb_kfdb_query_device(viorb_kfdb* db, int mode, int n_q, const int32_t* q_word, const double* q_val, const int32_t* q_count,
+                            int q_cap, const float* min_score, const int32_t* excl_start, const int32_t* excl_slot,
+                            const int32_t* covis10, int cand_cap, int32_t* cand, int32_t* n_cand, int32_t* stats, int32_t* common_out,
+                            float* score_out, void* workspace, size_t workspace_bytes, void* stream);
+int viorb_kfdb_query(viorb_kfdb* db, int mode, int n_q, const int32_t* q_word, const double* q_val, const int32_t* q_count, int q_cap,
+                     const float* min_score, const int32_t* excl_start, const int32_t* excl_slot, const int32_t* covis10, int cand_cap,
+                     int32_t* cand, int32_t* n_cand, int32_t* stats, int32_t* common_out, float* score_out);
+/* Host-only test hooks (no product path calls them): place_core.h compiled for the host. score: L1Scoring::score of two vectors.
+ * select: steps 2-6 of a query from the per-slot common-word counts, smallest common words and float scores (read where scored). */
+double viorb_debug_place_score(const int32_t* a_word, const double* a_val, int na, const int32_t* b_word, const double* b_val, int nb);
+int viorb_debug_place_select(int mode, int n_slots, const int32_t* common, const int32_t* min_word, const float* score, float min_score,
+                             const int32_t* covis10, int cand_cap, int32_t* cand, int32_t* n_cand, int32_t* stats4);
+
 
 #ifdef __cplusplus
 }

@@ -10,3 +10,4 @@ from .frontend import Frontend, ORBmatcher, PoseOptimization, PoseOptimizationSE
 from .mapping import TriangulatePairs, TriangulatePairsBatch, MapPointUpdate, CreateNewMapPoints, CreateNewMapPointsHost, mapping_camera  # noqa: F401
 from .vi_init import PreintegrateIntervals, PreintegrateIntervalsBatch, OptimizeInitialGyroBias, ViInit, ViInitHost, ViInitApplyHost, vi_config, unpack_est  # noqa: F401
 from .global_ba import GlobalBundleAdjustmentNavState, GlobalBundleAdjustmentNavStateDevice, gba_workspace_bytes  # noqa: F401
+from .place import BowVector, BowVector_device, BowScore, BowScorePairs, KeyFrameDatabase, pack_bows  # noqa: F401

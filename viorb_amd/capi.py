@@ -226,6 +226,22 @@ SIGNATURES = {
     "viorb_global_ba_navstate_device": (i32, [PP(GbaConfig), vp, i32, vp, vp, vp, vp, i32, vp, vp, i32] + [vp] * 8 + [sz, vp]),
     "viorb_debug_gba_cholesky": (i32, [vp, i32, vp, vp]),
     "viorb_debug_gba_last_trials": (i32, [vp, i32, PP(i32)]),
+    "viorb_bow_vector_device": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "viorb_bow_vector": (i32, [vp, vp, i32, vp, vp, PP(i32)]),
+    "viorb_bow_score_device": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]),
+    "viorb_bow_score": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, i32, vp]),
+    "viorb_kfdb_create": (i32, [i32, i32, i32, PP(vp)]),
+    "viorb_kfdb_destroy": (i32, [vp]),
+    "viorb_kfdb_add_device": (i32, [vp, vp, vp, vp, i32, i32, PP(i32), vp]),
+    "viorb_kfdb_add": (i32, [vp, vp, vp, i32, PP(i32)]),
+    "viorb_kfdb_erase": (i32, [vp, i32]),
+    "viorb_kfdb_clear": (i32, [vp]),
+    "viorb_kfdb_size": (i32, [vp, PP(i32), PP(i32)]),
+    "viorb_kfdb_query_workspace_bytes": (sz, [vp, i32]),
+    "viorb_kfdb_query_device": (i32, [vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "viorb_kfdb_query": (i32, [vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+    "viorb_debug_place_score": (C.c_double, [vp, vp, i32, vp, vp, i32]),
+    "viorb_debug_place_select": (i32, [i32, i32, vp, vp, vp, f32, vp, i32, vp, vp, vp]),
 }
 
 _lib = None

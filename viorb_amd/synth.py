@@ -919,3 +919,70 @@ def make_global_ba_problem(seed, N=21, n_points=None, revisit_frac=0.0, n_fixed=
     return dict(kfs=kfs0, kfs_true=kfs_true, prev=prev, fixed=fixed, preint=preint, points=np.float32(pts0).astype(np.float64), points_true=pts,
                 edge_idx=np.array(edges_i, np.int32).reshape(-1, 2), edge_obs=np.array(edges_o, np.float64).reshape(-1, 3),
                 gw=GRAVITY_CAM_WORLD.copy(), cam=cam, stream=stream, bias=(bg, ba))
+
+
+def _l1_normalised(words, weights):
+    """Ascending unique words and their summed weights divided by the norm, the norm summed in ascending word order (BowVector::normalize)."""
+    acc = {}
+    for w, v in zip(words.tolist(), weights.tolist()):
+        acc[w] = acc.get(w, 0.0) + v
+    ids = sorted(acc)
+    norm = 0.0
+    for k in ids:
+        norm += acc[k]
+    return np.array(ids, np.int32), np.array([acc[k] / norm for k in ids], np.float64)
+
+
+def _place_words(rng, N, per_kf, n_words, place_len, pool_frac, revisit_at):
+    """The word draws of a key-frame sequence that revisits its start: key frame i looks at place i // place_len, from revisit_at * N on at
+    the places of the start again; pool_frac of its words come from the place's pool of 2 * per_kf words, the rest from anywhere."""
+    first_revisit = int(revisit_at * N)
+    n_places = (N + place_len - 1) // place_len
+    pools = [rng.choice(n_words, min(2 * per_kf, n_words), replace=False) for _ in range(n_places)]
+    out = []
+    for i in range(N):
+        place = (i if i < first_revisit else i - first_revisit) // place_len
+        n_pool = int(pool_frac * per_kf)
+        out.append(np.concatenate([rng.choice(pools[place], n_pool), rng.integers(0, n_words, per_kf - n_pool)]))
+    return out
+
+
+def _place_graph(rng, N, erase_frac, n_connected):
+    """The database side of a place problem: key frames 0 .. N - 2 are the slots, key frame N - 1 asks. The last n_connected slots are
+    connected to it, erase_frac of the others are erased, and a slot's covisibles are its ten nearest slots, nearest first."""
+    S = N - 1
+    connected = list(range(max(S - n_connected, 0), S))
+    free = [s for s in range(S) if s not in connected]
+    erased = sorted(rng.choice(free, int(erase_frac * S), replace=False).tolist()) if free and erase_frac > 0 else []
+    covis10 = np.full((S, 10), -1, np.int32)
+    for s in range(S):
+        near = [t for d in range(1, 11) for t in (s - d, s + d) if 0 <= t < S][:10]
+        covis10[s, :len(near)] = near
+    return connected, erased, covis10
+
+
+def make_place_problem(seed, N=48, per_kf=120, n_words=4096, place_len=12, pool_frac=0.7, revisit_at=0.75, erase_frac=0.1, n_connected=6):
+    """A place-recognition problem built as BoW vectors directly: dict(n_words, bows = N (ids, vals) pairs — the first N - 1 are the
+    database's slots in add order, the last one is the query —, connected, erased, covis10 [N - 1, 10])."""
+    rng = np.random.Generator(np.random.PCG64(seed + 9090))
+    idf = rng.uniform(0.05, 8.0, n_words)
+    bows = [_l1_normalised(w, idf[w]) for w in _place_words(rng, N, per_kf, n_words, place_len, pool_frac, revisit_at)]
+    connected, erased, covis10 = _place_graph(rng, N, erase_frac, n_connected)
+    return dict(n_words=n_words, bows=bows, connected=connected, erased=erased, covis10=covis10)
+
+
+def make_place_descriptors(seed, voc, N=24, per_kf=100, noise_bits=2, place_len=6, pool_frac=0.7, revisit_at=0.75, erase_frac=0.1, n_connected=3):
+    """The same construction through a vocabulary (make_vocabulary): dict(desc = N arrays [per_kf, 32] near the drawn words' leaves,
+    connected, erased, covis10); the BoW vectors come out of the transform."""
+    rng = np.random.Generator(np.random.PCG64(seed + 9191))
+    leaf_of_word = np.nonzero(voc["word_id"] >= 0)[0]
+    leaf_of_word = leaf_of_word[np.argsort(voc["word_id"][leaf_of_word])]
+    desc = []
+    for w in _place_words(rng, N, per_kf, len(leaf_of_word), place_len, pool_frac, revisit_at):
+        d = voc["desc"][leaf_of_word[w]].copy()
+        for _ in range(noise_bits):
+            b = rng.integers(0, 256, len(d))
+            d[np.arange(len(d)), b >> 3] ^= (1 << (b & 7)).astype(np.uint8)
+        desc.append(d)
+    connected, erased, covis10 = _place_graph(rng, N, erase_frac, n_connected)
+    return dict(desc=desc, connected=connected, erased=erased, covis10=covis10)
