@@ -916,6 +916,10 @@ int viorb_debug_gba_cholesky(const double* A, int n, double* L, int32_t* ok);
 /* Test hook: accept (1) / reject (0) of every Levenberg trial of the calling thread's last global solve, in order; *n = their number. */
 int viorb_debug_gba_last_trials(uint8_t* accepted, int cap, int* n);
 
+/* The vision-only global bundle adjustment over SE3 poses (Optimizer::BundleAdjustment): viorb_global_ba_se3 and its companions are
+ * declared in a header of their own, which is part of this interface and reuses viorb_gba_config. */
+#include "viorb_global_ba_se3.h"
+
 /* ---- Place recognition: BowVector, ORBVocabulary::score and KeyFrameDatabase (reference src/KeyFrameDatabase.cc:40-309) ------------
  * The question relocalisation (src/Tracking.cc:2134) and loop detection (src/LoopClosing.cc:148-165) begin with: which stored key frames
  * look like this one? Integer, float-compare and ordered-sum arithmetic only: every output equals the reference's bit for bit.

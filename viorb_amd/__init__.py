@@ -9,5 +9,5 @@ from .extractor import ORBextractor  # noqa: F401
 from .frontend import Frontend, ORBmatcher, PoseOptimization, PoseOptimizationSE3, LocalBundleAdjustmentNavState, LocalBundleAdjustmentNavStateBatch, LocalBundleAdjustment, LocalBundleAdjustmentBatch, ORBVocabulary, SearchByBoW, SearchForTriangulation, Fuse, preintegrate, descriptor_distance, match_bruteforce, SearchLocalPoints, UndistortKeyPoints, ComputeImageBounds  # noqa: F401
 from .mapping import TriangulatePairs, TriangulatePairsBatch, MapPointUpdate, CreateNewMapPoints, CreateNewMapPointsHost, mapping_camera  # noqa: F401
 from .vi_init import PreintegrateIntervals, PreintegrateIntervalsBatch, OptimizeInitialGyroBias, ViInit, ViInitHost, ViInitApplyHost, vi_config, unpack_est  # noqa: F401
-from .global_ba import GlobalBundleAdjustmentNavState, GlobalBundleAdjustmentNavStateDevice, gba_workspace_bytes  # noqa: F401
+from .global_ba import GlobalBundleAdjustmentNavState, GlobalBundleAdjustmentNavStateDevice, gba_workspace_bytes, GlobalBundleAdjustmentSE3, GlobalBundleAdjustmentSE3Device, gba_se3_workspace_bytes  # noqa: F401
 from .place import BowVector, BowVector_device, BowScore, BowScorePairs, KeyFrameDatabase, pack_bows  # noqa: F401

@@ -1,5 +1,6 @@
-"""ctypes declarations of include/viorb.h (kept 1:1 with the header; tests/test_host_hooks.py checks that every
-declared entry point is exported, has a signature here and that the argument counts agree)."""
+"""ctypes declarations of include/viorb.h and of the header it includes, viorb_global_ba_se3.h (kept 1:1; tests/test_host_hooks.py checks that every
+declared entry point of viorb.h is exported, has a signature here and that the argument counts agree; tests/test_global_ba_se3_ref.py
+does the same for SIGNATURES_GLOBAL_BA_SE3)."""
 import ctypes as C
 import os
 import numpy as np
@@ -243,6 +244,14 @@ SIGNATURES = {
     "viorb_debug_place_score": (C.c_double, [vp, vp, i32, vp, vp, i32]),
     "viorb_debug_place_select": (i32, [i32, i32, vp, vp, vp, f32, vp, i32, vp, vp, vp]),
 }
+# mirrors include/viorb_global_ba_se3.h (the header viorb.h includes for the vision-only global bundle adjustment);
+# tests/test_global_ba_se3_ref.py checks names and argument counts against it
+SIGNATURES_GLOBAL_BA_SE3 = {
+    "viorb_global_ba_se3_workspace_bytes": (sz, [i32, i32, i32]),
+    "viorb_global_ba_se3": (i32, [PP(GbaConfig), vp, i32, vp, vp, i32, vp, vp, i32] + [vp] * 6),
+    "viorb_global_ba_se3_device": (i32, [PP(GbaConfig), vp, i32, vp, vp, i32, vp, vp, i32] + [vp] * 7 + [sz, vp]),
+    "viorb_debug_gba_se3_edge": (i32, [vp] * 7),
+}
 
 _lib = None
 
@@ -263,7 +272,7 @@ def lib():
         except Exception:
             pass
         L = C.CDLL(SO_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GLOBAL_BA_SE3.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -17,48 +17,19 @@
 // Workgroups never wait on each other inside a kernel; the steps are ordered by the stream. The Levenberg control runs on the host and
 // reads 3 doubles per trial (chi2, scale, pivot status). The graph bookkeeping (point and key-frame edge lists, free-key-frame ranks,
 // IMU information matrices, argument checks of the device form) is built on the device before the first iteration.
+// The graph bookkeeping, k_gba_dinv, k_gba_max_diag, the Cholesky chain and the Levenberg loop (gba_run) also serve the vision-only solve of
+// global_ba_se3.hip, which plugs its own launches in through GbaOps (global_ba_dev.h); the sizes that differ between the two come from GbaDev.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-#include "viorb_common.h"
-#include "global_ba_core.h"
+#include "global_ba_dev.h"
 
 namespace viorb {
 
 typedef double gba_v4d __attribute__((ext_vector_type(4)));
-enum { GBA_S_CHI = 0, GBA_S_SCALE, GBA_S_FAIL, GBA_S_MAXDIAG, GBA_S_N = 8 };
-enum { GBA_ST_INVALID = 0, GBA_ST_NFREE, GBA_ST_N = 4 };
-
-struct GbaDev {
-    int nk, np, ne, nfree, n, ld, robust;
-    double *kf, *kf_bak;                // [nk][22]
-    double *pt, *pt_bak;                // [np][3]
-    const int32_t* prev;                // [nk]
-    const uint8_t* fixed;               // [nk]
-    const int32_t* e_idx;               // [ne][2] (point, key frame)
-    const double *e_obs, *preint;       // [ne][3], [nk][142]
-    int *fidx, *pt_start, *kf_start, *kf_cur, *kf_tmp, *kf_list;   // rank among the free key frames or -1; CSR by point; CSR by key frame
-    double* info_pvr;                   // [nk][81]
-    double *err, *Jp, *Jk, *wgt, *We;   // [ne][2], [ne][6], [ne][12], [ne], [ne][18] = wgt Jk^T Jp
-    double *Hll, *bl, *Dinv, *db, *xl;  // [np][9], [np][3], [np][9], [np][3], [np][3]
-    double *Hd, *Ho, *bp;               // diagonal blocks [nk][144] by free rank, block (key frame i, prev[i]) [nk][144], [12 nk]
-    double *S, *rhs, *xp;               // [ld][ld] lower triangle, [ld], [ld]
-    double* scal;                       // GBA_S_*
-    int* status;                        // GBA_ST_*
-    uint8_t* included;                  // [np]
-    double cam[16], gw[3];
-};
-
-__device__ __forceinline__ double gba_block_sum(double v, double* s_red) {      // 256 threads; result valid in thread 0
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return s_red[0] + s_red[1] + s_red[2] + s_red[3];
-}
 
 // ---- graph bookkeeping ----------------------------------------------------------------------------------------------------------------
 // one workgroup: predecessor check, free ranks, information matrices of the IMU factors
@@ -82,7 +53,7 @@ __global__ __launch_bounds__(256) void k_gba_edges_scan(GbaDev D) {
     if (k >= D.ne) return;
     const int p = D.e_idx[2 * k], f = D.e_idx[2 * k + 1], before = k ? D.e_idx[2 * k - 2] : 0;
     if (!gba_edge_ok(p, f, before, D.np, D.nk) || before < 0 || before >= D.np) { atomicOr(&D.status[GBA_ST_INVALID], 2); return; }
-    if (!(D.e_obs[3 * (size_t)k + 2] > 0.0)) atomicOr(&D.status[GBA_ST_INVALID], 8);
+    if (!(D.e_obs[(size_t)D.obs_w * k + D.obs_w - 1] > 0.0)) atomicOr(&D.status[GBA_ST_INVALID], GBA_BAD_SIGMA);
     for (int q = (k ? before + 1 : 0); q <= p; q++) D.pt_start[q] = k;
     if (k == D.ne - 1) for (int q = p + 1; q <= D.np; q++) D.pt_start[q] = D.ne;
     atomicAdd(&D.kf_cur[f], 1);
@@ -289,9 +260,9 @@ __global__ __launch_bounds__(64) void k_gba_imu(GbaDev D) {
 __global__ __launch_bounds__(256) void k_gba_max_diag(GbaDev D) {
     __shared__ double s_red[4];
     double m = 0;
-    const int n = D.n;
+    const int n = D.n, blk = D.blk;
     for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < n + 3 * D.np; q += gridDim.x * blockDim.x)
-        m = fmax(m, fabs(q < n ? D.Hd[(size_t)(q / 12) * 144 + (q % 12) * 13] : D.Hll[(size_t)((q - n) / 3) * 9 + ((q - n) % 3) * 4]));
+        m = fmax(m, fabs(q < n ? D.Hd[(size_t)(q / blk) * blk * blk + (q % blk) * (blk + 1)] : D.Hll[(size_t)((q - n) / 3) * 9 + ((q - n) % 3) * 4]));
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) m = fmax(m, __shfl_xor(m, d));
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = m;
@@ -550,47 +521,29 @@ __global__ __launch_bounds__(256) void k_gba_update(GbaDev D, double lambda) {
     if (threadIdx.x == 0 && sc != 0.0) unsafeAtomicAdd(&D.scal[GBA_S_SCALE], sc);
 }
 
-namespace {
-// The host form's lease of a stream context. An error path may leave work queued on the stream: nothing of it may still run when the
-// next borrower takes the context, so the stream is drained before the context goes back. The arena grows to exactly what is asked for.
-struct GbaArena : StreamCtxLease {
-    ~GbaArena() { if (c) (void)hipStreamSynchronize(c->st); }
-    bool reserve(size_t bytes) {
-        if (c->bytes >= bytes) return true;
-        if (c->arena) (void)hipFree(c->arena);
-        c->arena = nullptr; c->bytes = 0;
-        if (hipMalloc(&c->arena, bytes) != hipSuccess) return false;
-        c->bytes = bytes;
-        return true;
-    }
-};
-// accept (1) / reject (0) of every trial of the calling thread's last solve, for viorb_debug_gba_last_trials
-thread_local std::vector<uint8_t> g_gba_trials;
+std::vector<uint8_t>& gba_trials() { thread_local std::vector<uint8_t> t; return t; }
 
-// Lays the work arrays out in a workspace; S (the only array whose size depends on the number of free key frames) comes last.
-// Returns the bytes up to S (head) and in all; nfree < 0: only the head is laid out
-size_t gba_layout(GbaDev& D, void* base, int nk, int np, int ne, int nfree, size_t* head_bytes) {
+size_t gba_layout(GbaDev& D, void* base, int nfree, size_t* clear_bytes) {
+    const int nk = D.nk, np = D.np, ne = D.ne, blk = D.blk, rows = D.rows;
+    const bool imu = blk == 12;
     WorkspaceLayout L(base);
     L.take(&D.scal, GBA_S_N); L.take(&D.status, GBA_ST_N);
     L.take(&D.pt_start, (size_t)np + 1); L.take(&D.kf_cur, nk);           // cleared together with scal / status: see gba_run
-    const size_t clear_bytes = L.off;
-    L.take(&D.kf_bak, (size_t)nk * 22); L.take(&D.pt_bak, (size_t)np * 3);
+    if (clear_bytes) *clear_bytes = L.off;
+    L.take(&D.kf_bak, (size_t)nk * D.kf_w); L.take(&D.pt_bak, (size_t)np * 3);
     L.take(&D.fidx, nk); L.take(&D.kf_start, (size_t)nk + 1); L.take(&D.kf_tmp, ne); L.take(&D.kf_list, ne);
-    L.take(&D.info_pvr, (size_t)nk * 81);
-    L.take(&D.err, (size_t)ne * 2); L.take(&D.Jp, (size_t)ne * 6); L.take(&D.Jk, (size_t)ne * 12); L.take(&D.wgt, ne); L.take(&D.We, (size_t)ne * 18);
+    L.take(&D.info_pvr, imu ? (size_t)nk * 81 : 0);
+    L.take(&D.err, (size_t)ne * rows); L.take(&D.Jp, (size_t)ne * 3 * rows); L.take(&D.Jk, (size_t)ne * 6 * rows); L.take(&D.wgt, ne); L.take(&D.We, (size_t)ne * 18);
     L.take(&D.Hll, (size_t)np * 9); L.take(&D.bl, (size_t)np * 3); L.take(&D.Dinv, (size_t)np * 9); L.take(&D.db, (size_t)np * 3); L.take(&D.xl, (size_t)np * 3);
-    L.take(&D.Hd, (size_t)nk * 144); L.take(&D.Ho, (size_t)nk * 144); L.take(&D.bp, (size_t)nk * 12);
-    L.take(&D.rhs, (size_t)gba_ld(12 * nk)); L.take(&D.xp, (size_t)gba_ld(12 * nk));
+    L.take(&D.Hd, (size_t)nk * blk * blk); L.take(&D.Ho, imu ? (size_t)nk * 144 : 0); L.take(&D.bp, (size_t)nk * blk);
+    L.take(&D.rhs, (size_t)gba_ld(blk * nk)); L.take(&D.xp, (size_t)gba_ld(blk * nk));
     L.take(static_cast<double**>(nullptr), 0);
-    if (head_bytes) *head_bytes = clear_bytes;
     const size_t head = L.end();
     if (nfree < 0) return head;
-    const size_t ld = gba_ld(12 * nfree);
+    const size_t ld = gba_ld(blk * nfree);
     D.S = reinterpret_cast<double*>(static_cast<uint8_t*>(base) + head);
     return head + ld * ld * sizeof(double);
 }
-
-inline unsigned gba_blocks(size_t n, unsigned per) { return (unsigned)std::max<size_t>(1, (n + per - 1) / per); }
 
 // the factorisation chain + both substitutions; S and rhs hold the system, xp receives the solution
 int gba_factor_solve(const GbaDev& D, hipStream_t st, bool solve) {
@@ -604,6 +557,20 @@ int gba_factor_solve(const GbaDev& D, hipStream_t st, bool solve) {
     return VIORB_OK;
 }
 
+int gba_point_inverses(const GbaDev& D, double lambda, hipStream_t st) {
+    if (D.np) VIORB_LAUNCH(k_gba_dinv, gba_blocks(D.np, 256), 256, 0, st, D, lambda);
+    return VIORB_OK;
+}
+int gba_mark_included(const GbaDev& D, hipStream_t st) {
+    if (D.ne) VIORB_LAUNCH(k_gba_included, gba_blocks(D.ne, 256), 256, 0, st, D);
+    return VIORB_OK;
+}
+
+namespace {
+int gba_setup(const GbaDev& D, hipStream_t st) {
+    VIORB_LAUNCH(k_gba_setup, 1, 256, 0, st, D);
+    return VIORB_OK;
+}
 int gba_errors(const GbaDev& D, hipStream_t st) {
     if (D.ne) VIORB_LAUNCH(k_gba_errors, gba_blocks(D.ne, 256), 256, 0, st, D);
     VIORB_LAUNCH(k_gba_imu_errors, gba_blocks(D.nk, 256), 256, 0, st, D);
@@ -616,27 +583,42 @@ int gba_linearise(const GbaDev& D, hipStream_t st) {
     VIORB_LAUNCH(k_gba_imu, D.nk, 64, 0, st, D);
     return VIORB_OK;
 }
+int gba_reduce(const GbaDev& D, double lambda, hipStream_t st) {
+    VIORB_TRY(gba_point_inverses(D, lambda, st));
+    VIORB_LAUNCH(k_gba_init_reduced, D.nk + gba_blocks(D.ld, 256), 256, 0, st, D, lambda);
+    if (D.np && D.ne) VIORB_LAUNCH(k_gba_schur, D.np, 64, 0, st, D);
+    return VIORB_OK;
+}
+int gba_step(const GbaDev& D, double lambda, hipStream_t st) {
+    if (D.np) VIORB_LAUNCH(k_gba_backsub, gba_blocks(D.np, 256), 256, 0, st, D);
+    VIORB_LAUNCH(k_gba_update, gba_blocks(std::max(D.nk, D.np), 256), 256, 0, st, D, lambda);
+    return VIORB_OK;
+}
+const GbaOps g_gba_navstate_ops = {GBA_MAX_FREE_KF, gba_setup, gba_errors, gba_linearise, gba_reduce, gba_step};
+void gba_navstate_shape(GbaDev& D, int nk, int np, int ne) { D.nk = nk; D.np = np; D.ne = ne; D.blk = 12; D.kf_w = 22; D.obs_w = 3; D.rows = 2; }
+} // namespace
 
 // The solve proper on device-resident inputs. `pinned`: 16 page-locked doubles. kf / pt (the working states) are kfs_out / points_out.
-int gba_run(const viorb_gba_config* cfg, GbaDev& D, void* workspace, size_t workspace_bytes, const volatile int* stop, double* pinned,
-            double info[6], hipStream_t st) {
+int gba_run(const viorb_gba_config* cfg, GbaDev& D, const GbaOps& ops, void* workspace, size_t workspace_bytes, const volatile int* stop,
+            double* pinned, double info[6], hipStream_t st) {
     size_t clear_bytes = 0;
-    const size_t head = gba_layout(D, workspace, D.nk, D.np, D.ne, -1, &clear_bytes);
+    const size_t head = gba_layout(D, workspace, -1, &clear_bytes);
     if (head > workspace_bytes) { set_error("global BA: workspace of %zu bytes, %zu needed", workspace_bytes, head); return VIORB_ERR_CAPACITY; }
     VIORB_HIP_TRY(hipMemsetAsync(workspace, 0, clear_bytes, st));
-    VIORB_LAUNCH(k_gba_setup, 1, 256, 0, st, D);
+    VIORB_TRY(ops.setup(D, st));
     if (D.ne) VIORB_LAUNCH(k_gba_edges_scan, gba_blocks(D.ne, 256), 256, 0, st, D);
     VIORB_HIP_TRY(hipMemcpyAsync(pinned, D.status, GBA_ST_N * sizeof(int), hipMemcpyDeviceToHost, st));
     VIORB_HIP_TRY(hipStreamSynchronize(st));
     const int* hst = reinterpret_cast<const int*>(pinned);
     if (hst[GBA_ST_INVALID]) {
-        set_error("invalid argument: global BA graph (%s%s%s%s)", (hst[GBA_ST_INVALID] & 1) ? " prev[i] >= i" : "", (hst[GBA_ST_INVALID] & 2) ? " edge index out of range or edges not sorted by point" : "",
-                  (hst[GBA_ST_INVALID] & 4) ? " singular pre-integration covariance" : "", (hst[GBA_ST_INVALID] & 8) ? " invSigma2 <= 0" : "");
+        const int bad = hst[GBA_ST_INVALID];
+        set_error("invalid argument: global BA graph (%s%s%s%s%s)", (bad & GBA_BAD_PREV) ? " prev[i] >= i" : "", (bad & GBA_BAD_EDGE) ? " edge index out of range or edges not sorted by point" : "",
+                  (bad & GBA_BAD_COV) ? " singular pre-integration covariance" : "", (bad & GBA_BAD_SIGMA) ? " invSigma2 <= 0" : "", (bad & GBA_BAD_BF) ? " stereo edge with bf <= 0" : "");
         return VIORB_ERR_INVALID_ARG;
     }
-    D.nfree = hst[GBA_ST_NFREE]; D.n = 12 * D.nfree; D.ld = gba_ld(D.n);
-    if (D.nfree > GBA_MAX_FREE_KF) { set_error("global BA: %d free key frames, at most %d", D.nfree, GBA_MAX_FREE_KF); return VIORB_ERR_CAPACITY; }
-    const size_t total = gba_layout(D, workspace, D.nk, D.np, D.ne, D.nfree, nullptr);
+    D.nfree = hst[GBA_ST_NFREE]; D.n = D.blk * D.nfree; D.ld = gba_ld(D.n);
+    if (D.nfree > ops.max_free) { set_error("global BA: %d free key frames, at most %d", D.nfree, ops.max_free); return VIORB_ERR_CAPACITY; }
+    const size_t total = gba_layout(D, workspace, D.nfree, nullptr);
     if (total > workspace_bytes) { set_error("global BA: workspace of %zu bytes, %zu needed", workspace_bytes, total); return VIORB_ERR_CAPACITY; }
     if (D.ne) {
         VIORB_LAUNCH(k_gba_kf_offsets, 1, 64, 0, st, D);
@@ -651,43 +633,40 @@ int gba_run(const viorb_gba_config* cfg, GbaDev& D, void* workspace, size_t work
         return VIORB_OK;
     };
     const size_t S_bytes = (size_t)D.ld * D.ld * sizeof(double);
-    VIORB_TRY(gba_errors(D, st));
-    VIORB_TRY(gba_linearise(D, st));
+    VIORB_TRY(ops.errors(D, st));
+    VIORB_TRY(ops.linearise(D, st));
     VIORB_LAUNCH(k_gba_max_diag, gba_blocks((size_t)D.n + 3 * (size_t)D.np, 256 * 8), 256, 0, st, D);
     if (int rc = read_scal()) return rc;
     gba_lm L; L.cur = pinned[GBA_S_CHI]; L.lambda = 1e-5 * pinned[GBA_S_MAXDIAG]; L.ni = 2;
     const double chi_before = L.cur;
     int its = 0, trials = 0, nfail = 0, nbad = 0;
-    g_gba_trials.clear();
+    gba_trials().clear();
     bool stale = false;
     for (int it = 0; it < cfg->iterations && !stopped(); it++) {
         if (it > 0) {                                      // err[] is that of the accepted trial = the current state
-            if (stale) { VIORB_TRY(gba_errors(D, st)); stale = false; }   // unless the last trial was rejected and restored
-            VIORB_TRY(gba_linearise(D, st));
+            if (stale) { VIORB_TRY(ops.errors(D, st)); stale = false; }   // unless the last trial was rejected and restored
+            VIORB_TRY(ops.linearise(D, st));
         }
         const double ini = L.cur;
-        VIORB_HIP_TRY(hipMemcpyAsync(D.kf_bak, D.kf, (size_t)D.nk * 22 * sizeof(double), hipMemcpyDeviceToDevice, st));
+        VIORB_HIP_TRY(hipMemcpyAsync(D.kf_bak, D.kf, (size_t)D.nk * D.kf_w * sizeof(double), hipMemcpyDeviceToDevice, st));
         if (D.np) VIORB_HIP_TRY(hipMemcpyAsync(D.pt_bak, D.pt, (size_t)D.np * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
         double rho = 0; int qmax = 0;
         do {
             VIORB_HIP_TRY(hipMemsetAsync(D.scal, 0, 3 * sizeof(double), st));
             VIORB_HIP_TRY(hipMemsetAsync(D.S, 0, S_bytes, st));
-            if (D.np) VIORB_LAUNCH(k_gba_dinv, gba_blocks(D.np, 256), 256, 0, st, D, L.lambda);
-            VIORB_LAUNCH(k_gba_init_reduced, D.nk + gba_blocks(D.ld, 256), 256, 0, st, D, L.lambda);
-            if (D.np && D.ne) VIORB_LAUNCH(k_gba_schur, D.np, 64, 0, st, D);
+            VIORB_TRY(ops.reduce(D, L.lambda, st));
             VIORB_TRY(gba_factor_solve(D, st, true));
-            if (D.np) VIORB_LAUNCH(k_gba_backsub, gba_blocks(D.np, 256), 256, 0, st, D);
-            VIORB_LAUNCH(k_gba_update, gba_blocks(std::max(D.nk, D.np), 256), 256, 0, st, D, L.lambda);
-            VIORB_TRY(gba_errors(D, st));
+            VIORB_TRY(ops.step(D, L.lambda, st));
+            VIORB_TRY(ops.errors(D, st));
             if (int rc = read_scal()) return rc;
             const bool ok = pinned[GBA_S_FAIL] == 0.0;
             if (!ok) nfail++;
             bool accepted;
             rho = gba_lm_trial(L, ok ? pinned[GBA_S_CHI] : DBL_MAX, ok ? pinned[GBA_S_SCALE] : 0.0, &accepted);
             stale = !accepted;
-            g_gba_trials.push_back(accepted ? 1 : 0);
+            gba_trials().push_back(accepted ? 1 : 0);
             if (!accepted) {
-                VIORB_HIP_TRY(hipMemcpyAsync(D.kf, D.kf_bak, (size_t)D.nk * 22 * sizeof(double), hipMemcpyDeviceToDevice, st));
+                VIORB_HIP_TRY(hipMemcpyAsync(D.kf, D.kf_bak, (size_t)D.nk * D.kf_w * sizeof(double), hipMemcpyDeviceToDevice, st));
                 if (D.np) VIORB_HIP_TRY(hipMemcpyAsync(D.pt, D.pt_bak, (size_t)D.np * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
             }
             qmax++; trials++;
@@ -707,7 +686,6 @@ int gba_check_config(const viorb_gba_config* cfg, int nk, int np, int ne) {
     VIORB_REQUIRE(nk >= 1 && np >= 0 && ne >= 0, "nk >= 1, np >= 0, ne >= 0");
     return VIORB_OK;
 }
-} // namespace
 } // namespace viorb
 
 using namespace viorb;
@@ -715,7 +693,8 @@ using namespace viorb;
 extern "C" size_t viorb_global_ba_navstate_workspace_bytes(int nk, int np, int ne) {
     if (nk < 1 || np < 0 || ne < 0) return 0;
     GbaDev D{};
-    return gba_layout(D, nullptr, nk, np, ne, std::min(nk, GBA_MAX_FREE_KF), nullptr);
+    gba_navstate_shape(D, nk, np, ne);
+    return gba_layout(D, nullptr, std::min(nk, GBA_MAX_FREE_KF), nullptr);
 }
 
 extern "C" int viorb_global_ba_navstate_device(const viorb_gba_config* cfg, const double* kfs, int nk, const int32_t* prev, const uint8_t* fixed,
@@ -729,23 +708,23 @@ extern "C" int viorb_global_ba_navstate_device(const viorb_gba_config* cfg, cons
     VIORB_TRY(require_device());
     hipStream_t st = (hipStream_t)stream;
     for (int k = 0; k < 6; k++) info[k] = 0;
-    g_gba_trials.clear();
+    gba_trials().clear();
     VIORB_HIP_TRY(hipMemcpyAsync(kfs_out, kfs, (size_t)nk * 22 * sizeof(double), hipMemcpyDeviceToDevice, st));
     if (np) VIORB_HIP_TRY(hipMemcpyAsync(points_out, points, (size_t)np * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
     GbaDev D{};
-    D.nk = nk; D.np = np; D.ne = ne; D.nfree = 0; D.n = 0; D.ld = GBA_NB; D.robust = cfg->robust;
+    gba_navstate_shape(D, nk, np, ne); D.nfree = 0; D.n = 0; D.ld = GBA_NB; D.robust = cfg->robust;
     D.kf = kfs_out; D.pt = points_out; D.prev = prev; D.fixed = fixed; D.e_idx = edge_idx; D.e_obs = edge_obs; D.preint = preint; D.included = point_included;
     for (int k = 0; k < 16; k++) D.cam[k] = cam[k];
     for (int k = 0; k < 3; k++) D.gw[k] = gw[k];
     if (stop && *stop) {                     // the reference's optimize() returns before its first iteration: everything stays
         if (np) VIORB_HIP_TRY(hipMemsetAsync(point_included, 0, np, st));
-        if (ne) hipLaunchKernelGGL(k_gba_included, dim3((ne + 255) / 256), dim3(256), 0, st, D);
+        VIORB_TRY(gba_mark_included(D, st));
         VIORB_HIP_TRY(hipStreamSynchronize(st));
         return VIORB_OK;
     }
     double* pinned = nullptr;
     VIORB_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&pinned), 16 * sizeof(double)));
-    const int rc = gba_run(cfg, D, workspace, workspace_bytes, stop, pinned, info, st);
+    const int rc = gba_run(cfg, D, g_gba_navstate_ops, workspace, workspace_bytes, stop, pinned, info, st);
     const hipError_t e = hipStreamSynchronize(st);
     (void)hipHostFree(pinned);
     if (rc == VIORB_OK && e != hipSuccess) { set_error("global BA: %s", hipGetErrorString(e)); return VIORB_ERR_HIP; }
@@ -768,7 +747,7 @@ extern "C" int viorb_global_ba_navstate(const viorb_gba_config* cfg, const doubl
     for (int i = 0; i < nk; i++) if (prev[i] >= 0) { double inv[81]; VIORB_REQUIRE(gba_inverse9(preint + (size_t)i * 142 + 60, inv), "singular pre-integration covariance"); }
     if (nfree > GBA_MAX_FREE_KF) { set_error("global BA: %d free key frames, at most %d", nfree, GBA_MAX_FREE_KF); return VIORB_ERR_CAPACITY; }
     for (int k = 0; k < 6; k++) info[k] = 0;
-    g_gba_trials.clear();
+    gba_trials().clear();
     if (stop && *stop) {
         memcpy(kfs_out, kfs, (size_t)nk * 22 * sizeof(double));
         if (np) { memcpy(points_out, points, (size_t)np * 3 * sizeof(double)); memset(point_included, 0, np); }
@@ -790,7 +769,8 @@ extern "C" int viorb_global_ba_navstate(const viorb_gba_config* cfg, const doubl
     };
     lay(in);
     const size_t in_bytes = in.end();
-    const size_t ws_bytes = gba_layout(D, nullptr, nk, np, ne, nfree, nullptr);
+    gba_navstate_shape(D, nk, np, ne);
+    const size_t ws_bytes = gba_layout(D, nullptr, nfree, nullptr);
     if (!lease.reserve(in_bytes + ws_bytes)) { set_error("global BA: hipMalloc of %zu bytes failed", in_bytes + ws_bytes); return VIORB_ERR_HIP; }
     WorkspaceLayout at(lease.c->arena);
     lay(at);
@@ -805,11 +785,11 @@ extern "C" int viorb_global_ba_navstate(const viorb_gba_config* cfg, const doubl
         VIORB_HIP_TRY(hipMemcpyAsync(d_obs, edge_obs, (size_t)ne * 3 * sizeof(double), hipMemcpyHostToDevice, st));
     }
     if (np) VIORB_HIP_TRY(hipMemsetAsync(d_inc, 0, np, st));
-    D.nk = nk; D.np = np; D.ne = ne; D.nfree = 0; D.n = 0; D.ld = GBA_NB; D.robust = cfg->robust;
+    gba_navstate_shape(D, nk, np, ne); D.nfree = 0; D.n = 0; D.ld = GBA_NB; D.robust = cfg->robust;
     D.kf = d_kf; D.pt = d_pt; D.prev = d_prev; D.fixed = d_fixed; D.e_idx = d_eidx; D.e_obs = d_obs; D.preint = d_preint; D.included = d_inc;
     for (int k = 0; k < 16; k++) D.cam[k] = cam[k];
     for (int k = 0; k < 3; k++) D.gw[k] = gw[k];
-    const int rc = gba_run(cfg, D, ws, ws_bytes, stop, lease.c->pinned, info, st);
+    const int rc = gba_run(cfg, D, g_gba_navstate_ops, ws, ws_bytes, stop, lease.c->pinned, info, st);
     if (rc != VIORB_OK) return rc;
     VIORB_HIP_TRY(hipMemcpyAsync(kfs_out, d_kf, (size_t)nk * 22 * sizeof(double), hipMemcpyDeviceToHost, st));
     if (np) {
@@ -850,7 +830,7 @@ extern "C" int viorb_debug_gba_cholesky(const double* A, int n, double* L, int32
 // number (at most cap are written).
 extern "C" int viorb_debug_gba_last_trials(uint8_t* accepted, int cap, int* n) {
     VIORB_REQUIRE(n && cap >= 0 && (cap == 0 || accepted), "accepted[cap], n");
-    *n = (int)g_gba_trials.size();
-    for (int k = 0; k < *n && k < cap; k++) accepted[k] = g_gba_trials[k];
+    *n = (int)gba_trials().size();
+    for (int k = 0; k < *n && k < cap; k++) accepted[k] = gba_trials()[k];
     return VIORB_OK;
 }

@@ -1,4 +1,5 @@
-"""Global bundle adjustment with NavState IMU edges (Optimizer::GlobalBundleAdjustmentNavState) through the C ABI of include/viorb.h.
+"""Global bundle adjustment with NavState IMU edges (Optimizer::GlobalBundleAdjustmentNavState) and the vision-only one over SE3 poses
+(Optimizer::BundleAdjustment, GlobalBundleAdjustmentSE3 below) through the C ABI of include/viorb.h.
 A problem is what synth.make_global_ba_problem returns: kfs [N,22] in an order with prev[i] < i, prev [N], fixed [N], preint [N,142]
 (row i = the interval ending at key frame i), points [P,3], edge_idx [E,2] = (point, key frame) sorted by point, edge_obs [E,3] = u v
 invSigma2, gw [3], cam [16]."""
@@ -63,6 +64,52 @@ def GlobalBundleAdjustmentNavStateDevice(kfs, prev, fixed, preint, points, edge_
                                                 len(points), ptr(t["ei"]), ptr(t["eo"]), len(ei), ptr(_f64(gw)), ptr(_f64(cam)),
                                                 ptr(stop) if stop is not None else None, ptr(ko), ptr(po), ptr(inc), ptr(info), ptr(ws), nbytes, None))
     return _result(ko.cpu().numpy(), po.cpu().numpy()[:len(points)], inc.cpu().numpy()[:len(points)], info)
+
+
+def gba_se3_workspace_bytes(nk, n_points, n_edges):
+    return int(lib().viorb_global_ba_se3_workspace_bytes(nk, n_points, n_edges))
+
+
+def GlobalBundleAdjustmentSE3(kfs, fixed, points, edge_idx, edge_obs, intr5, iterations=10, robust=False, stop=None):
+    """viorb_global_ba_se3 (Optimizer::BundleAdjustment): host buffers in and out. kfs [N,7] = qx qy qz qw tx ty tz of Tcw, fixed [N],
+    points [P,3], edge_idx [E,2] = (point, key frame) sorted by point, edge_obs [E,4] = u v uRight (< 0: monocular) invSigma2, intr5 = fx
+    fy cx cy bf. stop as GlobalBundleAdjustmentNavState. Returns the same result dictionary."""
+    kfs = _f64(kfs).reshape(-1, 7); points = _f64(points).reshape(-1, 3)
+    ei = _i32(edge_idx).reshape(-1, 2); eo = _f64(edge_obs).reshape(-1, 4)
+    fixed = np.ascontiguousarray(fixed, np.uint8)
+    assert len(fixed) == len(kfs) and len(ei) == len(eo)
+    ko, po, inc, info = np.zeros_like(kfs), np.zeros_like(points), np.zeros(max(len(points), 1), np.uint8), np.zeros(6)
+    cfg = capi.GbaConfig(int(iterations), int(bool(robust)))
+    check(lib().viorb_global_ba_se3(C.byref(cfg), ptr(kfs), len(kfs), ptr(fixed), ptr(points), len(points), ptr(ei), ptr(eo), len(ei),
+                                    ptr(_f64(intr5)), ptr(stop) if stop is not None else None, ptr(ko), ptr(po), ptr(inc), ptr(info)))
+    return _result(ko, po, inc[:len(points)], info)
+
+
+def GlobalBundleAdjustmentSE3Device(kfs, fixed, points, edge_idx, edge_obs, intr5, iterations=10, robust=False, stop=None):
+    """viorb_global_ba_se3_device: the arrays are uploaded here as torch tensors on cuda:0; the results come back as numpy arrays."""
+    import torch
+    dev = torch.device("cuda", 0)
+    kfs = _f64(kfs).reshape(-1, 7); points = _f64(points).reshape(-1, 3); ei = _i32(edge_idx).reshape(-1, 2)
+    t = dict(kfs=up(kfs), fixed=up(np.ascontiguousarray(fixed, np.uint8)), points=up(points if len(points) else np.zeros((1, 3))),
+             ei=up(ei if len(ei) else np.zeros((1, 2), np.int32)), eo=up(_f64(edge_obs).reshape(-1, 4) if len(ei) else np.zeros((1, 4))))
+    ko, po = torch.zeros_like(t["kfs"]), torch.zeros_like(t["points"])
+    inc = torch.zeros(max(len(points), 1), dtype=torch.uint8, device=dev)
+    nbytes = gba_se3_workspace_bytes(len(kfs), len(points), len(ei))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    info = np.zeros(6)
+    cfg = capi.GbaConfig(int(iterations), int(bool(robust)))
+    torch.cuda.synchronize()
+    check(lib().viorb_global_ba_se3_device(C.byref(cfg), ptr(t["kfs"]), len(kfs), ptr(t["fixed"]), ptr(t["points"]), len(points), ptr(t["ei"]), ptr(t["eo"]),
+                                           len(ei), ptr(_f64(intr5)), ptr(stop) if stop is not None else None, ptr(ko), ptr(po), ptr(inc), ptr(info),
+                                           ptr(ws), nbytes, None))
+    return _result(ko.cpu().numpy(), po.cpu().numpy()[:len(points)], inc.cpu().numpy()[:len(points)], info)
+
+
+def debug_se3_edge(kf7, pt3, obs4, intr5):
+    """viorb_debug_gba_se3_edge (no device): (dimension, e [3], Jp [3,3], Jk [3,6]) of one edge."""
+    e, Jp, Jk = np.zeros(3), np.zeros((3, 3)), np.zeros((3, 6))
+    dim = lib().viorb_debug_gba_se3_edge(ptr(_f64(kf7)), ptr(_f64(pt3)), ptr(_f64(obs4)), ptr(_f64(intr5)), ptr(e), ptr(Jp), ptr(Jk))
+    return dim, e, Jp, Jk
 
 
 def debug_cholesky(A):

@@ -9,6 +9,9 @@
 //   local_bundle_adjustment           Optimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap, pLM) src/Optimizer.cc:3980-4311 -> viorb_local_ba_se3
 //   global_bundle_adjustment_navstate Optimizer::GlobalBundleAdjustmentNavState(pMap, gw, nIterations, pbStopFlag, nLoopKF, bRobust)
 //                                                                                                 src/Optimizer.cc:50-320     -> viorb_global_ba_navstate
+//   bundle_adjustment                 Optimizer::BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust)
+//   global_bundle_adjustment          Optimizer::GlobalBundleAdjustemnt(pMap, nIterations, pbStopFlag, nLoopKF, bRobust)
+//                                                                                                 src/Optimizer.cc:3551-3747  -> viorb_global_ba_se3
 //
 // The window solves take `stop_mirror`: the reference's pbStopFlag is a bool*, the C ABI polls a `const volatile int*` — an int that
 // LocalMapping::InterruptBA sets next to mbAbortBA (one line there). A failure of the GPU library throws (viorb_shim::check).
@@ -297,6 +300,78 @@ inline void global_bundle_adjustment_navstate(MapT* pMap, const double gw[3], in
         if (nLoopKF == 0) { pts_v[p]->SetWorldPos(Pw); pts_v[p]->UpdateNormalAndDepth(); }
         else { pts_v[p]->mPosGBA = Pw; pts_v[p]->mnBAGlobalForKF = nLoopKF; }
     }
+}
+
+// Optimizer::BundleAdjustment (vision only): every good key frame of vpKFs as an SE3 pose and every good map point of vpMP in one solve.
+// mnId == 0 is fixed (:3589). Observations in bad key frames or with mnId > maxKFid are skipped (:3619); mvuRight < 0 gives the
+// monocular edge, otherwise the stereo edge (:3626); an observer that has no vertex (a good key frame missing from vpKFs) throws. A
+// point left without an edge is not written back (:3685-3693, :3725). nLoopKF == 0 stores the result in the key frames and points
+// (SetPose; SetWorldPos + UpdateNormalAndDepth), otherwise in mTcwGBA / mPosGBA / mnBAGlobalForKF (:3702-3745). Returns info[6] of the C
+// ABI through `info` when it is not NULL. pose_to_qt / qt_to_pose / stop_mirror as in local_bundle_adjustment.
+template <class KeyFrameT, class MapPointT, class PoseToQt, class QtToPose>
+inline void bundle_adjustment(const std::vector<KeyFrameT*>& vpKFs, const std::vector<MapPointT*>& vpMP, int nIterations, bool* pbStopFlag,
+                              const volatile int* stop_mirror, const unsigned long nLoopKF, const bool bRobust, PoseToQt pose_to_qt,
+                              QtToPose qt_to_pose, double* info = 0) {
+    std::vector<KeyFrameT*> kfs_v;
+    for (size_t i = 0; i < vpKFs.size(); i++) if (!vpKFs[i]->isBad()) kfs_v.push_back(vpKFs[i]);
+    if (kfs_v.empty()) return;
+    const int nk = (int)kfs_v.size();
+    unsigned long maxKFid = 0;
+    std::map<const KeyFrameT*, int> kf_index;
+    std::vector<double> kfs((size_t)nk * 7); std::vector<unsigned char> fixed(nk, 0);
+    for (int k = 0; k < nk; k++) {
+        kf_index[kfs_v[k]] = k;
+        pose_to_qt(kfs_v[k]->GetPose(), &kfs[(size_t)k * 7]);
+        fixed[k] = kfs_v[k]->mnId == 0;
+        if (kfs_v[k]->mnId > maxKFid) maxKFid = kfs_v[k]->mnId;
+    }
+    std::vector<MapPointT*> pts_v;
+    for (size_t i = 0; i < vpMP.size(); i++) if (!vpMP[i]->isBad()) pts_v.push_back(vpMP[i]);
+    const int np = (int)pts_v.size();
+    std::vector<double> points((size_t)(np + 1) * 3), edge_obs; std::vector<int32_t> edge_idx;
+    for (int p = 0; p < np; p++) {
+        const cv::Mat Pw = pts_v[p]->GetWorldPos();
+        for (int c = 0; c < 3; c++) points[(size_t)p * 3 + c] = Pw.template at<float>(c);
+        const auto observations = pts_v[p]->GetObservations();
+        for (auto mit = observations.begin(); mit != observations.end(); ++mit) {
+            KeyFrameT* pKFi = mit->first;
+            if (pKFi->isBad() || pKFi->mnId > maxKFid) continue;
+            // the reference looks the vertex up by id; a good observer that vpKFs does not hold has none
+            typename std::map<const KeyFrameT*, int>::const_iterator kit = kf_index.find(pKFi);
+            if (kit == kf_index.end()) throw std::runtime_error("BundleAdjustment: an observing key frame is not among the key frames");
+            const cv::KeyPoint& kpUn = pKFi->mvKeysUn[mit->second];
+            edge_idx.push_back(p); edge_idx.push_back(kit->second);
+            edge_obs.push_back(kpUn.pt.x); edge_obs.push_back(kpUn.pt.y); edge_obs.push_back(pKFi->mvuRight[mit->second]);      // < 0: mono edge
+            edge_obs.push_back(pKFi->mvInvLevelSigma2[kpUn.octave]);
+        }
+    }
+    (void)pbStopFlag;                                                      // read through its int mirror (setForceStopFlag, :3575-3576)
+    const int ne = (int)(edge_idx.size() / 2);
+    const double intr5[5] = {kfs_v[0]->fx, kfs_v[0]->fy, kfs_v[0]->cx, kfs_v[0]->cy, kfs_v[0]->mbf};
+    std::vector<double> kfs_out((size_t)nk * 7), points_out((size_t)(np + 1) * 3); std::vector<unsigned char> included(np + 1); double info_[6];
+    viorb_gba_config cfg; cfg.iterations = nIterations; cfg.robust = bRobust ? 1 : 0;
+    check(viorb_global_ba_se3(&cfg, &kfs[0], nk, &fixed[0], &points[0], np, ne ? &edge_idx[0] : 0, ne ? &edge_obs[0] : 0, ne, intr5, stop_mirror,
+                              &kfs_out[0], &points_out[0], &included[0], info_), "BundleAdjustment");
+    if (info) for (int k = 0; k < 6; k++) info[k] = info_[k];
+    for (int k = 0; k < nk; k++) {                                          // (:3702-3720)
+        if (nLoopKF == 0) { kfs_v[k]->SetPose(qt_to_pose(&kfs_out[(size_t)k * 7])); continue; }
+        kfs_v[k]->mTcwGBA = qt_to_pose(&kfs_out[(size_t)k * 7]);
+        kfs_v[k]->mnBAGlobalForKF = nLoopKF;
+    }
+    for (int p = 0; p < np; p++) {                                          // (:3722-3745)
+        if (!included[p]) continue;
+        cv::Mat Pw(3, 1, CV_32F);
+        for (int c = 0; c < 3; c++) Pw.template at<float>(c) = (float)points_out[(size_t)p * 3 + c];
+        if (nLoopKF == 0) { pts_v[p]->SetWorldPos(Pw); pts_v[p]->UpdateNormalAndDepth(); }
+        else { pts_v[p]->mPosGBA = Pw; pts_v[p]->mnBAGlobalForKF = nLoopKF; }
+    }
+}
+
+// Optimizer::GlobalBundleAdjustemnt: the whole map through bundle_adjustment (:3551-3556)
+template <class MapT, class PoseToQt, class QtToPose>
+inline void global_bundle_adjustment(MapT* pMap, int nIterations, bool* pbStopFlag, const volatile int* stop_mirror, const unsigned long nLoopKF,
+                                     const bool bRobust, PoseToQt pose_to_qt, QtToPose qt_to_pose, double* info = 0) {
+    bundle_adjustment(pMap->GetAllKeyFrames(), pMap->GetAllMapPoints(), nIterations, pbStopFlag, stop_mirror, nLoopKF, bRobust, pose_to_qt, qt_to_pose, info);
 }
 
 } // namespace viorb_shim

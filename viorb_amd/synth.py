@@ -921,6 +921,74 @@ def make_global_ba_problem(seed, N=21, n_points=None, revisit_frac=0.0, n_fixed=
                 gw=GRAVITY_CAM_WORLD.copy(), cam=cam, stream=stream, bias=(bg, ba))
 
 
+def make_global_ba_se3_problem(seed, N=12, stereo_frac=0.5, revisit_frac=0.0, n_fixed=1, n_points=None, outlier_frac=0.03, pix_sigma=1.5,
+                               step=0.3, w=1241, h=376):
+    """A vision-only Optimizer::BundleAdjustment problem (KITTI-shaped camera, as make_local_ba_se3_problem): N chronological key frames
+    creeping forward (`step` metres apart, so that a point stays in front of many of them), the first n_fixed fixed; n_points points
+    (default 30 per key frame), each seen by a contiguous run of 3..7 key frames (about 5); a revisit_frac share of them is seen again by
+    a distant run (loop re-observations, kept where the point still projects in front of the camera), so that the reduced matrix is not
+    banded. stereo_frac of the observations closer than 35 m carry uRight; outlier_frac of them are gross outliers. The start values
+    (perturbed poses, noisy points) are rounded through float, as a map holds them. Returns flat arrays in the layouts of
+    include/viorb.h (kfs [N,7] = qx qy qz qw tx ty tz of Tcw, edge_obs [E,4] = u v uRight invSigma2, intr5) + the truth. numpy / scipy only."""
+    from scipy.spatial.transform import Rotation
+    rng = np.random.Generator(np.random.PCG64(seed + 515151))
+    fx = fy = 718.856; cx, cy, bf = 607.1928, 185.2157, 386.1448
+    n_points = 30 * N if n_points is None else n_points
+    poses, p, yaw = [], np.zeros(3), 0.0
+    for k in range(N):
+        Rwc = Rotation.from_euler("y", yaw).as_matrix() @ _rotvec_to_R(rng.normal(0, 0.01, 3))
+        poses.append((Rwc.T, -Rwc.T @ p))                                     # Tcw
+        p = p + Rwc @ np.array([rng.normal(0, 0.03), rng.normal(0, 0.02), step + rng.normal(0, 0.03)]); yaw += rng.normal(0, 0.01)
+    sf = np.float32(1.2) ** np.arange(8)
+    pts, ei, eo = [], [], []
+
+    def observe(pid, X, ks):
+        n = 0
+        for k in ks:
+            Pc = poses[k][0] @ X + poses[k][1]
+            if Pc[2] < 1.0: continue
+            u, v = fx * Pc[0] / Pc[2] + cx, fy * Pc[1] / Pc[2] + cy
+            if not (-0.5 * w < u < 1.5 * w and -0.5 * h < v < 1.5 * h): continue
+            octv = int(rng.integers(0, 8)); sg = pix_sigma * float(sf[octv]) / 1.5
+            ou, ov = u + rng.normal(0, sg), v + rng.normal(0, sg)
+            stereo = rng.random() < stereo_frac and Pc[2] < 35 and u - bf / Pc[2] > 30      # uRight stays positive under the noise
+            our = (u - bf / Pc[2] + rng.normal(0, sg)) if stereo else -1.0
+            if rng.random() < outlier_frac: ou += rng.choice([-1, 1]) * rng.uniform(12, 25)
+            ei.append((pid, k)); eo.append((np.float32(ou), np.float32(ov), np.float32(our) if stereo else -1.0, 1.0 / float(np.float32(sf[octv]) ** 2)))
+            n += 1
+        return n
+    while len(pts) < n_points:
+        run = int(min(N, rng.integers(3, 8))); k0 = int(rng.integers(0, N - run + 1))
+        Rcw, tcw = poses[k0 + run // 2]
+        z = rng.uniform(6, 40)
+        X = Rcw.T @ (np.array([(rng.uniform(20, w - 20) - cx) / fx * z, (rng.uniform(20, h - 20) - cy) / fy * z, z]) - tcw)
+        ks = list(range(k0, k0 + run))
+        if rng.random() < revisit_frac and N > 2 * run + 8:
+            run2 = int(rng.integers(3, 8)); far = [k for k in range(0, N - run2 + 1) if k + run2 <= k0 - 8 or k >= k0 + run + 8]
+            if far:
+                k2 = int(far[int(rng.integers(0, len(far)))]); ks = sorted(ks + list(range(k2, k2 + run2)))
+        m0 = len(ei)
+        if observe(len(pts), X, ks) < 2:
+            del ei[m0:], eo[m0:]
+            continue
+        pts.append(X)
+    pts = np.array(pts).reshape(-1, 3)
+
+    def to7(R, t):
+        q = Rotation.from_matrix(R).as_quat(); q = q if q[3] >= 0 else -q
+        return np.concatenate([q, t])
+    kfs_true = np.stack([to7(R, t) for R, t in poses])
+    kfs = kfs_true.copy()
+    for i in range(N):
+        R, t = poses[i]
+        if i >= n_fixed:
+            R, t = _rotvec_to_R(rng.normal(0, 0.01, 3)) @ R, t + rng.normal(0, 0.05, 3)
+        kfs[i] = to7(np.float32(R).astype(np.float64), np.float32(t).astype(np.float64))     # KeyFrame::Tcw is a float matrix
+    fixed = np.zeros(N, np.uint8); fixed[:n_fixed] = 1
+    return dict(kfs=kfs, kfs_true=kfs_true, fixed=fixed, points=np.float32(pts + rng.normal(0, 0.1, pts.shape)).astype(np.float64), points_true=pts,
+                edge_idx=np.array(ei, np.int32).reshape(-1, 2), edge_obs=np.array(eo, np.float64).reshape(-1, 4), intr5=np.array([fx, fy, cx, cy, bf]))
+
+
 def _l1_normalised(words, weights):
     """Ascending unique words and their summed weights divided by the norm, the norm summed in ascending word order (BowVector::normalize)."""
     acc = {}
