@@ -11,3 +11,4 @@ from .mapping import TriangulatePairs, TriangulatePairsBatch, MapPointUpdate, Cr
 from .vi_init import PreintegrateIntervals, PreintegrateIntervalsBatch, OptimizeInitialGyroBias, ViInit, ViInitHost, ViInitApplyHost, vi_config, unpack_est  # noqa: F401
 from .global_ba import GlobalBundleAdjustmentNavState, GlobalBundleAdjustmentNavStateDevice, gba_workspace_bytes, GlobalBundleAdjustmentSE3, GlobalBundleAdjustmentSE3Device, gba_se3_workspace_bytes  # noqa: F401
 from .place import BowVector, BowVector_device, BowScore, BowScorePairs, KeyFrameDatabase, pack_bows  # noqa: F401
+from .two_view import TwoViewInit, TwoViewBatch, draw_sets, two_view_config  # noqa: F401

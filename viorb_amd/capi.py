@@ -1,6 +1,6 @@
-"""ctypes declarations of include/viorb.h and of the header it includes, viorb_global_ba_se3.h (kept 1:1; tests/test_host_hooks.py checks that every
+"""ctypes declarations of include/viorb.h and of the headers it includes, viorb_global_ba_se3.h and viorb_two_view.h (kept 1:1; tests/test_host_hooks.py checks that every
 declared entry point of viorb.h is exported, has a signature here and that the argument counts agree; tests/test_global_ba_se3_ref.py
-does the same for SIGNATURES_GLOBAL_BA_SE3)."""
+does the same for SIGNATURES_GLOBAL_BA_SE3, tests/test_two_view_ref.py for SIGNATURES_TWO_VIEW)."""
 import ctypes as C
 import os
 import numpy as np
@@ -71,6 +71,21 @@ class ViInitConfig(C.Structure):
 class GbaConfig(C.Structure):
     """viorb_gba_config (include/viorb.h)."""
     _fields_ = [("iterations", C.c_int32), ("robust", C.c_int32)]
+
+
+class TwoViewConfig(C.Structure):
+    """viorb_two_view_config (include/viorb_two_view.h)."""
+    _fields_ = [("sigma", C.c_float), ("iterations", C.c_int32), ("min_parallax_deg", C.c_float), ("min_triangulated", C.c_int32),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float)]
+
+
+TWO_VIEW_OUTPUT_FIELDS = ("status", "reason", "n_matches", "scores", "best_iter", "H21", "F21", "inliers_h", "inliers_f", "R21", "t21", "P3D",
+                          "triangulated", "n_hyp", "hyp_n_good", "hyp_parallax", "hyp_R", "hyp_t")
+
+
+class TwoViewOutputs(C.Structure):
+    """viorb_two_view_outputs (include/viorb_two_view.h)."""
+    _fields_ = [(n, C.c_void_p) for n in TWO_VIEW_OUTPUT_FIELDS]
 
 
 class TrackerConfig(C.Structure):
@@ -253,6 +268,26 @@ SIGNATURES_GLOBAL_BA_SE3 = {
     "viorb_debug_gba_se3_edge": (i32, [vp] * 7),
 }
 
+# mirrors include/viorb_two_view.h (the two-view initialiser); tests/test_two_view_ref.py checks names and argument counts against it
+_tv_in = [PP(TwoViewConfig), vp, vp, vp, vp, i32, vp]          # cfg, xy1, n1, xy2, n2, cap, matches12
+SIGNATURES_TWO_VIEW = {
+    "viorb_two_view_draw_sets": (i32, [i32, i32, C.c_uint64, vp]),
+    "viorb_two_view_workspace_bytes": (sz, [i32, i32, i32]),
+    "viorb_two_view_init_device": (i32, _tv_in + [vp, i32, PP(TwoViewOutputs), vp, sz, vp]),
+    "viorb_two_view_init": (i32, [PP(TwoViewConfig), vp, i32, vp, i32, vp, vp, PP(TwoViewOutputs)]),
+    "viorb_two_view_hypotheses_device": (i32, _tv_in + [vp, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "viorb_two_view_score_device": (i32, _tv_in + [i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "viorb_two_view_reconstruct_device": (i32, _tv_in + [i32, vp, vp, vp, PP(TwoViewOutputs), vp, sz, vp]),
+    "viorb_debug_two_view_hypothesis": (i32, [i32, vp, vp, vp, vp]),
+    "viorb_debug_two_view_denormalise": (i32, [i32, vp, vp, vp, vp, vp]),
+    "viorb_debug_two_view_normalise": (i32, [vp, i32, vp]),
+    "viorb_debug_two_view_chi2": (i32, [i32, vp, vp, vp, f32, vp, vp]),
+    "viorb_debug_two_view_decompose": (i32, [i32, vp, vp, vp, vp, vp]),
+    "viorb_debug_two_view_check_rt": (i32, [vp, vp, vp, vp, f32, vp, vp]),
+    "viorb_debug_two_view_parallax": (f32, [vp, i32]),
+    "viorb_debug_two_view_accept": (i32, [i32, vp, vp, i32, f32, i32, vp]),
+}
+
 _lib = None
 
 
@@ -272,7 +307,7 @@ def lib():
         except Exception:
             pass
         L = C.CDLL(SO_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GLOBAL_BA_SE3.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GLOBAL_BA_SE3.items()) + list(SIGNATURES_TWO_VIEW.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

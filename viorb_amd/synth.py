@@ -620,6 +620,48 @@ def make_two_view_problem(seed, n1=900, n2=950, n_common=500, stereo_frac=0.0, w
                 inv_level_sigma2=(np.float32(1) / (sf * sf)).astype(np.float32), truth12=truth, X=X)
 
 
+def make_two_view_init_problem(seed, kind="general", n1=400, n2=430, n_matches=300, outlier_share=0.1, noise_px=0.5, w=752, h=480):
+    """Two monocular frames with putative matches, for the two-view initialiser (Initializer::Initialize): xy1 [n1,2], xy2 [n2,2]
+    undistorted key points (float32), matches12 [n1] (index in frame 2 or -1), K4. Camera 1 is the origin, X2 = R21 X1 + t21.
+    kind: "general" (depths 4..12, sideways motion), "planar" (every point on one tilted plane), "low_parallax" (rotation, baseline about
+    1e-3 of the depth), "forward" (motion along the optical axis). n_matches matches of which outlier_share point to a random key point
+    of frame 2; the other key points of both frames are unmatched clutter (so that Normalize over all key points differs from one over
+    the matched ones). Ground truth: R21, t21 (unit), scale = |t| before normalisation, depth1 [n1] = depth in camera 1 of a true match
+    (nan otherwise), true12 [n1] (1 for a true match). numpy only."""
+    rng = np.random.Generator(np.random.PCG64(seed + 424243))
+    fx, fy, cx, cy = [float(np.float32(v)) for v in (EUROC_K["fx"], EUROC_K["fy"], EUROC_K["cx"], EUROC_K["cy"])]
+    motion = dict(general=((0.03, (-0.55, 0.04, 0.03))), planar=((0.04, (-0.5, 0.06, 0.05))), low_parallax=((0.05, (-0.008, 0.001, 0.0))),
+                  forward=((0.02, (0.03, 0.02, -0.7))))[kind]
+    R = _rotvec_to_R(rng.normal(0, motion[0], 3)); t = np.array(motion[1]) + rng.normal(0, 0.02, 3) * np.linalg.norm(motion[1])
+    m = 6 * n_matches + 64
+    uv1 = np.stack([rng.uniform(15, w - 15, m), rng.uniform(15, h - 15, m)], 1)
+    ray = np.stack([(uv1[:, 0] - cx) / fx, (uv1[:, 1] - cy) / fy, np.ones(m)], 1)
+    if kind == "planar":
+        nrm = np.array([0.3, 0.2, 1.0]); z = 6.0 / (ray @ nrm)            # the plane 0.3 x + 0.2 y + z = 6
+    else:
+        z = rng.uniform(4.0, 12.0, m)
+    X = ray * z[:, None]
+    X2 = X @ R.T + t
+    uv2 = np.stack([fx * X2[:, 0] / X2[:, 2] + cx, fy * X2[:, 1] / X2[:, 2] + cy], 1)
+    ok = (z > 0.5) & (X2[:, 2] > 0.5) & (uv2[:, 0] > 15) & (uv2[:, 0] < w - 15) & (uv2[:, 1] > 15) & (uv2[:, 1] < h - 15)
+    uv1, uv2, z = uv1[ok][:n_matches], uv2[ok][:n_matches], z[ok][:n_matches]
+    nm = len(uv1)
+    assert nm == n_matches and n1 >= nm and n2 >= nm, "not enough visible points / key points for n_matches"
+    xy1 = np.concatenate([uv1 + rng.normal(0, noise_px, (nm, 2)), np.stack([rng.uniform(15, w - 15, n1 - nm), rng.uniform(15, h - 15, n1 - nm)], 1)])
+    xy2 = np.concatenate([uv2 + rng.normal(0, noise_px, (nm, 2)), np.stack([rng.uniform(15, w - 15, n2 - nm), rng.uniform(15, h - 15, n2 - nm)], 1)])
+    match = np.full(n1, -1, np.int64); match[:nm] = np.arange(nm)
+    true12 = np.zeros(n1, np.uint8); true12[:nm] = 1
+    out = rng.permutation(nm)[:int(round(outlier_share * nm))]
+    match[out] = rng.integers(0, n2, len(out)); true12[out] = 0
+    depth = np.full(n1, np.nan); depth[:nm] = z; depth[out] = np.nan
+    p1, p2 = rng.permutation(n1), rng.permutation(n2)
+    inv2 = np.empty(n2, np.int64); inv2[p2] = np.arange(n2)
+    match = np.where(match >= 0, inv2[np.maximum(match, 0)], -1)[p1]
+    return dict(xy1=xy1[p1].astype(np.float32), xy2=xy2[p2].astype(np.float32), matches12=match.astype(np.int32),
+                K4=np.array([fx, fy, cx, cy], np.float32), R21=R, t21=t / np.linalg.norm(t), scale=float(np.linalg.norm(t)), depth1=depth[p1],
+                true12=true12[p1], kind=kind)
+
+
 def make_local_ba_se3_problem(seed, W=8, n_fixed=3, n_points=600, stereo_frac=0.5, outlier_frac=0.05, pix_sigma=1.5, w=1241, h=376):
     """A vision-only LocalBundleAdjustment problem (KITTI-shaped camera): W free key frames + n_fixed fixed ones on a forward-moving
     trajectory, points seen by 3..7 key frames, a mix of mono and stereo observations, Gaussian pixel noise and gross outliers.
