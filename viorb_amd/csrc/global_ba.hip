@@ -95,32 +95,25 @@ __global__ __launch_bounds__(256) void k_gba_errors(GbaDev D) {
     if (k < D.ne) {
         const cam_t K = ld_cam(D.cam);
         double e[2];
-        gba_proj_error(K, D.kf + (size_t)D.e_idx[2 * k + 1] * 22, D.pt + (size_t)D.e_idx[2 * k] * 3, D.e_obs + 3 * (size_t)k, e);
+        ba_nav_error(K, ba_nav_geom(K, D.kf + (size_t)D.e_idx[2 * k + 1] * 22, D.pt + (size_t)D.e_idx[2 * k] * 3).Pc, D.e_obs + 3 * (size_t)k, e);
         D.err[2 * k] = e[0]; D.err[2 * k + 1] = e[1];
         double r1;
-        gba_robust(D.robust, D.e_obs[3 * (size_t)k + 2] * (e[0] * e[0] + e[1] * e[1]), gba_delta_mono(), &c, &r1);
+        ba_robust(D.robust, D.e_obs[3 * (size_t)k + 2] * (e[0] * e[0] + e[1] * e[1]), ba_delta_mono_map(), &c, &r1);
     }
-    c = gba_block_sum(c, s_red);
+    c = ba_block_sum(c, s_red);
     if (threadIdx.x == 0 && c != 0.0) unsafeAtomicAdd(&D.scal[GBA_S_CHI], c);
-}
-__device__ __forceinline__ double gba_chi9(const double* info, const double* e) {
-    double chi = 0;
-    for (int a = 0; a < 9; a++) { double t = 0; for (int b = 0; b < 9; b++) t += info[a * 9 + b] * e[b]; chi += e[a] * t; }
-    return chi;
 }
 __global__ __launch_bounds__(256) void k_gba_imu_errors(GbaDev D) {
     __shared__ double s_red[4];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     double c = 0;
     if (i < D.nk && D.prev[i] >= 0) {
-        const double* ki = D.kf + (size_t)i * 22; const double* kj = D.kf + (size_t)D.prev[i] * 22;
-        double e[9], r0, r1;
-        pvr_edge(ld_pvr(kj), ld_pvr(ki), ld3(kj + 16), ld3(kj + 19), D.preint + (size_t)i * 142, ld3(D.gw), e, nullptr);
-        gba_robust(D.robust, gba_chi9(D.info_pvr + (size_t)i * 81, e), gba_delta_pvr(), &r0, &r1); c = r0;
-        const d3 eb = (ld3(ki + 13) + ld3(ki + 19)) - (ld3(kj + 13) + ld3(kj + 19));
-        gba_robust(D.robust, dot3(eb, eb) / GBA_ACC_BIAS_RW2 / D.preint[(size_t)i * 142 + 141], gba_delta_bias(), &r0, &r1); c += r0;
+        double e[9], rho[2]; d3 eb;
+        ba_imu_chi2(D.kf + (size_t)i * 22, D.kf + (size_t)D.prev[i] * 22, D.preint + (size_t)i * 142, D.info_pvr + (size_t)i * 81, ld3(D.gw), GBA_ACC_BIAS_RW2,
+                    D.robust, e, &eb, rho);
+        c = rho[0]; c += rho[1];
     }
-    c = gba_block_sum(c, s_red);
+    c = ba_block_sum(c, s_red);
     if (threadIdx.x == 0 && c != 0.0) unsafeAtomicAdd(&D.scal[GBA_S_CHI], c);
 }
 __global__ __launch_bounds__(256) void k_gba_lin_edges(GbaDev D) {
@@ -128,10 +121,10 @@ __global__ __launch_bounds__(256) void k_gba_lin_edges(GbaDev D) {
     if (k >= D.ne) return;
     const cam_t K = ld_cam(D.cam);
     double Jp[6], Jk[12];
-    gba_proj_lin(K, D.kf + (size_t)D.e_idx[2 * k + 1] * 22, D.pt + (size_t)D.e_idx[2 * k] * 3, Jp, Jk);
+    ba_nav_jac(K, ba_nav_geom(K, D.kf + (size_t)D.e_idx[2 * k + 1] * 22, D.pt + (size_t)D.e_idx[2 * k] * 3), Jp, Jk);
     const double e0 = D.err[2 * k], e1 = D.err[2 * k + 1], is2 = D.e_obs[3 * (size_t)k + 2];
     double r0, r1;
-    gba_robust(D.robust, is2 * (e0 * e0 + e1 * e1), gba_delta_mono(), &r0, &r1);
+    ba_robust(D.robust, is2 * (e0 * e0 + e1 * e1), ba_delta_mono_map(), &r0, &r1);
     const double w = r1 * is2;
     D.wgt[k] = w;
     double2* Jpo = reinterpret_cast<double2*>(D.Jp + 6 * (size_t)k); double2* Jko = reinterpret_cast<double2*>(D.Jk + 12 * (size_t)k);
@@ -141,29 +134,11 @@ __global__ __launch_bounds__(256) void k_gba_lin_edges(GbaDev D) {
 #pragma unroll
     for (int a = 0; a < 6; a++) Jko[a] = make_double2(Jk[2 * a], Jk[2 * a + 1]);
     double We[18];
-#pragma unroll
-    for (int r = 0; r < 6; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) We[3 * r + c] = w * (Jk[r] * Jp[c] + Jk[6 + r] * Jp[3 + c]);
+    ba_w_block<2>(w, Jk, Jp, We);
 #pragma unroll
     for (int a = 0; a < 9; a++) Wo[a] = make_double2(We[2 * a], We[2 * a + 1]);
 }
-__global__ __launch_bounds__(256) void k_gba_hll(GbaDev D) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= D.np) return;
-    double H[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
-    for (int k = D.pt_start[p]; k < D.pt_start[p + 1]; k++) {
-        const double* Jp = D.Jp + 6 * (size_t)k;
-        const double w = D.wgt[k], e0 = D.err[2 * k], e1 = D.err[2 * k + 1];
-        H[0] += w * (Jp[0] * Jp[0] + Jp[3] * Jp[3]); H[1] += w * (Jp[0] * Jp[1] + Jp[3] * Jp[4]); H[2] += w * (Jp[0] * Jp[2] + Jp[3] * Jp[5]);
-        H[3] += w * (Jp[1] * Jp[1] + Jp[4] * Jp[4]); H[4] += w * (Jp[1] * Jp[2] + Jp[4] * Jp[5]); H[5] += w * (Jp[2] * Jp[2] + Jp[5] * Jp[5]);
-        for (int a = 0; a < 3; a++) b[a] -= w * (Jp[a] * e0 + Jp[3 + a] * e1);
-    }
-    double* Ho = D.Hll + (size_t)p * 9;
-    Ho[0] = H[0]; Ho[1] = H[1]; Ho[2] = H[2]; Ho[3] = H[1]; Ho[4] = H[3]; Ho[5] = H[4]; Ho[6] = H[2]; Ho[7] = H[4]; Ho[8] = H[5];
-    for (int a = 0; a < 3; a++) D.bl[(size_t)p * 3 + a] = b[a];
-    D.included[p] = D.pt_start[p + 1] > D.pt_start[p];            // a point without an edge is not a vertex (src/Optimizer.cc:234-242)
-}
+__global__ __launch_bounds__(256) void k_gba_hll(GbaDev D) { gba_hll_body<2>(D); }
 // one workgroup per key frame: writes the whole 12 x 12 diagonal block and bp of a free one (the IMU kernel adds to them afterwards) and
 // clears its predecessor block
 __global__ __launch_bounds__(256) void k_gba_hpp(GbaDev D) {
@@ -176,41 +151,18 @@ __global__ __launch_bounds__(256) void k_gba_hpp(GbaDev D) {
     for (int k = 0; k < 27; k++) a[k] = 0;
     for (int q = D.kf_start[i] + t; q < D.kf_start[i + 1]; q += blockDim.x) {
         const int k = D.kf_list[q];
-        const double* J = D.Jk + (size_t)12 * k; const double w = D.wgt[k];
-#pragma unroll
-        for (int row = 0; row < 2; row++) {
-            const double* Jr = J + 6 * row; const double er = D.err[2 * k + row];
-            int c = 0;
-#pragma unroll
-            for (int rr = 0; rr < 6; rr++)
-#pragma unroll
-                for (int cc = rr; cc < 6; cc++) a[c++] += w * (Jr[rr] * Jr[cc]);
-#pragma unroll
-            for (int rr = 0; rr < 6; rr++) a[21 + rr] -= w * (Jr[rr] * er);
-        }
+        ba_kf_add<2>(a, D.wgt[k], D.Jk + (size_t)12 * k, D.err + 2 * k);
     }
-#pragma unroll
-    for (int k = 0; k < 27; k++) {
-        double v = a[k];
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-        if ((t & 63) == 0) s_red[t >> 6][k] = v;
-    }
-    __syncthreads();
+    ba_kf_reduce(a, s_red);
     if (t < 144) {
         const int rr = t / 12, cc = t % 12;
         // index of (min, max) in the packed upper triangle of the 6 x 6 block, for the coordinates an observation touches
         const int a6 = rr < 3 ? rr : (rr >= 6 && rr < 9 ? rr - 3 : -1), b6 = cc < 3 ? cc : (cc >= 6 && cc < 9 ? cc - 3 : -1);
-        double v = 0.0;
-        if (a6 >= 0 && b6 >= 0) {
-            const int lo = a6 < b6 ? a6 : b6, hi = a6 < b6 ? b6 : a6, k = lo * 6 - lo * (lo - 1) / 2 + (hi - lo);
-            v = s_red[0][k] + s_red[1][k] + s_red[2][k] + s_red[3][k];
-        }
-        D.Hd[(size_t)r * 144 + t] = v;
+        D.Hd[(size_t)r * 144 + t] = a6 >= 0 && b6 >= 0 ? ba_kf_sum(s_red, ba_kf_tri(a6, b6)) : 0.0;
     }
     if (t < 12) {
         const int a6 = t < 3 ? t : (t >= 6 && t < 9 ? t - 3 : -1);
-        D.bp[12 * r + t] = a6 >= 0 ? s_red[0][21 + a6] + s_red[1][21 + a6] + s_red[2][21 + a6] + s_red[3][21 + a6] : 0.0;
+        D.bp[12 * r + t] = a6 >= 0 ? ba_kf_sum(s_red, 21 + a6) : 0.0;
     }
 }
 // one wavefront per key frame i with a predecessor j: EdgeNavStatePVR on (PVR j, PVR i, bias j) and EdgeNavStateBias on (bias j, bias i).
@@ -225,13 +177,10 @@ __global__ __launch_bounds__(64) void k_gba_imu(GbaDev D) {
     const double* ki = D.kf + (size_t)i * 22; const double* kj = D.kf + (size_t)j * 22;
     const double* info = D.info_pvr + (size_t)i * 81;
     if (t == 0) {
-        pvr_edge(ld_pvr(kj), ld_pvr(ki), ld3(kj + 16), ld3(kj + 19), D.preint + (size_t)i * 142, ld3(D.gw), e, J);
-        double r0, r1;
-        gba_robust(D.robust, gba_chi9(info, e), gba_delta_pvr(), &r0, &r1); s_w = r1;
-        const d3 eb = (ld3(ki + 13) + ld3(ki + 19)) - (ld3(kj + 13) + ld3(kj + 19));
-        const double binfo = 1.0 / GBA_ACC_BIAS_RW2 / D.preint[(size_t)i * 142 + 141];
-        gba_robust(D.robust, binfo * dot3(eb, eb), gba_delta_bias(), &r0, &r1);
-        const double wb = r1 * binfo, ev[3] = {eb.x, eb.y, eb.z};
+        d3 eb; double w_pvr, wb;
+        ba_imu_weights(ki, kj, D.preint + (size_t)i * 142, info, ld3(D.gw), GBA_ACC_BIAS_RW2, D.robust, e, J, &w_pvr, &eb, &wb);
+        s_w = w_pvr;
+        const double ev[3] = {eb.x, eb.y, eb.z};
         for (int c = 0; c < 3; c++) {
             const int d = (9 + c) * 12 + 9 + c;
             if (ri >= 0) { unsafeAtomicAdd(&D.Hd[(size_t)ri * 144 + d], wb); unsafeAtomicAdd(&D.bp[12 * ri + 9 + c], -wb * ev[c]); }
@@ -240,7 +189,7 @@ __global__ __launch_bounds__(64) void k_gba_imu(GbaDev D) {
         }
     }
     __syncthreads();
-    for (int q = t; q < 189; q += 64) { const int r = q / 21, c = q % 21; double s = 0; for (int k = 0; k < 9; k++) s += info[r * 9 + k] * J[k * 21 + c]; OJ[q] = s; }
+    ba_omega_j(info, J, OJ, t, 64);
     __syncthreads();
     const double w = s_w;
     for (int q = t; q < 441 + 21; q += 64) {
@@ -277,13 +226,7 @@ __global__ __launch_bounds__(256) void k_gba_dinv(GbaDev D, double lambda) {
     if (p >= D.np) return;
     double* Di = D.Dinv + (size_t)p * 9;
     if (D.pt_start[p + 1] == D.pt_start[p]) { for (int a = 0; a < 9; a++) Di[a] = 0.0; for (int a = 0; a < 3; a++) D.db[3 * (size_t)p + a] = 0.0; return; }
-    const double* H = D.Hll + (size_t)p * 9;
-    const double a = H[0] + lambda, b = H[1], c = H[2], d = H[4] + lambda, e = H[5], f = H[8] + lambda;
-    const double det = a * (d * f - e * e) - b * (b * f - c * e) + c * (b * e - c * d), id = 1.0 / det;
-    const double i00 = (d * f - e * e) * id, i01 = (c * e - b * f) * id, i02 = (b * e - c * d) * id, i11 = (a * f - c * c) * id, i12 = (b * c - a * e) * id, i22 = (a * d - b * b) * id;
-    Di[0] = i00; Di[1] = i01; Di[2] = i02; Di[3] = i01; Di[4] = i11; Di[5] = i12; Di[6] = i02; Di[7] = i12; Di[8] = i22;
-    const double b0 = D.bl[3 * (size_t)p], b1 = D.bl[3 * (size_t)p + 1], b2 = D.bl[3 * (size_t)p + 2];
-    D.db[3 * (size_t)p] = i00 * b0 + i01 * b1 + i02 * b2; D.db[3 * (size_t)p + 1] = i01 * b0 + i11 * b1 + i12 * b2; D.db[3 * (size_t)p + 2] = i02 * b0 + i12 * b1 + i22 * b2;
+    ba_point_inverse(D.Hll + (size_t)p * 9, lambda, D.bl + 3 * (size_t)p, Di, D.db + 3 * (size_t)p);
 }
 // S was cleared by a memset; blocks [0, nk): the blocks of key frame i; the blocks behind them: right-hand side and the identity on the padding
 __global__ __launch_bounds__(256) void k_gba_init_reduced(GbaDev D, double lambda) {
@@ -302,38 +245,7 @@ __global__ __launch_bounds__(256) void k_gba_init_reduced(GbaDev D, double lambd
         if (q >= D.n) D.S[(size_t)q * ld + q] = 1.0;
     }
 }
-// Schur complement of the point block (block_solver.hpp:381-432): one wavefront per point walks the ordered pairs (a, b) of its
-// observers; the pair with rank(a) > rank(b) owns block (a, b) of the lower triangle, a pair on one key frame the lower triangle of its
-// diagonal block. S_ab -= W_a Dinv W_b^T, bs_a -= W_a Dinv bl (W = wgt Jk^T Jp, 6 x 3).
-__global__ __launch_bounds__(64) void k_gba_schur(GbaDev D) {
-    const int p = blockIdx.x, s = D.pt_start[p], m = D.pt_start[p + 1] - s, ld = D.ld;
-    if (m == 0) return;
-    double Di[9], db[3];
-    for (int a = 0; a < 9; a++) Di[a] = D.Dinv[(size_t)p * 9 + a];
-    for (int a = 0; a < 3; a++) db[a] = D.db[(size_t)p * 3 + a];
-    for (int q = threadIdx.x; q < m * m; q += 64) {
-        const int a = s + q / m, b = s + q % m;
-        const int fa = D.fidx[D.e_idx[2 * a + 1]], fb = D.fidx[D.e_idx[2 * b + 1]];
-        if (fa < 0 || fb < 0 || fa < fb) continue;
-        double Wa[18], Wb[18], BD[18];
-#pragma unroll
-        for (int k = 0; k < 18; k++) { Wa[k] = D.We[18 * (size_t)a + k]; Wb[k] = D.We[18 * (size_t)b + k]; }
-#pragma unroll
-        for (int r = 0; r < 6; r++)
-#pragma unroll
-            for (int c = 0; c < 3; c++) BD[3 * r + c] = Wa[3 * r] * Di[c] + Wa[3 * r + 1] * Di[3 + c] + Wa[3 * r + 2] * Di[6 + c];
-#pragma unroll
-        for (int r = 0; r < 6; r++) {
-            double* row = D.S + (size_t)(12 * fa + gba_loc(r)) * ld + 12 * fb;
-#pragma unroll
-            for (int c = 0; c < 6; c++) {
-                if (fa == fb && c > r) continue;
-                unsafeAtomicAdd(&row[gba_loc(c)], -(BD[3 * r] * Wb[3 * c] + BD[3 * r + 1] * Wb[3 * c + 1] + BD[3 * r + 2] * Wb[3 * c + 2]));
-            }
-            if (a == b) unsafeAtomicAdd(&D.rhs[12 * fa + gba_loc(r)], -(Wa[3 * r] * db[0] + Wa[3 * r + 1] * db[1] + Wa[3 * r + 2] * db[2]));
-        }
-    }
-}
+__global__ __launch_bounds__(64) void k_gba_schur(GbaDev D) { gba_schur_body<12>(D); }
 
 // ---- blocked right-looking Cholesky of the lower triangle of S (row-major, leading dimension ld, a multiple of GBA_NB), in place ------
 #define GBA_LDS 65        // tile rows in LDS, padded against bank conflicts of column walks
@@ -487,20 +399,7 @@ __global__ __launch_bounds__(256) void k_gba_bwd(GbaDev D, int kb) {
 }
 
 // ---- increments, retraction, restore ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_gba_backsub(GbaDev D) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= D.np) return;
-    if (D.scal[GBA_S_FAIL] != 0.0) return;
-    double cl[3] = {D.bl[3 * (size_t)p], D.bl[3 * (size_t)p + 1], D.bl[3 * (size_t)p + 2]};
-    for (int k = D.pt_start[p]; k < D.pt_start[p + 1]; k++) {
-        const int r = D.fidx[D.e_idx[2 * k + 1]];
-        if (r < 0) continue;
-        const double* W = D.We + 18 * (size_t)k; const double* x = D.xp + 12 * (size_t)r;
-        for (int c = 0; c < 3; c++) { double s = 0; for (int a = 0; a < 6; a++) s += W[3 * a + c] * x[gba_loc(a)]; cl[c] -= s; }
-    }
-    const double* Di = D.Dinv + (size_t)p * 9;
-    for (int a = 0; a < 3; a++) D.xl[3 * (size_t)p + a] = Di[3 * a] * cl[0] + Di[3 * a + 1] * cl[1] + Di[3 * a + 2] * cl[2];
-}
+__global__ __launch_bounds__(256) void k_gba_backsub(GbaDev D) { gba_backsub_body<12>(D); }
 // oplus of every vertex (NavState::IncSmallPVR / IncSmallBias, point += xl) and scale = sum x (lambda x + b) of the gain ratio
 __global__ __launch_bounds__(256) void k_gba_update(GbaDev D, double lambda) {
     __shared__ double s_red[4];
@@ -517,7 +416,7 @@ __global__ __launch_bounds__(256) void k_gba_update(GbaDev D, double lambda) {
         }
         if (q < D.np) for (int a = 0; a < 3; a++) { const double x = D.xl[3 * (size_t)q + a]; sc += x * (lambda * x + D.bl[3 * (size_t)q + a]); D.pt[3 * (size_t)q + a] += x; }
     }
-    sc = gba_block_sum(sc, s_red);
+    sc = ba_block_sum(sc, s_red);
     if (threadIdx.x == 0 && sc != 0.0) unsafeAtomicAdd(&D.scal[GBA_S_SCALE], sc);
 }
 

@@ -2,7 +2,8 @@
 // (GbaDev), the host functions of global_ba.hip that both call (graph bookkeeping, the blocked Cholesky chain, the Levenberg loop) and
 // the table of launches a solve plugs into that loop (GbaOps). global_ba.hip is the NavState solve (12 coordinates per free key frame,
 // IMU factors), global_ba_se3.hip the vision-only one (6 coordinates, monocular and stereo edges). The kernels named here live in
-// global_ba.hip; the other translation unit reaches them through these host functions only.
+// global_ba.hip; the other translation unit reaches them through these host functions only. The Schur complement, the back-substitution
+// and the point blocks differ between the two only in the block order and the residual rows: one template body each, below.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
@@ -38,12 +39,69 @@ struct GbaDev {
     double cam[16], gw[3];              // NavState solve: cam[16], gw; SE3 solve: cam[0..4] = fx fy cx cy bf
 };
 
-__device__ __forceinline__ double gba_block_sum(double v, double* s_red) {      // 256 threads; result valid in thread 0
+// ---- kernel bodies both solves instantiate with their block order BLK (12 / 6) and residual rows ROWS (2 / 3); the __global__
+// wrappers k_gba_* / k_gse3_* keep the names the profile tools report
+// one thread per point: Hll, bl in edge order
+template <int ROWS> __device__ __forceinline__ void gba_hll_body(const GbaDev& D) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= D.np) return;
+    double H[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
+    for (int k = D.pt_start[p]; k < D.pt_start[p + 1]; k++) {
+        const double* Jp = D.Jp + 3 * ROWS * (size_t)k;
+        const double w = D.wgt[k];
+        double e[ROWS];
+        for (int r = 0; r < ROWS; r++) e[r] = D.err[ROWS * k + r];
+        ba_point_add<ROWS>(H, b, w, Jp, e);
+    }
+    ba_point_store(D.Hll + (size_t)p * 9, D.bl + (size_t)p * 3, H, b);
+    D.included[p] = D.pt_start[p + 1] > D.pt_start[p];            // a point without an edge is not a vertex (src/Optimizer.cc:234-242, :3685-3693)
+}
+// Schur complement of the point block (block_solver.hpp:381-432): one wavefront per point walks the ordered pairs (a, b) of its
+// observers; the pair with rank(a) > rank(b) owns block (a, b) of the lower triangle, a pair on one key frame the lower triangle of its
+// diagonal block. S_ab -= W_a Dinv W_b^T, bs_a -= W_a Dinv bl (W = wgt Jk^T Jp, 6 x 3), FP64 hardware atomics.
+template <int BLK> __device__ __forceinline__ void gba_schur_body(const GbaDev& D) {
+    const int p = blockIdx.x, s = D.pt_start[p], m = D.pt_start[p + 1] - s, ld = D.ld;
+    if (m == 0) return;
+    double Di[9], db[3];
+    for (int a = 0; a < 9; a++) Di[a] = D.Dinv[(size_t)p * 9 + a];
+    for (int a = 0; a < 3; a++) db[a] = D.db[(size_t)p * 3 + a];
+    for (int q = threadIdx.x; q < m * m; q += 64) {
+        const int a = s + q / m, b = s + q % m;
+        const int fa = D.fidx[D.e_idx[2 * a + 1]], fb = D.fidx[D.e_idx[2 * b + 1]];
+        if (fa < 0 || fb < 0 || fa < fb) continue;
+        double Wa[18], Wb[18], BD[18];
 #pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return s_red[0] + s_red[1] + s_red[2] + s_red[3];
+        for (int k = 0; k < 18; k++) { Wa[k] = D.We[18 * (size_t)a + k]; Wb[k] = D.We[18 * (size_t)b + k]; }
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+#pragma unroll
+            for (int c = 0; c < 3; c++) BD[3 * r + c] = Wa[3 * r] * Di[c] + Wa[3 * r + 1] * Di[3 + c] + Wa[3 * r + 2] * Di[6 + c];
+#pragma unroll
+        for (int r = 0; r < 6; r++) {
+            double* row = D.S + (size_t)(BLK * fa + loc6(BLK, r)) * ld + BLK * fb;
+#pragma unroll
+            for (int c = 0; c < 6; c++) {
+                if (fa == fb && c > r) continue;
+                unsafeAtomicAdd(&row[loc6(BLK, c)], -(BD[3 * r] * Wb[3 * c] + BD[3 * r + 1] * Wb[3 * c + 1] + BD[3 * r + 2] * Wb[3 * c + 2]));
+            }
+            if (a == b) unsafeAtomicAdd(&D.rhs[BLK * fa + loc6(BLK, r)], -(Wa[3 * r] * db[0] + Wa[3 * r + 1] * db[1] + Wa[3 * r + 2] * db[2]));
+        }
+    }
+}
+// point increments xl = Dinv (bl - sum W^T xp): every edge's product is summed first and subtracted once
+template <int BLK> __device__ __forceinline__ void gba_backsub_body(const GbaDev& D) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= D.np) return;
+    if (D.scal[GBA_S_FAIL] != 0.0) return;
+    double cl[3] = {D.bl[3 * (size_t)p], D.bl[3 * (size_t)p + 1], D.bl[3 * (size_t)p + 2]};
+    for (int k = D.pt_start[p]; k < D.pt_start[p + 1]; k++) {
+        const int r = D.fidx[D.e_idx[2 * k + 1]];
+        if (r < 0) continue;
+        const double* W = D.We + 18 * (size_t)k; const double* x = D.xp + BLK * (size_t)r;
+        for (int c = 0; c < 3; c++) { double s = 0; for (int a = 0; a < 6; a++) s += W[3 * a + c] * x[loc6(BLK, a)]; cl[c] -= s; }
+    }
+    const double* Di = D.Dinv + (size_t)p * 9;
+    for (int a = 0; a < 3; a++) D.xl[3 * (size_t)p + a] = Di[3 * a] * cl[0] + Di[3 * a + 1] * cl[1] + Di[3 * a + 2] * cl[2];
 }
 
 // The host form's lease of a stream context. An error path may leave work queued on the stream: nothing of it may still run when the

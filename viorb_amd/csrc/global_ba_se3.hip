@@ -44,22 +44,22 @@ __global__ __launch_bounds__(256) void k_gse3_errors(GbaDev D) {
         gba_se3_error(D.kf + (size_t)D.e_idx[2 * k + 1] * 7, D.pt + (size_t)D.e_idx[2 * k] * 3, ob, D.cam, e);
         D.err[3 * (size_t)k] = e[0]; D.err[3 * (size_t)k + 1] = e[1]; D.err[3 * (size_t)k + 2] = e[2];
         double r1;
-        gba_robust(D.robust, ob[3] * (e[0] * e[0] + e[1] * e[1] + e[2] * e[2]), gba_se3_delta(ob), &c, &r1);
+        ba_robust(D.robust, ob[3] * (e[0] * e[0] + e[1] * e[1] + e[2] * e[2]), gba_se3_delta(ob), &c, &r1);
     }
-    c = gba_block_sum(c, s_red);
+    c = ba_block_sum(c, s_red);
     if (threadIdx.x == 0 && c != 0.0) unsafeAtomicAdd(&D.scal[GBA_S_CHI], c);
 }
 
-// err[] is that of the current state (k_gse3_errors ran on it); the error computed here with the Jacobians is the same value
+// err[] is that of the current state (k_gse3_errors ran on it)
 __global__ __launch_bounds__(256) void k_gse3_lin_edges(GbaDev D) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= D.ne) return;
     const double* ob = D.e_obs + 4 * (size_t)k;
-    double e[3], Jp[9], Jk[18];
-    gba_se3_lin(D.kf + (size_t)D.e_idx[2 * k + 1] * 7, D.pt + (size_t)D.e_idx[2 * k] * 3, ob, D.cam, e, Jp, Jk);
+    double Jp[9], Jk[18];
+    gba_se3_jac(D.kf + (size_t)D.e_idx[2 * k + 1] * 7, D.pt + (size_t)D.e_idx[2 * k] * 3, ob, D.cam, Jp, Jk);
     const double e0 = D.err[3 * (size_t)k], e1 = D.err[3 * (size_t)k + 1], e2 = D.err[3 * (size_t)k + 2];
     double r0, r1;
-    gba_robust(D.robust, ob[3] * (e0 * e0 + e1 * e1 + e2 * e2), gba_se3_delta(ob), &r0, &r1);
+    ba_robust(D.robust, ob[3] * (e0 * e0 + e1 * e1 + e2 * e2), gba_se3_delta(ob), &r0, &r1);
     const double w = r1 * ob[3];
     D.wgt[k] = w;
     double* Jpo = D.Jp + 9 * (size_t)k; double2* Jko = reinterpret_cast<double2*>(D.Jk + 18 * (size_t)k);
@@ -69,30 +69,12 @@ __global__ __launch_bounds__(256) void k_gse3_lin_edges(GbaDev D) {
 #pragma unroll
     for (int a = 0; a < 9; a++) Jko[a] = make_double2(Jk[2 * a], Jk[2 * a + 1]);
     double We[18];
-#pragma unroll
-    for (int r = 0; r < 6; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) We[3 * r + c] = w * (Jk[r] * Jp[c] + Jk[6 + r] * Jp[3 + c] + Jk[12 + r] * Jp[6 + c]);
+    ba_w_block<3>(w, Jk, Jp, We);
 #pragma unroll
     for (int a = 0; a < 9; a++) Wo[a] = make_double2(We[2 * a], We[2 * a + 1]);
 }
 
-__global__ __launch_bounds__(256) void k_gse3_hll(GbaDev D) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= D.np) return;
-    double H[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
-    for (int k = D.pt_start[p]; k < D.pt_start[p + 1]; k++) {
-        const double* J = D.Jp + 9 * (size_t)k; const double* e = D.err + 3 * (size_t)k;
-        const double w = D.wgt[k];
-        H[0] += w * (J[0] * J[0] + J[3] * J[3] + J[6] * J[6]); H[1] += w * (J[0] * J[1] + J[3] * J[4] + J[6] * J[7]); H[2] += w * (J[0] * J[2] + J[3] * J[5] + J[6] * J[8]);
-        H[3] += w * (J[1] * J[1] + J[4] * J[4] + J[7] * J[7]); H[4] += w * (J[1] * J[2] + J[4] * J[5] + J[7] * J[8]); H[5] += w * (J[2] * J[2] + J[5] * J[5] + J[8] * J[8]);
-        for (int a = 0; a < 3; a++) b[a] -= w * (J[a] * e[0] + J[3 + a] * e[1] + J[6 + a] * e[2]);
-    }
-    double* Ho = D.Hll + (size_t)p * 9;
-    Ho[0] = H[0]; Ho[1] = H[1]; Ho[2] = H[2]; Ho[3] = H[1]; Ho[4] = H[3]; Ho[5] = H[4]; Ho[6] = H[2]; Ho[7] = H[4]; Ho[8] = H[5];
-    for (int a = 0; a < 3; a++) D.bl[(size_t)p * 3 + a] = b[a];
-    D.included[p] = D.pt_start[p + 1] > D.pt_start[p];            // a point without an edge is not a vertex (src/Optimizer.cc:3685-3693)
-}
+__global__ __launch_bounds__(256) void k_gse3_hll(GbaDev D) { gba_hll_body<3>(D); }
 
 // one workgroup per key frame: the 6 x 6 diagonal block (21 sums) and bp (6 sums) of a free one. A thread takes every 256th entry of the
 // key frame's edge list (sorted by edge number), so the order of the sums is fixed by the graph.
@@ -105,32 +87,11 @@ __global__ __launch_bounds__(256) void k_gse3_hpp(GbaDev D) {
     for (int k = 0; k < 27; k++) a[k] = 0;
     for (int q = D.kf_start[i] + t; q < D.kf_start[i + 1]; q += blockDim.x) {
         const int k = D.kf_list[q];
-        const double* J = D.Jk + (size_t)18 * k; const double w = D.wgt[k];
-#pragma unroll
-        for (int row = 0; row < 3; row++) {
-            const double* Jr = J + 6 * row; const double er = D.err[3 * (size_t)k + row];
-            int c = 0;
-#pragma unroll
-            for (int rr = 0; rr < 6; rr++)
-#pragma unroll
-                for (int cc = rr; cc < 6; cc++) a[c++] += w * (Jr[rr] * Jr[cc]);
-#pragma unroll
-            for (int rr = 0; rr < 6; rr++) a[21 + rr] -= w * (Jr[rr] * er);
-        }
+        ba_kf_add<3>(a, D.wgt[k], D.Jk + (size_t)18 * k, D.err + 3 * (size_t)k);
     }
-#pragma unroll
-    for (int k = 0; k < 27; k++) {
-        double v = a[k];
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-        if ((t & 63) == 0) s_red[t >> 6][k] = v;
-    }
-    __syncthreads();
-    if (t < 36) {
-        const int rr = t / 6, cc = t % 6, lo = rr < cc ? rr : cc, hi = rr < cc ? cc : rr, k = lo * 6 - lo * (lo - 1) / 2 + (hi - lo);
-        D.Hd[(size_t)r * 36 + t] = s_red[0][k] + s_red[1][k] + s_red[2][k] + s_red[3][k];
-    }
-    if (t < 6) D.bp[6 * r + t] = s_red[0][21 + t] + s_red[1][21 + t] + s_red[2][21 + t] + s_red[3][21 + t];
+    ba_kf_reduce(a, s_red);
+    if (t < 36) D.Hd[(size_t)r * 36 + t] = ba_kf_sum(s_red, ba_kf_tri(t / 6, t % 6));
+    if (t < 6) D.bp[6 * r + t] = ba_kf_sum(s_red, 21 + t);
 }
 
 // S was cleared by a memset; blocks [0, nk): the diagonal block of key frame i; the blocks behind them: right-hand side and the
@@ -150,53 +111,8 @@ __global__ __launch_bounds__(256) void k_gse3_init_reduced(GbaDev D, double lamb
     }
 }
 
-// Schur complement of the point block (block_solver.hpp:381-432): one wavefront per point walks the ordered pairs (a, b) of its
-// observers; the pair with rank(a) > rank(b) owns block (a, b) of the lower triangle, a pair on one key frame the lower triangle of its
-// diagonal block. S_ab -= W_a Dinv W_b^T, bs_a -= W_a Dinv bl (W = wgt Jk^T Jp, 6 x 3).
-__global__ __launch_bounds__(64) void k_gse3_schur(GbaDev D) {
-    const int p = blockIdx.x, s = D.pt_start[p], m = D.pt_start[p + 1] - s, ld = D.ld;
-    if (m == 0) return;
-    double Di[9], db[3];
-    for (int a = 0; a < 9; a++) Di[a] = D.Dinv[(size_t)p * 9 + a];
-    for (int a = 0; a < 3; a++) db[a] = D.db[(size_t)p * 3 + a];
-    for (int q = threadIdx.x; q < m * m; q += 64) {
-        const int a = s + q / m, b = s + q % m;
-        const int fa = D.fidx[D.e_idx[2 * a + 1]], fb = D.fidx[D.e_idx[2 * b + 1]];
-        if (fa < 0 || fb < 0 || fa < fb) continue;
-        double Wa[18], Wb[18], BD[18];
-#pragma unroll
-        for (int k = 0; k < 18; k++) { Wa[k] = D.We[18 * (size_t)a + k]; Wb[k] = D.We[18 * (size_t)b + k]; }
-#pragma unroll
-        for (int r = 0; r < 6; r++)
-#pragma unroll
-            for (int c = 0; c < 3; c++) BD[3 * r + c] = Wa[3 * r] * Di[c] + Wa[3 * r + 1] * Di[3 + c] + Wa[3 * r + 2] * Di[6 + c];
-#pragma unroll
-        for (int r = 0; r < 6; r++) {
-            double* row = D.S + (size_t)(6 * fa + r) * ld + 6 * fb;
-#pragma unroll
-            for (int c = 0; c < 6; c++) {
-                if (fa == fb && c > r) continue;
-                unsafeAtomicAdd(&row[c], -(BD[3 * r] * Wb[3 * c] + BD[3 * r + 1] * Wb[3 * c + 1] + BD[3 * r + 2] * Wb[3 * c + 2]));
-            }
-            if (a == b) unsafeAtomicAdd(&D.rhs[6 * fa + r], -(Wa[3 * r] * db[0] + Wa[3 * r + 1] * db[1] + Wa[3 * r + 2] * db[2]));
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_gse3_backsub(GbaDev D) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= D.np) return;
-    if (D.scal[GBA_S_FAIL] != 0.0) return;
-    double cl[3] = {D.bl[3 * (size_t)p], D.bl[3 * (size_t)p + 1], D.bl[3 * (size_t)p + 2]};
-    for (int k = D.pt_start[p]; k < D.pt_start[p + 1]; k++) {
-        const int r = D.fidx[D.e_idx[2 * k + 1]];
-        if (r < 0) continue;
-        const double* W = D.We + 18 * (size_t)k; const double* x = D.xp + 6 * (size_t)r;
-        for (int c = 0; c < 3; c++) { double s = 0; for (int a = 0; a < 6; a++) s += W[3 * a + c] * x[a]; cl[c] -= s; }
-    }
-    const double* Di = D.Dinv + (size_t)p * 9;
-    for (int a = 0; a < 3; a++) D.xl[3 * (size_t)p + a] = Di[3 * a] * cl[0] + Di[3 * a + 1] * cl[1] + Di[3 * a + 2] * cl[2];
-}
+__global__ __launch_bounds__(64) void k_gse3_schur(GbaDev D) { gba_schur_body<6>(D); }
+__global__ __launch_bounds__(256) void k_gse3_backsub(GbaDev D) { gba_backsub_body<6>(D); }
 // oplus of every vertex (VertexSE3Expmap::oplusImpl: SE3Quat::exp(update) * estimate; point += xl) and scale = sum x (lambda x + b)
 __global__ __launch_bounds__(256) void k_gse3_update(GbaDev D, double lambda) {
     __shared__ double s_red[4];
@@ -208,11 +124,11 @@ __global__ __launch_bounds__(256) void k_gse3_update(GbaDev D, double lambda) {
             double* k7 = D.kf + (size_t)q * 7;
             double u[6];
             for (int a = 0; a < 6; a++) { u[a] = x[a]; sc += u[a] * (lambda * u[a] + b[a]); }
-            gba_st_se3(k7, se3_mul(se3_exp(u), gba_ld_se3(k7)));
+            se3_oplus7(k7, u);
         }
         if (q < D.np) for (int a = 0; a < 3; a++) { const double x = D.xl[3 * (size_t)q + a]; sc += x * (lambda * x + D.bl[3 * (size_t)q + a]); D.pt[3 * (size_t)q + a] += x; }
     }
-    sc = gba_block_sum(sc, s_red);
+    sc = ba_block_sum(sc, s_red);
     if (threadIdx.x == 0 && sc != 0.0) unsafeAtomicAdd(&D.scal[GBA_S_SCALE], sc);
 }
 
@@ -363,10 +279,11 @@ extern "C" int viorb_global_ba_se3(const viorb_gba_config* cfg, const double* kf
     return VIORB_OK;
 }
 
-// Test hook without a device: global_ba_se3_core.h compiled for the host. One edge's error e3, Jp9 = d e / d point [3][3], Jk18 = d e / d
+// Test hook without a device: gba_se3_error and ba_se3_jac (ba_core.h: the window solve's Jacobians too) compiled for the host. One edge's error e3, Jp9 = d e / d point [3][3], Jk18 = d e / d
 // (omega, upsilon) [3][6] (third rows zero on a monocular edge); returns the edge's dimension, 2 or 3.
 extern "C" int viorb_debug_gba_se3_edge(const double* kf7, const double* pt3, const double* obs4, const double* intr5, double* e3, double* Jp9,
                                         double* Jk18) {
     VIORB_REQUIRE(kf7 && pt3 && obs4 && intr5 && e3 && Jp9 && Jk18, "NULL argument");
-    return gba_se3_lin(kf7, pt3, obs4, intr5, e3, Jp9, Jk18);
+    gba_se3_jac(kf7, pt3, obs4, intr5, Jp9, Jk18);
+    return gba_se3_error(kf7, pt3, obs4, intr5, e3);
 }

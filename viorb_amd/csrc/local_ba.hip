@@ -23,33 +23,34 @@
 #include <cstdlib>
 #include <limits>
 #include "viorb_common.h"
-#include "vio_core.h"
+#include "ba_core.h"
 
 namespace viorb {
 
 struct BaDev {
     int W, NK, NP, NE, np, ld, prev_kf;
     int pose_dim, rows, kf_stride;  // unknowns per key frame (12: PVR+bias, 6: SE3), residual rows per edge (2, or 3 with stereo), doubles per key-frame state
-    double *kf, *kf_bak;            // [NK][22]
+    // layouts as NavState window / SE3 window where they differ (kf_stride 22 / 7, rows 2 / 3)
+    double *kf, *kf_bak;            // [NK][22] navstate / [NK][7] qx qy qz qw tx ty tz of Tcw
     double *pt, *pt_bak;            // [NP][3]
     const int *e_pt, *e_kf;         // [NE]
-    const double *e_obs;            // [NE][3] u v invSigma2
+    const double *e_obs;            // [NE][3] u v invSigma2 / [NE][4] u v uRight invSigma2 (uRight < 0: mono)
     uint8_t* level;                 // [NE]
-    double *err, *Jp, *Jk, *wgt;    // [NE][2], [NE][6], [NE][12], [NE]
+    double *err, *Jp, *Jk, *wgt;    // [NE][rows], [NE][3 rows], [NE][6 rows], [NE]
     double *We;                     // [NE][6][3] = wgt * Jk^T Jp, the edge's block of W (block_solver.hpp's Hpl), written with the linearisation
     int *pr_start, *pr_ent;         // CSR over the key-frame pairs (a >= b, pair a (a + 1) / 2 + b): (edge of a, edge of b) of every point both observe (k_ba_pairs_*)
     const int *pt_start;            // [NP+1]
     const int *kf_start, *kf_list;  // CSR of the edges of each local key frame
     double *Hll, *bl, *Dinv, *db;   // [NP][9], [NP][3], [NP][9], [NP][3] = Dinv bl
     double *Hpp, *bp, *S, *bs, *xp, *xl;
-    const double *preint, *info_pvr; // [W][142], [W][81]
-    double *e_pvr, *e_b;            // [W][9], [W][3]
+    const double *preint, *info_pvr; // [W][142], [W][81] (NavState window)
+    double *e_pvr, *e_b;            // [W][9], [W][3] (NavState window)
     double *scal;                   // [8]: 0 chi2, 1 scale, 2 ok, 3 max diag
     double *ctl;                    // device-side LM control (BA_CTL_*), used when use_ctl != 0: kernels return at once while ctl[HALT] != 0
     int *ticket;                    // block counter of k_ba_f_errors_decide (the last block to add its chi2 takes the trial's decision)
     int use_ctl;                    // and take lambda from ctl[LAMBDA] instead of their argument
     const unsigned long long* abort_host;   // page-locked word the waiting host thread sets when the caller's pbStopFlag goes up (nullptr: no flag)
-    double cam[16], gw[3];
+    double cam[16], gw[3];          // NavState window: cam[16], gw; SE3 window: cam[0..4] = fx fy cx cy bf
     double acc_bias_rw2;
 };
 
@@ -66,17 +67,11 @@ __device__ __forceinline__ bool ba_abort_requested(const BaDev& D) {
 }
 __device__ __forceinline__ double ba_lambda(const BaDev& D, double arg) { return D.use_ctl ? D.ctl[BA_CTL_LAMBDA] : arg; }
 
-__device__ __forceinline__ void ba_edge_geom(const BaDev& D, int k, const double* kfv, const double* ptv, d3& Pc, m33& RwbT, d3& Paux, cam_t& K) {
-    K = ld_cam(D.cam);
-    const pvr s = ld_pvr(kfv + (size_t)D.e_kf[k] * 22);
-    RwbT = tr(qmat(s.q));
-    Paux = mulv(K.Rcb, mulv(RwbT, ld3(ptv + (size_t)D.e_pt[k] * 3) - s.P));
-    Pc = Paux - K.RcbPbc;
+__device__ __forceinline__ nav_geom ba_edge_geom(const BaDev& D, int k, const cam_t& K) {
+    return ba_nav_geom(K, D.kf + (size_t)D.e_kf[k] * 22, D.pt + (size_t)D.e_pt[k] * 3);
 }
 __device__ __forceinline__ int ba_pred(const BaDev& D, int i) { return i == 0 ? D.prev_kf : i - 1; }
-// position, inside a key frame's block of unknowns, of the r-th of the six coordinates a reprojection edge depends on:
-// NavState block = [P V Phi | bias] -> P at 0..2, Phi at 6..8; SE3 block = [omega upsilon] -> 0..5
-__device__ __forceinline__ int ba_loc(const BaDev& D, int r) { return D.pose_dim == 12 ? (r < 3 ? r : r + 3) : r; }
+__device__ __forceinline__ int ba_loc(const BaDev& D, int r) { return loc6(D.pose_dim, r); }
 
 // residuals of the active edges + robust chi2 (mono kernel optional) + IMU / bias factors
 __device__ __forceinline__ void k_ba_errors_body(const BaDev& D, int mono_kernel) {
@@ -84,29 +79,21 @@ __device__ __forceinline__ void k_ba_errors_body(const BaDev& D, int mono_kernel
     __shared__ double s_red[8];
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     double c = 0;
-    const double d_mono = (double)(float)sqrt(5.991);
     if (k < D.NE && D.level[k] == 0) {
-        d3 Pc, Paux; m33 RT; cam_t K;
-        ba_edge_geom(D, k, D.kf, D.pt, Pc, RT, Paux, K);
-        const double e0 = D.e_obs[3 * k] - (Pc.x / Pc.z * K.fx + K.cx), e1 = D.e_obs[3 * k + 1] - (Pc.y / Pc.z * K.fy + K.cy);
-        D.err[2 * k] = e0; D.err[2 * k + 1] = e1;
-        const double chi = D.e_obs[3 * k + 2] * (e0 * e0 + e1 * e1);
-        double r0 = chi, r1;
-        if (mono_kernel) huber(chi, d_mono, &r0, &r1);
-        c = r0;
+        const cam_t K = ld_cam(D.cam);
+        double e[2], r1;
+        ba_nav_error(K, ba_edge_geom(D, k, K).Pc, D.e_obs + 3 * k, e);
+        D.err[2 * k] = e[0]; D.err[2 * k + 1] = e[1];
+        ba_robust(mono_kernel, D.e_obs[3 * k + 2] * (e[0] * e[0] + e[1] * e[1]), ba_delta_mono_window(), &c, &r1);
     }
     if (blockIdx.x == 0 && threadIdx.x < D.W) {               // W <= blockDim.x
         const int i = threadIdx.x, j = ba_pred(D, i);
         if (j >= 0) {
-            const double* ki = D.kf + (size_t)i * 22; const double* kj = D.kf + (size_t)j * 22;
-            double e[9];
-            pvr_edge(ld_pvr(kj), ld_pvr(ki), ld3(kj + 16), ld3(kj + 19), D.preint + (size_t)i * 142, ld3(D.gw), e, nullptr);
-            double chi = 0;
-            for (int a = 0; a < 9; a++) { double t = 0; for (int b = 0; b < 9; b++) t += D.info_pvr[i * 81 + a * 9 + b] * e[b]; chi += e[a] * t; D.e_pvr[i * 9 + a] = e[a]; }
-            double r0, r1; huber(chi, (double)(float)sqrt(21.666), &r0, &r1); c += r0;
-            const d3 eb = (ld3(ki + 13) + ld3(ki + 19)) - (ld3(kj + 13) + ld3(kj + 19));
+            double e[9], rho[2]; d3 eb;                       // the window always applies the Huber kernel to these two factors
+            ba_imu_chi2(D.kf + (size_t)i * 22, D.kf + (size_t)j * 22, D.preint + (size_t)i * 142, D.info_pvr + i * 81, ld3(D.gw), D.acc_bias_rw2, 1, e, &eb, rho);
+            for (int a = 0; a < 9; a++) D.e_pvr[i * 9 + a] = e[a];
             st3(D.e_b + i * 3, eb);
-            huber(dot3(eb, eb) / D.acc_bias_rw2 / D.preint[(size_t)i * 142 + 141], (double)(float)sqrt(16.812), &r0, &r1); c += r0;
+            c += rho[0]; c += rho[1];
         }
     }
 #pragma unroll
@@ -122,40 +109,22 @@ __device__ __forceinline__ void k_ba_lin_points_body(const BaDev& D, int mono_ke
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= D.NP) return;
     double H[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
-    const double d_mono = (double)(float)sqrt(5.991);
     for (int k = D.pt_start[p]; k < D.pt_start[p + 1]; k++) {
         if (D.level[k] != 0) continue;
-        d3 Pc, Paux; m33 RT; cam_t K;
-        ba_edge_geom(D, k, D.kf, D.pt, Pc, RT, Paux, K);
-        const double x = Pc.x, y = Pc.y, z = Pc.z;
-        const double j00 = K.fx / z, j02 = -x / z * K.fx / z, j11 = K.fy / z, j12 = -y / z * K.fy / z;
-        const m33 RR = mul(K.Rcb, RT), HR = mul(hat3(Paux), K.Rcb);
+        const cam_t K = ld_cam(D.cam);
         double Jp[6], Jk[12];
-        // point block: -Jpi * Rcb * Rwb^T ; key-frame block: Jpi * Rcb | -Jpi * hat(Paux) * Rcb
-        Jp[0] = -(j00 * RR.a00 + j02 * RR.a20); Jp[1] = -(j00 * RR.a01 + j02 * RR.a21); Jp[2] = -(j00 * RR.a02 + j02 * RR.a22);
-        Jp[3] = -(j11 * RR.a10 + j12 * RR.a20); Jp[4] = -(j11 * RR.a11 + j12 * RR.a21); Jp[5] = -(j11 * RR.a12 + j12 * RR.a22);
-        Jk[0] = j00 * K.Rcb.a00 + j02 * K.Rcb.a20; Jk[1] = j00 * K.Rcb.a01 + j02 * K.Rcb.a21; Jk[2] = j00 * K.Rcb.a02 + j02 * K.Rcb.a22;
-        Jk[3] = -(j00 * HR.a00 + j02 * HR.a20); Jk[4] = -(j00 * HR.a01 + j02 * HR.a21); Jk[5] = -(j00 * HR.a02 + j02 * HR.a22);
-        Jk[6] = j11 * K.Rcb.a10 + j12 * K.Rcb.a20; Jk[7] = j11 * K.Rcb.a11 + j12 * K.Rcb.a21; Jk[8] = j11 * K.Rcb.a12 + j12 * K.Rcb.a22;
-        Jk[9] = -(j11 * HR.a10 + j12 * HR.a20); Jk[10] = -(j11 * HR.a11 + j12 * HR.a21); Jk[11] = -(j11 * HR.a12 + j12 * HR.a22);
-        const double e0 = D.err[2 * k], e1 = D.err[2 * k + 1], is2 = D.e_obs[3 * k + 2];
-        double r0, r1 = 1;
-        if (mono_kernel) huber(is2 * (e0 * e0 + e1 * e1), d_mono, &r0, &r1);
+        ba_nav_jac(K, ba_edge_geom(D, k, K), Jp, Jk);
+        const double e[2] = {D.err[2 * k], D.err[2 * k + 1]}, is2 = D.e_obs[3 * k + 2];
+        double r0, r1;
+        ba_robust(mono_kernel, is2 * (e[0] * e[0] + e[1] * e[1]), ba_delta_mono_window(), &r0, &r1);
         const double w = r1 * is2;
         D.wgt[k] = w;
         for (int a = 0; a < 6; a++) D.Jp[6 * k + a] = Jp[a];
         for (int a = 0; a < 12; a++) D.Jk[12 * k + a] = Jk[a];
-#pragma unroll
-        for (int r = 0; r < 6; r++)
-#pragma unroll
-            for (int c = 0; c < 3; c++) D.We[18 * (size_t)k + 3 * r + c] = w * (Jk[r] * Jp[c] + Jk[6 + r] * Jp[3 + c]);
-        H[0] += w * (Jp[0] * Jp[0] + Jp[3] * Jp[3]); H[1] += w * (Jp[0] * Jp[1] + Jp[3] * Jp[4]); H[2] += w * (Jp[0] * Jp[2] + Jp[3] * Jp[5]);
-        H[3] += w * (Jp[1] * Jp[1] + Jp[4] * Jp[4]); H[4] += w * (Jp[1] * Jp[2] + Jp[4] * Jp[5]); H[5] += w * (Jp[2] * Jp[2] + Jp[5] * Jp[5]);
-        for (int a = 0; a < 3; a++) b[a] -= w * (Jp[a] * e0 + Jp[3 + a] * e1);
+        ba_w_block<2>(w, Jk, Jp, D.We + 18 * (size_t)k);
+        ba_point_add<2>(H, b, w, Jp, e);
     }
-    double* Ho = D.Hll + (size_t)p * 9;
-    Ho[0] = H[0]; Ho[1] = H[1]; Ho[2] = H[2]; Ho[3] = H[1]; Ho[4] = H[3]; Ho[5] = H[4]; Ho[6] = H[2]; Ho[7] = H[4]; Ho[8] = H[5];
-    for (int a = 0; a < 3; a++) D.bl[(size_t)p * 3 + a] = b[a];
+    ba_point_store(D.Hll + (size_t)p * 9, D.bl + (size_t)p * 3, H, b);
 }
 
 // The same linearisation with one thread per EDGE (Jacobians, weight, W block) and the point blocks summed afterwards by one thread per
@@ -165,22 +134,12 @@ __device__ __forceinline__ void k_ba_lin_edges_body(const BaDev& D, int mono_ker
     if (ba_skip(D)) return;
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= D.NE || D.level[k] != 0) return;
-    const double d_mono = (double)(float)sqrt(5.991);
-    d3 Pc, Paux; m33 RT; cam_t K;
-    ba_edge_geom(D, k, D.kf, D.pt, Pc, RT, Paux, K);
-    const double x = Pc.x, y = Pc.y, z = Pc.z;
-    const double j00 = K.fx / z, j02 = -x / z * K.fx / z, j11 = K.fy / z, j12 = -y / z * K.fy / z;
-    const m33 RR = mul(K.Rcb, RT), HR = mul(hat3(Paux), K.Rcb);
+    const cam_t K = ld_cam(D.cam);
     double Jp[6], Jk[12];
-    Jp[0] = -(j00 * RR.a00 + j02 * RR.a20); Jp[1] = -(j00 * RR.a01 + j02 * RR.a21); Jp[2] = -(j00 * RR.a02 + j02 * RR.a22);
-    Jp[3] = -(j11 * RR.a10 + j12 * RR.a20); Jp[4] = -(j11 * RR.a11 + j12 * RR.a21); Jp[5] = -(j11 * RR.a12 + j12 * RR.a22);
-    Jk[0] = j00 * K.Rcb.a00 + j02 * K.Rcb.a20; Jk[1] = j00 * K.Rcb.a01 + j02 * K.Rcb.a21; Jk[2] = j00 * K.Rcb.a02 + j02 * K.Rcb.a22;
-    Jk[3] = -(j00 * HR.a00 + j02 * HR.a20); Jk[4] = -(j00 * HR.a01 + j02 * HR.a21); Jk[5] = -(j00 * HR.a02 + j02 * HR.a22);
-    Jk[6] = j11 * K.Rcb.a10 + j12 * K.Rcb.a20; Jk[7] = j11 * K.Rcb.a11 + j12 * K.Rcb.a21; Jk[8] = j11 * K.Rcb.a12 + j12 * K.Rcb.a22;
-    Jk[9] = -(j11 * HR.a10 + j12 * HR.a20); Jk[10] = -(j11 * HR.a11 + j12 * HR.a21); Jk[11] = -(j11 * HR.a12 + j12 * HR.a22);
+    ba_nav_jac(K, ba_edge_geom(D, k, K), Jp, Jk);
     const double e0 = D.err[2 * k], e1 = D.err[2 * k + 1], is2 = D.e_obs[3 * k + 2];
-    double r0, r1 = 1;
-    if (mono_kernel) huber(is2 * (e0 * e0 + e1 * e1), d_mono, &r0, &r1);
+    double r0, r1;
+    ba_robust(mono_kernel, is2 * (e0 * e0 + e1 * e1), ba_delta_mono_window(), &r0, &r1);
     const double w = r1 * is2;
     D.wgt[k] = w;
     // 16-byte stores (the blocks are 48, 96 and 144 bytes: 16-byte aligned): the kernel is bound by the number of per-lane memory operations
@@ -191,10 +150,7 @@ __device__ __forceinline__ void k_ba_lin_edges_body(const BaDev& D, int mono_ker
 #pragma unroll
     for (int a = 0; a < 6; a++) Jko[a] = make_double2(Jk[2 * a], Jk[2 * a + 1]);
     double We[18];
-#pragma unroll
-    for (int r = 0; r < 6; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) We[3 * r + c] = w * (Jk[r] * Jp[c] + Jk[6 + r] * Jp[3 + c]);
+    ba_w_block<2>(w, Jk, Jp, We);
 #pragma unroll
     for (int a = 0; a < 9; a++) Wo[a] = make_double2(We[2 * a], We[2 * a + 1]);
 }
@@ -205,15 +161,9 @@ __device__ __forceinline__ void k_ba_hll_body(const BaDev& D, int bid) {
     double H[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
     for (int k = D.pt_start[p]; k < D.pt_start[p + 1]; k++) {
         if (D.level[k] != 0) continue;
-        const double* Jp = D.Jp + 6 * (size_t)k;
-        const double w = D.wgt[k], e0 = D.err[2 * k], e1 = D.err[2 * k + 1];
-        H[0] += w * (Jp[0] * Jp[0] + Jp[3] * Jp[3]); H[1] += w * (Jp[0] * Jp[1] + Jp[3] * Jp[4]); H[2] += w * (Jp[0] * Jp[2] + Jp[3] * Jp[5]);
-        H[3] += w * (Jp[1] * Jp[1] + Jp[4] * Jp[4]); H[4] += w * (Jp[1] * Jp[2] + Jp[4] * Jp[5]); H[5] += w * (Jp[2] * Jp[2] + Jp[5] * Jp[5]);
-        for (int a = 0; a < 3; a++) b[a] -= w * (Jp[a] * e0 + Jp[3 + a] * e1);
+        ba_point_add<2>(H, b, D.wgt[k], D.Jp + 6 * (size_t)k, D.err + 2 * k);
     }
-    double* Ho = D.Hll + (size_t)p * 9;
-    Ho[0] = H[0]; Ho[1] = H[1]; Ho[2] = H[2]; Ho[3] = H[1]; Ho[4] = H[3]; Ho[5] = H[4]; Ho[6] = H[2]; Ho[7] = H[4]; Ho[8] = H[5];
-    for (int a = 0; a < 3; a++) D.bl[(size_t)p * 3 + a] = b[a];
+    ba_point_store(D.Hll + (size_t)p * 9, D.bl + (size_t)p * 3, H, b);
 }
 
 // one workgroup per local key frame: sum of Jk^T w Jk / Jk^T w e over its active edges -> the 6x6 reprojection block of Hpp, bp
@@ -228,27 +178,11 @@ __device__ __forceinline__ void k_ba_hpp_body(const BaDev& D, int i = blockIdx.x
         const int k = D.kf_list[q];
         if (D.level[k] != 0) continue;
         const double* J = D.Jk + (size_t)6 * rows * k; const double* e = D.err + (size_t)rows * k; const double w = D.wgt[k];
-        for (int row = 0; row < rows; row++) {
-            const double* Jr = J + 6 * row; const double er = e[row];
-            int c = 0;
-#pragma unroll
-            for (int r = 0; r < 6; r++)
-#pragma unroll
-                for (int cc = r; cc < 6; cc++) a[c++] += w * (Jr[r] * Jr[cc]);
-#pragma unroll
-            for (int r = 0; r < 6; r++) a[21 + r] -= w * (Jr[r] * er);
-        }
+        for (int row = 0; row < rows; row++) ba_kf_add_row(a, w, J + 6 * row, e[row]);
     }
-#pragma unroll
-    for (int k = 0; k < 27; k++) {
-        double v = a[k];
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-        if ((t & 63) == 0) s_red[t >> 6][k] = v;
-    }
-    __syncthreads();
+    ba_kf_reduce(a, s_red);
     if (t < 27) {
-        const double v = s_red[0][t] + s_red[1][t] + s_red[2][t] + s_red[3][t];
+        const double v = ba_kf_sum(s_red, t);
         const int base = D.pose_dim * i, n = D.np;
         if (t < 21) {
             int kk = 0, rr = 0, cc = 0;
@@ -269,17 +203,13 @@ __device__ __forceinline__ void k_ba_imu_body(const BaDev& D, int i = blockIdx.x
     if (j < 0) return;
     const double* ki = D.kf + (size_t)i * 22; const double* kj = D.kf + (size_t)j * 22;
     if (t == 0) {
-        pvr_edge(ld_pvr(kj), ld_pvr(ki), ld3(kj + 16), ld3(kj + 19), D.preint + (size_t)i * 142, ld3(D.gw), e, J);
-        double chi = 0;
-        for (int a = 0; a < 9; a++) { double s = 0; for (int b = 0; b < 9; b++) s += D.info_pvr[i * 81 + a * 9 + b] * e[b]; chi += e[a] * s; }
-        double r0, r1; huber(chi, (double)(float)sqrt(21.666), &r0, &r1); s_w = r1;
+        d3 eb; double w_pvr, wb;                              // the window always applies the Huber kernel to these two factors
+        ba_imu_weights(ki, kj, D.preint + (size_t)i * 142, D.info_pvr + i * 81, ld3(D.gw), D.acc_bias_rw2, 1, e, J, &w_pvr, &eb, &wb);
+        s_w = w_pvr;
         for (int c = 0; c < 9; c++) { map[c] = j < D.W ? 12 * j + c : -1; map[9 + c] = 12 * i + c; }
         for (int c = 0; c < 3; c++) map[18 + c] = j < D.W ? 12 * j + 9 + c : -1;
         // bias factor
-        const d3 eb = (ld3(ki + 13) + ld3(ki + 19)) - (ld3(kj + 13) + ld3(kj + 19));
-        const double binfo = 1.0 / D.acc_bias_rw2 / D.preint[(size_t)i * 142 + 141];
-        huber(binfo * dot3(eb, eb), (double)(float)sqrt(16.812), &r0, &r1);
-        const double wb = r1 * binfo, ev[3] = {eb.x, eb.y, eb.z};
+        const double ev[3] = {eb.x, eb.y, eb.z};
         for (int c = 0; c < 3; c++) {
             const int ic = 12 * i + 9 + c, jc = j < D.W ? 12 * j + 9 + c : -1;
             atomicAdd(&D.Hpp[(size_t)ic * n + ic], wb); atomicAdd(&D.bp[ic], -wb * ev[c]);
@@ -287,7 +217,7 @@ __device__ __forceinline__ void k_ba_imu_body(const BaDev& D, int i = blockIdx.x
         }
     }
     __syncthreads();
-    for (int q = t; q < 189; q += blockDim.x) { const int r = q / 21, c = q % 21; double s = 0; for (int k = 0; k < 9; k++) s += D.info_pvr[i * 81 + r * 9 + k] * J[k * 21 + c]; OJ[q] = s; }
+    ba_omega_j(D.info_pvr + i * 81, J, OJ, t, blockDim.x);
     __syncthreads();
     const double w = s_w;
     for (int q = t; q < 441 + 21; q += blockDim.x) {
@@ -330,14 +260,7 @@ __device__ __forceinline__ void k_ba_dinv_body(const BaDev& D, double lambda_arg
     const double lambda = ba_lambda(D, lambda_arg);
     const int p = bid * blockDim.x + threadIdx.x;
     if (p >= D.NP) return;
-    const double* H = D.Hll + (size_t)p * 9;
-    const double a = H[0] + lambda, b = H[1], c = H[2], d = H[4] + lambda, e = H[5], f = H[8] + lambda;
-    const double det = a * (d * f - e * e) - b * (b * f - c * e) + c * (b * e - c * d), id = 1.0 / det;
-    const double i00 = (d * f - e * e) * id, i01 = (c * e - b * f) * id, i02 = (b * e - c * d) * id, i11 = (a * f - c * c) * id, i12 = (b * c - a * e) * id, i22 = (a * d - b * b) * id;
-    double* Di = D.Dinv + (size_t)p * 9;
-    Di[0] = i00; Di[1] = i01; Di[2] = i02; Di[3] = i01; Di[4] = i11; Di[5] = i12; Di[6] = i02; Di[7] = i12; Di[8] = i22;
-    const double b0 = D.bl[3 * p], b1 = D.bl[3 * p + 1], b2 = D.bl[3 * p + 2];
-    D.db[3 * p] = i00 * b0 + i01 * b1 + i02 * b2; D.db[3 * p + 1] = i01 * b0 + i11 * b1 + i12 * b2; D.db[3 * p + 2] = i02 * b0 + i12 * b1 + i22 * b2;
+    ba_point_inverse(D.Hll + (size_t)p * 9, lambda, D.bl + 3 * p, D.Dinv + (size_t)p * 9, D.db + 3 * p);
 }
 // Schur complement of the point block (block_solver.hpp:381-432), gathered per key-frame PAIR: wavefront (a, b), a >= b, owns the 6 x 6 block
 // S[a][b] -= sum_p (W_pa Dinv_p) W_pb^T over the points p both observe (W = wgt Jk^T Jp from the linearisation, Dinv from k_ba_dinv; the
@@ -685,11 +608,8 @@ __device__ __forceinline__ void k_ba_backsub_body(const BaDev& D, double lambda_
         sc = x0 * (lambda * x0 + D.bl[3 * p]) + x1 * (lambda * x1 + D.bl[3 * p + 1]) + x2 * (lambda * x2 + D.bl[3 * p + 2]);
     }
     if (blockIdx.x == 0) for (int q = threadIdx.x; q < D.np; q += blockDim.x) sc += D.xp[q] * (lambda * D.xp[q] + D.bp[q]);
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) sc += __shfl_xor(sc, d);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = sc;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(&D.scal[1], s_red[0] + s_red[1] + s_red[2] + s_red[3]);
+    sc = ba_block_sum(sc, s_red);
+    if (threadIdx.x == 0) atomicAdd(&D.scal[1], sc);
 }
 
 __device__ __forceinline__ void k_ba_update_body(const BaDev& D) {
@@ -715,10 +635,9 @@ __device__ __forceinline__ void k_ba_restore_body(const BaDev& D) {
 __device__ __forceinline__ void k_ba_gate_body(const BaDev& D, uint8_t* out, int set_level) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= D.NE) return;
-    d3 Pc, Paux; m33 RT; cam_t K;
-    ba_edge_geom(D, k, D.kf, D.pt, Pc, RT, Paux, K);
+    const d3 Pc = ba_edge_geom(D, k, ld_cam(D.cam)).Pc;
     const double chi = D.e_obs[3 * k + 2] * (D.err[2 * k] * D.err[2 * k] + D.err[2 * k + 1] * D.err[2 * k + 1]);
-    const int bad = (chi > 5.991 || !(Pc.z > 0.0)) ? 1 : 0;
+    const int bad = (chi > BA_GATE_CHI2_MONO || !(Pc.z > 0.0)) ? 1 : 0;
     if (set_level) { if (bad) D.level[k] = 1; } else out[k] = (uint8_t)bad;
 }
 
@@ -893,7 +812,6 @@ __global__ void k_bab_phase(const BaDev* __restrict__ Dv, int nwin, int* __restr
 // ---- vision-only LocalBundleAdjustment (reference src/Optimizer.cc:3980-4311): SE3 key frames (kf = qx qy qz qw tx ty tz of Tcw),
 // EdgeSE3ProjectXYZ / EdgeStereoSE3ProjectXYZ (Thirdparty/g2o/g2o/types/types_six_dof_expmap.cpp:66-250). e_obs[k] = u v uRight invSigma2
 // (uRight < 0: mono); cam[0..4] = fx fy cx cy bf. Three residual rows per edge (the third is zero for mono edges).
-__device__ __forceinline__ se3q ba_ld_se3(const double* k) { se3q s; s.r = mkq(k[0], k[1], k[2], k[3]); s.t = mk3(k[4], k[5], k[6]); return s; }
 __device__ __forceinline__ void k_ba_se3_errors_body(const BaDev& D, int kernels) {
     if (ba_skip(D)) return;
     __shared__ double s_red[8];
@@ -902,12 +820,11 @@ __device__ __forceinline__ void k_ba_se3_errors_body(const BaDev& D, int kernels
     if (k < D.NE && D.level[k] == 0) {
         const double* ob = D.e_obs + 4 * (size_t)k;
         double e[3];
-        se3_edge(ba_ld_se3(D.kf + (size_t)D.e_kf[k] * 7), ld3(D.pt + (size_t)D.e_pt[k] * 3), ob[0], ob[1], ob[2], D.cam[0], D.cam[1], D.cam[2], D.cam[3], D.cam[4], false, e, nullptr);
+        se3_edge(se3_ld7(D.kf + (size_t)D.e_kf[k] * 7), ld3(D.pt + (size_t)D.e_pt[k] * 3), ob[0], ob[1], ob[2], D.cam[0], D.cam[1], D.cam[2], D.cam[3], D.cam[4], false, e, nullptr);
         D.err[3 * k] = e[0]; D.err[3 * k + 1] = e[1]; D.err[3 * k + 2] = e[2];
         const double chi = ob[3] * (e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
-        double r0 = chi, r1;
-        if (kernels) huber(chi, (double)(float)sqrt(ob[2] < 0 ? 5.991 : 7.815), &r0, &r1);
-        c = r0;
+        double r1;
+        ba_robust(kernels, chi, ba_se3_stereo(ob) ? ba_delta_stereo() : ba_delta_mono_window(), &c, &r1);
     }
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
@@ -924,49 +841,20 @@ __device__ __forceinline__ void k_ba_se3_lin_points_body(const BaDev& D, int ker
     for (int k = D.pt_start[p]; k < D.pt_start[p + 1]; k++) {
         if (D.level[k] != 0) continue;
         const double* ob = D.e_obs + 4 * (size_t)k;
-        const bool stereo = !(ob[2] < 0);
-        const se3q T = ba_ld_se3(D.kf + (size_t)D.e_kf[k] * 7);
-        const d3 pc = se3_map(T, ld3(D.pt + (size_t)p * 3));
-        const m33 R = qmat(T.r);
-        const double x = pc.x, y = pc.y, z = pc.z, z_2 = z * z;
+        const bool stereo = ba_se3_stereo(ob);
         double Jp[9], Jk[18];
-        const double Rr[9] = {R.a00, R.a01, R.a02, R.a10, R.a11, R.a12, R.a20, R.a21, R.a22};
-        if (!stereo) {
-            const double t0[3] = {fx, 0, -x / z * fx}, t1[3] = {0, fy, -y / z * fy};
-            for (int c = 0; c < 3; c++) {
-                double s0 = 0, s1 = 0;
-                for (int q = 0; q < 3; q++) { s0 += (-1. / z * t0[q]) * Rr[3 * q + c]; s1 += (-1. / z * t1[q]) * Rr[3 * q + c]; }
-                Jp[c] = s0; Jp[3 + c] = s1; Jp[6 + c] = 0;
-            }
-        } else {
-            for (int c = 0; c < 3; c++) {
-                Jp[c] = -fx * Rr[c] / z + fx * x * Rr[6 + c] / z_2;
-                Jp[3 + c] = -fy * Rr[3 + c] / z + fy * y * Rr[6 + c] / z_2;
-                Jp[6 + c] = Jp[c] - bf * Rr[6 + c] / z_2;
-            }
-        }
-        Jk[0] = x * y / z_2 * fx; Jk[1] = -(1 + (x * x / z_2)) * fx; Jk[2] = y / z * fx; Jk[3] = -1. / z * fx; Jk[4] = 0; Jk[5] = x / z_2 * fx;
-        Jk[6] = (1 + y * y / z_2) * fy; Jk[7] = -x * y / z_2 * fy; Jk[8] = -x / z * fy; Jk[9] = 0; Jk[10] = -1. / z * fy; Jk[11] = y / z_2 * fy;
-        if (stereo) { Jk[12] = Jk[0] - bf * y / z_2; Jk[13] = Jk[1] + bf * x / z_2; Jk[14] = Jk[2]; Jk[15] = Jk[3]; Jk[16] = 0; Jk[17] = Jk[5] - bf / z_2; }
-        else { for (int q = 12; q < 18; q++) Jk[q] = 0; }
-        const double e0 = D.err[3 * k], e1 = D.err[3 * k + 1], e2 = D.err[3 * k + 2], is2 = ob[3];
-        double r0, r1 = 1;
-        if (kernels) huber(is2 * (e0 * e0 + e1 * e1 + e2 * e2), (double)(float)sqrt(stereo ? 7.815 : 5.991), &r0, &r1);
+        ba_se3_jac(se3_ld7(D.kf + (size_t)D.e_kf[k] * 7), ld3(D.pt + (size_t)p * 3), stereo, fx, fy, bf, Jp, Jk);
+        const double e[3] = {D.err[3 * k], D.err[3 * k + 1], D.err[3 * k + 2]}, is2 = ob[3];
+        double r0, r1;
+        ba_robust(kernels, is2 * (e[0] * e[0] + e[1] * e[1] + e[2] * e[2]), stereo ? ba_delta_stereo() : ba_delta_mono_window(), &r0, &r1);
         const double w = r1 * is2;
         D.wgt[k] = w;
         for (int a = 0; a < 9; a++) D.Jp[9 * (size_t)k + a] = Jp[a];
         for (int a = 0; a < 18; a++) D.Jk[18 * (size_t)k + a] = Jk[a];
-#pragma unroll
-        for (int r = 0; r < 6; r++)
-#pragma unroll
-            for (int c = 0; c < 3; c++) D.We[18 * (size_t)k + 3 * r + c] = w * (Jk[r] * Jp[c] + Jk[6 + r] * Jp[3 + c] + Jk[12 + r] * Jp[6 + c]);
-        H[0] += w * (Jp[0] * Jp[0] + Jp[3] * Jp[3] + Jp[6] * Jp[6]); H[1] += w * (Jp[0] * Jp[1] + Jp[3] * Jp[4] + Jp[6] * Jp[7]); H[2] += w * (Jp[0] * Jp[2] + Jp[3] * Jp[5] + Jp[6] * Jp[8]);
-        H[3] += w * (Jp[1] * Jp[1] + Jp[4] * Jp[4] + Jp[7] * Jp[7]); H[4] += w * (Jp[1] * Jp[2] + Jp[4] * Jp[5] + Jp[7] * Jp[8]); H[5] += w * (Jp[2] * Jp[2] + Jp[5] * Jp[5] + Jp[8] * Jp[8]);
-        for (int a = 0; a < 3; a++) b[a] -= w * (Jp[a] * e0 + Jp[3 + a] * e1 + Jp[6 + a] * e2);
+        ba_w_block<3>(w, Jk, Jp, D.We + 18 * (size_t)k);
+        ba_point_add<3>(H, b, w, Jp, e);
     }
-    double* Ho = D.Hll + (size_t)p * 9;
-    Ho[0] = H[0]; Ho[1] = H[1]; Ho[2] = H[2]; Ho[3] = H[1]; Ho[4] = H[3]; Ho[5] = H[4]; Ho[6] = H[2]; Ho[7] = H[4]; Ho[8] = H[5];
-    for (int a = 0; a < 3; a++) D.bl[(size_t)p * 3 + a] = b[a];
+    ba_point_store(D.Hll + (size_t)p * 9, D.bl + (size_t)p * 3, H, b);
 }
 __device__ __forceinline__ void k_ba_se3_update_body(const BaDev& D) {
     if (ba_skip(D)) return;
@@ -974,8 +862,7 @@ __device__ __forceinline__ void k_ba_se3_update_body(const BaDev& D) {
     if (q < D.W) {                                                   // VertexSE3Expmap::oplusImpl: T <- exp(update) * T
         double* k = D.kf + (size_t)q * 7;
         for (int c = 0; c < 7; c++) D.kf_bak[(size_t)q * 7 + c] = k[c];
-        const se3q s = se3_mul(se3_exp(D.xp + 6 * q), ba_ld_se3(k));
-        k[0] = s.r.x; k[1] = s.r.y; k[2] = s.r.z; k[3] = s.r.w; k[4] = s.t.x; k[5] = s.t.y; k[6] = s.t.z;
+        se3_oplus7(k, D.xp + 6 * q);
     }
     if (q < D.NP) for (int c = 0; c < 3; c++) { D.pt_bak[3 * q + c] = D.pt[3 * q + c]; D.pt[3 * q + c] += D.xl[3 * q + c]; }
 }
@@ -984,9 +871,9 @@ __device__ __forceinline__ void k_ba_se3_gate_body(const BaDev& D, uint8_t* out,
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= D.NE) return;
     const double* ob = D.e_obs + 4 * (size_t)k;
-    const d3 pc = se3_map(ba_ld_se3(D.kf + (size_t)D.e_kf[k] * 7), ld3(D.pt + (size_t)D.e_pt[k] * 3));
+    const d3 pc = se3_map(se3_ld7(D.kf + (size_t)D.e_kf[k] * 7), ld3(D.pt + (size_t)D.e_pt[k] * 3));
     const double chi = ob[3] * (D.err[3 * k] * D.err[3 * k] + D.err[3 * k + 1] * D.err[3 * k + 1] + D.err[3 * k + 2] * D.err[3 * k + 2]);
-    const int bad = (chi > (ob[2] < 0 ? 5.991 : 7.815) || !(pc.z > 0.0)) ? 1 : 0;
+    const int bad = (chi > (ba_se3_stereo(ob) ? BA_GATE_CHI2_STEREO : BA_GATE_CHI2_MONO) || !(pc.z > 0.0)) ? 1 : 0;
     if (set_level) { if (bad) D.level[k] = 1; } else out[k] = (uint8_t)bad;
 }
 __global__ void k_ba_se3_errors(BaDev D, int kernels) { k_ba_se3_errors_body(D, kernels); }
@@ -1049,11 +936,8 @@ __device__ __forceinline__ void k_ba_backsub8_update_body(const BaDev& D) {
         for (int c = 0; c < 3; c++) { D.pt_bak[3 * p + c] = D.pt[3 * p + c]; D.pt[3 * p + c] += xs[c]; }      // k_ba_*_update_body's point part
     }
     if (blockIdx.x == 0) for (int q = threadIdx.x; q < D.np; q += blockDim.x) sc += D.xp[q] * (lambda * D.xp[q] + D.bp[q]);
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) sc += __shfl_xor(sc, d);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = sc;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(&D.scal[1], s_red[0] + s_red[1] + s_red[2] + s_red[3]);
+    sc = ba_block_sum(sc, s_red);
+    if (threadIdx.x == 0) atomicAdd(&D.scal[1], sc);
     if (g < D.W) {                                                       // the key frames (k_ba_update_body / k_ba_se3_update_body)
         if (D.pose_dim == 12) {
             double* k = D.kf + (size_t)g * 22;
@@ -1064,8 +948,7 @@ __device__ __forceinline__ void k_ba_backsub8_update_body(const BaDev& D) {
         } else {
             double* k = D.kf + (size_t)g * 7;
             for (int c = 0; c < 7; c++) D.kf_bak[(size_t)g * 7 + c] = k[c];
-            const se3q s = se3_mul(se3_exp(D.xp + 6 * g), ba_ld_se3(k));
-            k[0] = s.r.x; k[1] = s.r.y; k[2] = s.r.z; k[3] = s.r.w; k[4] = s.t.x; k[5] = s.t.y; k[6] = s.t.z;
+            se3_oplus7(k, D.xp + 6 * g);
         }
     }
 }
