@@ -923,6 +923,9 @@ int viorb_debug_gba_last_trials(uint8_t* accepted, int cap, int* n);
 /* The two-view (monocular) initialiser (Initializer::Initialize): viorb_two_view_init and its stages, in a header of their own. */
 #include "viorb_two_view.h"
 
+/* The Sim3 RANSAC solver of loop closing (Sim3Solver): viorb_sim3_ransac and its stages, in a header of their own. */
+#include "viorb_sim3.h"
+
 /* ---- Place recognition: BowVector, ORBVocabulary::score and KeyFrameDatabase (reference src/KeyFrameDatabase.cc:40-309) ------------
  * The question relocalisation (src/Tracking.cc:2134) and loop detection (src/LoopClosing.cc:148-165) begin with: which stored key frames
  * look like this one? Integer, float-compare and ordered-sum arithmetic only: every output equals the reference's bit for bit.

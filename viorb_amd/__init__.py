@@ -12,3 +12,5 @@ from .vi_init import PreintegrateIntervals, PreintegrateIntervalsBatch, Optimize
 from .global_ba import GlobalBundleAdjustmentNavState, GlobalBundleAdjustmentNavStateDevice, gba_workspace_bytes, GlobalBundleAdjustmentSE3, GlobalBundleAdjustmentSE3Device, gba_se3_workspace_bytes  # noqa: F401
 from .place import BowVector, BowVector_device, BowScore, BowScorePairs, KeyFrameDatabase, pack_bows  # noqa: F401
 from .two_view import TwoViewInit, TwoViewBatch, draw_sets, two_view_config  # noqa: F401
+from .sim3 import Sim3Batch, sim3_ransac, sim3_config, optimize_sim3, optimize_sim3_batch, ransac_iterations  # noqa: F401
+from .sim3 import draw_sets as sim3_draw_sets  # noqa: F401  (draw_sets is the two-view initialiser's)

@@ -1,6 +1,6 @@
-"""ctypes declarations of include/viorb.h and of the headers it includes, viorb_global_ba_se3.h and viorb_two_view.h (kept 1:1; tests/test_host_hooks.py checks that every
+"""ctypes declarations of include/viorb.h and of the headers it includes, viorb_global_ba_se3.h, viorb_two_view.h and viorb_sim3.h (kept 1:1; tests/test_host_hooks.py checks that every
 declared entry point of viorb.h is exported, has a signature here and that the argument counts agree; tests/test_global_ba_se3_ref.py
-does the same for SIGNATURES_GLOBAL_BA_SE3, tests/test_two_view_ref.py for SIGNATURES_TWO_VIEW)."""
+does the same for SIGNATURES_GLOBAL_BA_SE3, tests/test_two_view_ref.py for SIGNATURES_TWO_VIEW, tests/test_sim3_ref.py for SIGNATURES_SIM3)."""
 import ctypes as C
 import os
 import numpy as np
@@ -86,6 +86,29 @@ TWO_VIEW_OUTPUT_FIELDS = ("status", "reason", "n_matches", "scores", "best_iter"
 class TwoViewOutputs(C.Structure):
     """viorb_two_view_outputs (include/viorb_two_view.h)."""
     _fields_ = [(n, C.c_void_p) for n in TWO_VIEW_OUTPUT_FIELDS]
+
+
+class Sim3Inputs(C.Structure):
+    """viorb_sim3_inputs (include/viorb_sim3.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("X1c", "X2c", "sigma2_1", "sigma2_2", "K1", "K2", "n")] + [("cap", C.c_int32)]
+
+
+class Sim3OptInputs(C.Structure):
+    """viorb_sim3_opt_inputs (include/viorb_sim3.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("S12", "X1c", "X2c", "obs1", "obs2", "inv_sigma2_1", "inv_sigma2_2", "valid", "K1", "K2", "n")] + [("cap", C.c_int32)]
+
+
+class Sim3Config(C.Structure):
+    """viorb_sim3_config (include/viorb_sim3.h)."""
+    _fields_ = [("iterations", C.c_int32), ("min_inliers", C.c_int32), ("fix_scale", C.c_int32), ("iterations_per_call", C.c_int32)]
+
+
+SIM3_OUTPUT_FIELDS = ("status", "iterations_done", "best_inliers", "best_iter", "R12", "t12", "s12", "T12", "n_inliers", "inliers")
+
+
+class Sim3Outputs(C.Structure):
+    """viorb_sim3_outputs (include/viorb_sim3.h)."""
+    _fields_ = [(n, C.c_void_p) for n in SIM3_OUTPUT_FIELDS]
 
 
 class TrackerConfig(C.Structure):
@@ -288,6 +311,26 @@ SIGNATURES_TWO_VIEW = {
     "viorb_debug_two_view_accept": (i32, [i32, vp, vp, i32, f32, i32, vp]),
 }
 
+# mirrors include/viorb_sim3.h (the Sim3 RANSAC solver); tests/test_sim3_ref.py checks names and argument counts against it
+_s3_in = [PP(Sim3Inputs), PP(Sim3Config)]
+SIGNATURES_SIM3 = {
+    "viorb_sim3_draw_sets": (i32, [i32, i32, C.c_uint64, vp]),
+    "viorb_sim3_ransac_iterations": (i32, [i32, C.c_double, i32, i32]),
+    "viorb_sim3_workspace_bytes": (sz, [i32, i32, i32]),
+    "viorb_sim3_hypotheses_device": (i32, _s3_in + [vp, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "viorb_sim3_inliers_device": (i32, _s3_in + [i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "viorb_sim3_select_device": (i32, [PP(Sim3Config), vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+    "viorb_sim3_ransac_device": (i32, _s3_in + [vp, vp, vp, vp, i32, PP(Sim3Outputs), vp, sz, vp]),
+    "viorb_sim3_ransac": (i32, [PP(Sim3Config), vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, PP(Sim3Outputs)]),
+    "viorb_optimize_sim3_device": (i32, [PP(Sim3OptInputs), f32, i32, i32, vp, vp, vp, vp, vp]),
+    "viorb_optimize_sim3": (i32, [vp, f32, i32] + [vp] * 9 + [i32, vp, vp, vp, vp]),
+    "viorb_debug_sim3_exp": (i32, [vp, vp, vp, vp]),
+    "viorb_debug_sim3_edges": (i32, [vp] * 7 + [i32, vp, vp]),
+    "viorb_debug_sim3_horn": (i32, [vp, vp, i32, vp, vp, vp]),
+    "viorb_debug_sim3_inlier": (i32, [vp, vp, f32, vp, vp, vp, vp, f32, f32, vp, vp]),
+    "viorb_debug_sim3_select": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+}
+
 _lib = None
 
 
@@ -307,7 +350,8 @@ def lib():
         except Exception:
             pass
         L = C.CDLL(SO_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GLOBAL_BA_SE3.items()) + list(SIGNATURES_TWO_VIEW.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GLOBAL_BA_SE3.items()) + list(SIGNATURES_TWO_VIEW.items()) \
+                + list(SIGNATURES_SIM3.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

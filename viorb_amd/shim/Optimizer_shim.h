@@ -374,5 +374,40 @@ inline void global_bundle_adjustment(MapT* pMap, int nIterations, bool* pbStopFl
     bundle_adjustment(pMap->GetAllKeyFrames(), pMap->GetAllMapPoints(), nIterations, pbStopFlag, stop_mirror, nLoopKF, bRobust, pose_to_qt, qt_to_pose, info);
 }
 
+// Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (src/Optimizer.cc:4589-4784) over viorb_optimize_sim3. The
+// snapshot of :4642-4721 is built here: entry i holds the map point of key frame 1 at key point i and its match in camera coordinates
+// (the reference's own expression), both key points and their mvInvLevelSigma2; `valid` is the test of :4644-4657. S12 = r(x y z w) t s
+// of g2oS12 goes in and comes out as eight doubles (sim3_get / sim3_set adapt g2o::Sim3); vpMatches1 is nulled where keep is 0.
+template <class KeyFrameT, class MapPointT, class Sim3T, class GetS, class SetS>
+inline int optimize_sim3(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches1, Sim3T& g2oS12, const float th2, const bool bFixScale,
+                         GetS sim3_get, SetS sim3_set) {
+    const int N = (int)vpMatches1.size();
+    const std::vector<MapPointT*> vpMapPoints1 = pKF1->GetMapPointMatches();
+    const cv::Mat R1w = pKF1->GetRotation(), t1w = pKF1->GetTranslation(), R2w = pKF2->GetRotation(), t2w = pKF2->GetTranslation();
+    std::vector<float> X1(3 * (size_t)N + 3), X2(3 * (size_t)N + 3), o1(2 * (size_t)N + 2), o2(2 * (size_t)N + 2), w1((size_t)N + 1), w2((size_t)N + 1);
+    std::vector<uint8_t> valid((size_t)N + 1, 0), keep((size_t)N + 1, 0);
+    for (int i = 0; i < N; i++) {
+        MapPointT* pMP2 = vpMatches1[i];
+        MapPointT* pMP1 = pMP2 ? vpMapPoints1[i] : (MapPointT*)0;
+        if (!pMP1 || pMP1->isBad() || pMP2->isBad()) continue;
+        const int i2 = pMP2->GetIndexInKeyFrame(pKF2);
+        if (i2 < 0) continue;
+        const cv::Mat P1 = R1w * pMP1->GetWorldPos() + t1w, P2 = R2w * pMP2->GetWorldPos() + t2w;
+        for (int r = 0; r < 3; r++) { X1[3 * i + r] = P1.template at<float>(r); X2[3 * i + r] = P2.template at<float>(r); }
+        o1[2 * i] = pKF1->mvKeysUn[i].pt.x; o1[2 * i + 1] = pKF1->mvKeysUn[i].pt.y; o2[2 * i] = pKF2->mvKeysUn[i2].pt.x; o2[2 * i + 1] = pKF2->mvKeysUn[i2].pt.y;
+        w1[i] = pKF1->mvInvLevelSigma2[pKF1->mvKeysUn[i].octave]; w2[i] = pKF2->mvInvLevelSigma2[pKF2->mvKeysUn[i2].octave];
+        valid[i] = 1;
+    }
+    const float K1[4] = {pKF1->mK.template at<float>(0, 0), pKF1->mK.template at<float>(1, 1), pKF1->mK.template at<float>(0, 2), pKF1->mK.template at<float>(1, 2)};
+    const float K2[4] = {pKF2->mK.template at<float>(0, 0), pKF2->mK.template at<float>(1, 1), pKF2->mK.template at<float>(0, 2), pKF2->mK.template at<float>(1, 2)};
+    double S[8], So[8], info[8]; int32_t nIn = 0;
+    sim3_get(g2oS12, S);
+    check(viorb_optimize_sim3(S, th2, bFixScale ? 1 : 0, &X1[0], &X2[0], &o1[0], &o2[0], &w1[0], &w2[0], &valid[0], K1, K2, N, So, &keep[0], &nIn, info),
+          "Optimizer::OptimizeSim3");
+    for (int i = 0; i < N; i++) if (valid[i] && !keep[i]) vpMatches1[i] = static_cast<MapPointT*>(0);
+    if (info[0] - info[1] >= 10) sim3_set(g2oS12, So);            // :4754 returns before g2oS12 is written
+    return nIn;
+}
+
 } // namespace viorb_shim
 #endif

@@ -1096,3 +1096,41 @@ def make_place_descriptors(seed, voc, N=24, per_kf=100, noise_bits=2, place_len=
         desc.append(d)
     connected, erased, covis10 = _place_graph(rng, N, erase_frac, n_connected)
     return dict(desc=desc, connected=connected, erased=erased, covis10=covis10)
+
+
+def make_sim3_problem(seed, kind="general", n=300, outlier_frac=0.0, noise_px=0.5, noise_m=0.002, w=752, h=480):
+    """Two key frames that see a common cloud, for the Sim3 solver (Sim3Solver) and OptimizeSim3: X1c, X2c [n,3] float32, the matched map
+    points in the frame of their own camera, related by X1 = s12 R12 X2 + t12 (ground truth R12, t12, s12) up to noise_m metres of
+    Gaussian noise on each map point; obs1, obs2 [n,2] the undistorted key points (the true projections with noise_px pixels of noise),
+    octave1, octave2 [n], sigma2_1, sigma2_2 [n] = 1.2^(2 octave), K1 = K2 = fx fy cx cy. kind: "general" (about 20 degrees, s12 = 1.3),
+    "fix_scale" (s12 = 1, as with a stereo or RGB-D map) and "small_rotation" (about 0.5 degrees, s12 = 1.05). outlier_frac of the
+    correspondences pair a point of camera 1 with the wrong point of camera 2 (true_inlier [n] = 0). numpy only."""
+    rng = np.random.Generator(np.random.PCG64(seed + 515151))
+    fx, fy, cx, cy = [float(np.float32(v)) for v in (EUROC_K["fx"], EUROC_K["fy"], EUROC_K["cx"], EUROC_K["cy"])]
+    angle, s12 = dict(general=(np.radians(20.0), 1.3), fix_scale=(np.radians(12.0), 1.0), small_rotation=(np.radians(0.5), 1.05))[kind]
+    axis = rng.normal(0, 1, 3); axis /= np.linalg.norm(axis)
+    R12 = _rotvec_to_R(axis * angle)
+    t12 = np.array([0.6, -0.1, 0.25]) + rng.normal(0, 0.05, 3)
+    m = 12 * n + 64
+    uv1 = np.stack([rng.uniform(15, w - 15, m), rng.uniform(15, h - 15, m)], 1)
+    z = rng.uniform(2.0, 10.0, m)
+    X1 = np.stack([(uv1[:, 0] - cx) / fx * z, (uv1[:, 1] - cy) / fy * z, z], 1)
+    X2 = (X1 - t12) @ R12 / s12                                    # R12^T (X1 - t12) / s12
+    uv2 = np.stack([fx * X2[:, 0] / X2[:, 2] + cx, fy * X2[:, 1] / X2[:, 2] + cy], 1)
+    ok = (X2[:, 2] > 1.0) & (uv2[:, 0] > 15) & (uv2[:, 0] < w - 15) & (uv2[:, 1] > 15) & (uv2[:, 1] < h - 15)
+    X1, X2, uv1, uv2 = X1[ok][:n], X2[ok][:n], uv1[ok][:n], uv2[ok][:n]
+    assert len(X1) == n, "not enough points visible in both cameras"
+    true_inlier = np.ones(n, np.uint8)
+    out = rng.permutation(n)[:int(round(outlier_frac * n))]
+    if len(out):
+        other = (out + rng.integers(1, n, len(out))) % n           # never itself
+        X2, uv2 = X2.copy(), uv2.copy()
+        X2[out], uv2[out] = X2[other], uv2[other]
+        true_inlier[out] = 0
+    o1, o2 = rng.integers(0, 8, n), rng.integers(0, 8, n)
+    sig = lambda o: (np.float32(1.2) ** o.astype(np.float32)) ** 2
+    return dict(X1c=(X1 + rng.normal(0, noise_m, (n, 3))).astype(np.float32), X2c=(X2 + rng.normal(0, noise_m, (n, 3))).astype(np.float32),
+                obs1=(uv1 + rng.normal(0, noise_px, (n, 2))).astype(np.float32), obs2=(uv2 + rng.normal(0, noise_px, (n, 2))).astype(np.float32),
+                octave1=o1.astype(np.int32), octave2=o2.astype(np.int32), sigma2_1=sig(o1).astype(np.float32), sigma2_2=sig(o2).astype(np.float32),
+                K1=np.array([fx, fy, cx, cy], np.float32), K2=np.array([fx, fy, cx, cy], np.float32), R12=R12, t12=t12, s12=float(s12),
+                true_inlier=true_inlier, kind=kind)
