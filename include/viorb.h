@@ -926,6 +926,10 @@ int viorb_debug_gba_last_trials(uint8_t* accepted, int cap, int* n);
 /* The Sim3 RANSAC solver of loop closing (Sim3Solver): viorb_sim3_ransac and its stages, in a header of their own. */
 #include "viorb_sim3.h"
 
+/* The matchers of loop closing that project through a similarity (SearchBySim3, SearchByProjection and Fuse by Scw) and the handle-free
+ * key-frame grid, in a header of their own. */
+#include "viorb_sim3_match.h"
+
 /* ---- Place recognition: BowVector, ORBVocabulary::score and KeyFrameDatabase (reference src/KeyFrameDatabase.cc:40-309) ------------
  * The question relocalisation (src/Tracking.cc:2134) and loop detection (src/LoopClosing.cc:148-165) begin with: which stored key frames
  * look like this one? Integer, float-compare and ordered-sum arithmetic only: every output equals the reference's bit for bit.

@@ -1,5 +1,6 @@
 /* include/viorb_sim3.h — the Sim3 RANSAC solver of the C ABI: reference src/Sim3Solver.cc:37-423 (the arithmetic of
- * LoopClosing::ComputeSim3, src/LoopClosing.cc:255-375, up to the call of SearchBySim3). Included by viorb.h; include viorb.h, not this
+ * LoopClosing::ComputeSim3, src/LoopClosing.cc:255-375, up to the call of SearchBySim3, which is viorb_search_by_sim3_device of
+ * viorb_sim3_match.h and reads R12 / t12 / s12 of viorb_sim3_outputs where they lie). Included by viorb.h; include viorb.h, not this
  * file. The ctypes mirror is viorb_amd/capi.py: SIGNATURES_SIM3.
  *
  * Conventions (those of viorb_two_view.h): a batch of independent key-frame pairs, arrays [batch][cap] with per-pair counts

@@ -1,6 +1,7 @@
 """ctypes declarations of include/viorb.h and of the headers it includes, viorb_global_ba_se3.h, viorb_two_view.h and viorb_sim3.h (kept 1:1; tests/test_host_hooks.py checks that every
 declared entry point of viorb.h is exported, has a signature here and that the argument counts agree; tests/test_global_ba_se3_ref.py
-does the same for SIGNATURES_GLOBAL_BA_SE3, tests/test_two_view_ref.py for SIGNATURES_TWO_VIEW, tests/test_sim3_ref.py for SIGNATURES_SIM3)."""
+does the same for SIGNATURES_GLOBAL_BA_SE3, tests/test_two_view_ref.py for SIGNATURES_TWO_VIEW, tests/test_sim3_ref.py for SIGNATURES_SIM3,
+tests/test_sim3_match_ref.py for SIGNATURES_SIM3_MATCH)."""
 import ctypes as C
 import os
 import numpy as np
@@ -109,6 +110,16 @@ SIM3_OUTPUT_FIELDS = ("status", "iterations_done", "best_inliers", "best_iter", 
 class Sim3Outputs(C.Structure):
     """viorb_sim3_outputs (include/viorb_sim3.h)."""
     _fields_ = [(n, C.c_void_p) for n in SIM3_OUTPUT_FIELDS]
+
+
+class S3mKeyframes(C.Structure):
+    """viorb_s3m_keyframes (include/viorb_sim3_match.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("kps", "desc", "count", "cell_start", "cell_idx")] + [("cap", C.c_int32)]
+
+
+class S3mSide(C.Structure):
+    """viorb_s3m_side (include/viorb_sim3_match.h)."""
+    _fields_ = [("kf", S3mKeyframes)] + [(n, C.c_void_p) for n in ("pose12", "has_point", "pts_f", "pts_desc", "already")]
 
 
 class TrackerConfig(C.Structure):
@@ -331,6 +342,25 @@ SIGNATURES_SIM3 = {
     "viorb_debug_sim3_select": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp]),
 }
 
+# mirrors include/viorb_sim3_match.h (the Sim3 matchers); tests/test_sim3_match_ref.py checks names and argument counts against it
+_cam = [PP(MappingCamera), vp, f32]                             # cam, bounds4, th
+SIGNATURES_SIM3_MATCH = {
+    "viorb_sim3_match_workspace_bytes": (sz, [i32, i32, i32]),
+    "viorb_sim3_match_shape": (i32, [vp]),
+    "viorb_keyframe_grid_device": (i32, [vp, vp, i32, i32, vp, vp, vp, vp]),
+    "viorb_keyframe_grid": (i32, [vp, i32, vp, vp, vp]),
+    "viorb_search_by_sim3_device": (i32, [PP(S3mSide), PP(S3mSide), vp, vp, vp] + _cam + [i32] + [vp] * 7 + [sz, vp]),
+    "viorb_search_by_sim3": (i32, [vp, vp, i32, vp, vp, vp, vp, vp] * 2 + [vp, vp, f32] + _cam + [vp] * 6),
+    "viorb_search_by_projection_sim3_device": (i32, [PP(S3mKeyframes), vp, vp, vp, vp, vp, i32, vp] + _cam + [i32, vp, vp, vp, vp, sz, vp]),
+    "viorb_search_by_projection_sim3": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, vp] + _cam + [vp, vp, vp]),
+    "viorb_fuse_sim3_device": (i32, [PP(S3mKeyframes), vp, vp, vp, vp, i32, i32] + _cam + [i32, vp, vp, vp, vp, sz, vp]),
+    "viorb_fuse_sim3": (i32, [vp, vp, i32, vp, vp, vp, vp, i32] + _cam + [vp, vp, vp]),
+    "viorb_debug_sim3_decompose": (i32, [vp, vp]),
+    "viorb_debug_sim3_pair": (i32, [vp, vp, f32, vp]),
+    "viorb_debug_sim3_project": (i32, [i32, vp, vp, vp, vp] + _cam + [vp, vp]),
+    "viorb_debug_claim_in_order": (i32, [vp, vp, i32, i32, vp, i32, vp, vp]),
+}
+
 _lib = None
 
 
@@ -351,7 +381,7 @@ def lib():
             pass
         L = C.CDLL(SO_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GLOBAL_BA_SE3.items()) + list(SIGNATURES_TWO_VIEW.items()) \
-                + list(SIGNATURES_SIM3.items()):
+                + list(SIGNATURES_SIM3.items()) + list(SIGNATURES_SIM3_MATCH.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -1692,6 +1692,24 @@ int viorb_frontend_grid_device(viorb_frontend* h, const viorb_keypoint* kps, con
     return VIORB_OK;
 }
 
+// KeyFrame::mGrid without a handle (include/viorb_sim3_match.h): k_frame_grid with the sort length viorb_frontend_create derives from cap
+int viorb_keyframe_grid_device(const viorb_keypoint* kps, const int32_t* count, int cap, int batch, const float bounds4[4], int32_t* cell_start,
+                               int32_t* cell_idx, void* stream) {
+    VIORB_REQUIRE(kps && count && bounds4 && cell_start && cell_idx, "null array");
+    VIORB_REQUIRE(cap >= 1, "cap >= 1");
+    VIORB_REQUIRE(batch >= 1 && batch <= 65535, "1 <= batch <= 65535");
+    VIORB_REQUIRE(bounds4[1] > bounds4[0] && bounds4[3] > bounds4[2], "empty image bounds");
+    if (cap > VIORB_S3M_MAX_FEATURES) { set_error("cap %d above VIORB_S3M_MAX_FEATURES", cap); return VIORB_ERR_CAPACITY; }
+    VIORB_TRY(require_device());
+    int sort_n = 64; while (sort_n < cap) sort_n <<= 1;
+    const size_t lds = (size_t)sort_n * 4;                            // cap <= VIORB_S3M_MAX_FEATURES: at most 64 KiB
+    if (lds > 48 * 1024) VIORB_HIP_TRY(raise_dynamic_lds(reinterpret_cast<const void*>(k_frame_grid), lds));
+    const float wInv = static_cast<float>(GRID_COLS) / static_cast<float>(bounds4[1] - bounds4[0]);
+    const float hInv = static_cast<float>(GRID_ROWS) / static_cast<float>(bounds4[3] - bounds4[2]);
+    VIORB_LAUNCH(k_frame_grid, batch, 256, lds, (hipStream_t)stream, kps, count, cap, bounds4[0], bounds4[2], wInv, hInv, cell_start, cell_idx, sort_n);
+    return VIORB_OK;
+}
+
 static UndistortArgs undistort_args(const float* intr4, const float* dist5) {
     UndistortArgs A;
     A.fx = intr4[0]; A.fy = intr4[1]; A.cx = intr4[2]; A.cy = intr4[3];

@@ -11,6 +11,9 @@
 //   search_by_bow                    ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches)              src/ORBmatcher.cc:159-288
 //   search_for_triangulation         ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo)   :657-823
 //   fuse                             ORBmatcher::Fuse(KeyFrame*, vpMapPoints, th)                               :825-975
+//   search_by_sim3                   ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th)       :1102-1326
+//   search_by_projection_sim3        ORBmatcher::SearchByProjection(KeyFrame*, Scw, vpPoints, vpMatched, th)    :290-403
+//   fuse_sim3                        ORBmatcher::Fuse(KeyFrame*, Scw, vpPoints, th, vpReplacePoint)             :977-1100
 //
 // Two accessors the reference does not have are needed on MapPoint (its mfMinDistance / mfMaxDistance are protected and the existing
 // getters return them scaled by 0.8 / 1.2): `float GetMinDistance()` and `float GetMaxDistance()`, returning the raw members under
@@ -19,6 +22,7 @@
 #define VIORB_ORBMATCHER_SHIM_H
 
 #include <vector>
+#include <set>
 #include <utility>
 #include <cstring>
 #include "viorb_tracking_shim.h"
@@ -197,6 +201,124 @@ inline int fuse(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, floa
                 if (pMPinKF->Observations() > pMP->Observations()) pMP->Replace(pMPinKF);
                 else pMPinKF->Replace(pMP);
             }
+        } else {
+            pMP->AddObservation(pKF, best[p]);
+            pKF->AddMapPoint(pMP, best[p]);
+        }
+    }
+    return nFused;
+}
+
+// ---- the loop-closing matchers that take a similarity (include/viorb_sim3_match.h) ------------------------------------------------------
+template <class KeyFrameT> inline viorb_mapping_camera sim3_match_camera(const KeyFrameT* pKF, float bounds4[4]) {
+    viorb_mapping_camera cam; std::memset(&cam, 0, sizeof(cam));
+    cam.fx = pKF->fx; cam.fy = pKF->fy; cam.cx = pKF->cx; cam.cy = pKF->cy; cam.nlevels = pKF->mnScaleLevels;
+    for (int i = 0; i < 16; i++) cam.scale_factors[i] = pKF->mvScaleFactors[i < pKF->mnScaleLevels ? i : pKF->mnScaleLevels - 1];
+    cam.scale_factor = cam.scale_factors[pKF->mnScaleLevels > 1 ? 1 : 0];
+    bounds4[0] = pKF->mnMinX; bounds4[1] = pKF->mnMaxX; bounds4[2] = pKF->mnMinY; bounds4[3] = pKF->mnMaxY;
+    return cam;
+}
+// Scw12 = the top three rows of a 4x4 CV_32F similarity
+inline void flatten_scw(const cv::Mat& Scw, float* S12) { for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) S12[4 * r + c] = Scw.at<float>(r, c); }
+
+// One side of SearchBySim3: the key frame's features and the map point of each (vpMapPoints = GetMapPointMatches()).
+template <class KeyFrameT, class MapPointT> struct Sim3MatchSide {
+    std::vector<viorb_keypoint> keys; std::vector<unsigned char> has, desc, already; std::vector<float> pts_f; float pose[12];
+    Sim3MatchSide(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints) {
+        const int n = pKF->N;
+        flatten_keys(pKF->mvKeysUn, n, keys);
+        has.assign(n + 1, 0); already.assign(n + 1, 0); desc.assign((size_t)(n + 1) * 32, 0); pts_f.assign((size_t)(n + 1) * 8, 0.f);
+        for (int i = 0; i < n; i++) {
+            MapPointT* pMP = vpMapPoints[i];
+            if (!pMP || pMP->isBad()) continue;                              // (:1152-1156, :1232-1236)
+            has[i] = 1;
+            flatten_point(pMP, &pts_f[(size_t)i * 8], &desc[(size_t)i * 32]);
+        }
+        const cv::Mat R = pKF->GetRotation(), t = pKF->GetTranslation();
+        for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) pose[3 * r + c] = R.at<float>(r, c); pose[9 + r] = t.at<float>(r); }
+    }
+};
+
+// ORBmatcher::SearchBySim3(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint*> &vpMatches12, const float &s12, const cv::Mat &R12,
+// const cv::Mat &t12, const float th): vbAlreadyMatched1 / 2 (:1129-1142) are derived here, both searches and the agreement check run on the
+// device, vpMatches12 is written as :1319 writes it. Returns nFound.
+template <class KeyFrameT, class MapPointT>
+inline int search_by_sim3(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches12, const float& s12, const cv::Mat& R12, const cv::Mat& t12,
+                          float th) {
+    const std::vector<MapPointT*> vpMapPoints1 = pKF1->GetMapPointMatches(), vpMapPoints2 = pKF2->GetMapPointMatches();
+    const int N1 = (int)vpMapPoints1.size(), N2 = (int)vpMapPoints2.size();
+    Sim3MatchSide<KeyFrameT, MapPointT> S1(pKF1, vpMapPoints1), S2(pKF2, vpMapPoints2);
+    for (int i = 0; i < N1; i++) {
+        MapPointT* pMP = vpMatches12[i];
+        if (!pMP) continue;
+        S1.already[i] = 1;
+        const int idx2 = pMP->GetIndexInKeyFrame(pKF2);
+        if (idx2 >= 0 && idx2 < N2) S2.already[idx2] = 1;
+    }
+    float R[9], t[3], bounds[4];
+    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) R[3 * r + c] = R12.at<float>(r, c); t[r] = t12.at<float>(r); }
+    const viorb_mapping_camera cam = sim3_match_camera(pKF1, bounds);
+    std::vector<int32_t> match12(N1 + 1, -1); int nFound = 0;
+    check(viorb_search_by_sim3(&S1.keys[0], pKF1->mDescriptors.data, N1, S1.pose, &S1.has[0], &S1.pts_f[0], &S1.desc[0], &S1.already[0], &S2.keys[0],
+                               pKF2->mDescriptors.data, N2, S2.pose, &S2.has[0], &S2.pts_f[0], &S2.desc[0], &S2.already[0], R, t, s12, &cam, bounds, th,
+                               &match12[0], &nFound, 0, 0, 0, 0), "SearchBySim3");
+    for (int i1 = 0; i1 < N1; i1++) if (match12[i1] >= 0) vpMatches12[i1] = vpMapPoints2[match12[i1]];
+    return nFound;
+}
+
+// ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*> &vpPoints, vector<MapPoint*> &vpMatched, int th):
+// spAlreadyFound (:306-307) and the entry state of vpMatched are flattened, the ordered search runs on the device, vpMatched[bestIdx] = pMP
+// (:396) is written in point order. Returns nmatches.
+template <class KeyFrameT, class MapPointT>
+inline int search_by_projection_sim3(KeyFrameT* pKF, const cv::Mat& Scw, const std::vector<MapPointT*>& vpPoints, std::vector<MapPointT*>& vpMatched, int th) {
+    const int np = (int)vpPoints.size(), n = pKF->N;
+    std::vector<viorb_keypoint> kk; flatten_keys(pKF->mvKeysUn, n, kk);
+    std::set<MapPointT*> spAlreadyFound(vpMatched.begin(), vpMatched.end());
+    spAlreadyFound.erase(static_cast<MapPointT*>(0));
+    std::vector<float> pts_f((size_t)(np + 1) * 8, 0.f);
+    std::vector<unsigned char> valid(np + 1, 0), pdesc((size_t)(np + 1) * 32, 0), taken(n + 1, 0);
+    for (int p = 0; p < np; p++) {
+        MapPointT* pMP = vpPoints[p];
+        if (pMP->isBad() || spAlreadyFound.count(pMP)) continue;              // (:317)
+        valid[p] = 1;
+        flatten_point(pMP, &pts_f[(size_t)p * 8], &pdesc[(size_t)p * 32]);
+    }
+    for (int i = 0; i < n && i < (int)vpMatched.size(); i++) taken[i] = vpMatched[i] ? 1 : 0;
+    float S[12], bounds[4]; flatten_scw(Scw, S);
+    const viorb_mapping_camera cam = sim3_match_camera(pKF, bounds);
+    std::vector<int32_t> best(np + 1, -1); int nmatches = 0;
+    check(viorb_search_by_projection_sim3(&kk[0], pKF->mDescriptors.data, n, S, &pts_f[0], &pdesc[0], &valid[0], np, &taken[0], &cam, bounds, (float)th,
+                                          &best[0], &nmatches, 0), "SearchByProjection(KeyFrame, Scw)");
+    for (int p = 0; p < np; p++) if (best[p] >= 0) vpMatched[best[p]] = vpPoints[p];
+    return nmatches;
+}
+
+// ORBmatcher::Fuse(KeyFrame *pKF, cv::Mat Scw, const vector<MapPoint *> &vpPoints, float th, vector<MapPoint *> &vpReplacePoint): the search
+// runs on the device; the reference's own block (:1081-1096) runs here over best_idx in point order, so that a point added to the key frame
+// (:1092-1093) is what a later point with the same feature finds there. Returns nFused.
+template <class KeyFrameT, class MapPointT>
+inline int fuse_sim3(KeyFrameT* pKF, const cv::Mat& Scw, const std::vector<MapPointT*>& vpPoints, float th, std::vector<MapPointT*>& vpReplacePoint) {
+    const int np = (int)vpPoints.size(), n = pKF->N;
+    std::vector<viorb_keypoint> kk; flatten_keys(pKF->mvKeysUn, n, kk);
+    const std::set<MapPointT*> spAlreadyFound = pKF->GetMapPoints();
+    std::vector<float> pts_f((size_t)(np + 1) * 8, 0.f);
+    std::vector<unsigned char> valid(np + 1, 0), pdesc((size_t)(np + 1) * 32, 0);
+    for (int p = 0; p < np; p++) {
+        MapPointT* pMP = vpPoints[p];
+        if (pMP->isBad() || spAlreadyFound.count(pMP)) continue;              // (:1005)
+        valid[p] = 1;
+        flatten_point(pMP, &pts_f[(size_t)p * 8], &pdesc[(size_t)p * 32]);
+    }
+    float S[12], bounds[4]; flatten_scw(Scw, S);
+    const viorb_mapping_camera cam = sim3_match_camera(pKF, bounds);
+    std::vector<int32_t> best(np + 1, -1); int nFused = 0;
+    check(viorb_fuse_sim3(&kk[0], pKF->mDescriptors.data, n, S, &pts_f[0], &pdesc[0], &valid[0], np, &cam, bounds, th, &best[0], &nFused, 0), "Fuse(KeyFrame, Scw)");
+    for (int p = 0; p < np; p++) {
+        if (best[p] < 0) continue;
+        MapPointT* pMP = vpPoints[p];
+        MapPointT* pMPinKF = pKF->GetMapPoint(best[p]);
+        if (pMPinKF) {
+            if (!pMPinKF->isBad()) vpReplacePoint[p] = pMPinKF;
         } else {
             pMP->AddObservation(pKF, best[p]);
             pKF->AddMapPoint(pMP, best[p]);

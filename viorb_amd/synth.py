@@ -1134,3 +1134,153 @@ def make_sim3_problem(seed, kind="general", n=300, outlier_frac=0.0, noise_px=0.
                 octave1=o1.astype(np.int32), octave2=o2.astype(np.int32), sigma2_1=sig(o1).astype(np.float32), sigma2_2=sig(o2).astype(np.float32),
                 K1=np.array([fx, fy, cx, cy], np.float32), K2=np.array([fx, fy, cx, cy], np.float32), R12=R12, t12=t12, s12=float(s12),
                 true_inlier=true_inlier, kind=kind)
+
+
+def _flip_bits(rng, d, k):
+    """A copy of descriptors d [n,32] with k random bit flips per row (a bit may be hit twice)."""
+    d = np.array(d, np.uint8, copy=True).reshape(-1, 32)
+    for _ in range(k):
+        b = rng.integers(0, 256, len(d))
+        d[np.arange(len(d)), b >> 3] ^= (1 << (b & 7)).astype(np.uint8)
+    return d
+
+
+def make_sim3_match_problem(seed, n1=1000, n2=1000, n_common=500, fix_scale=False, duplicates=0, siblings=60, cluster=0, n_kf=1, n_extra=300,
+                            n_special=12, nlevels=8, w=752, h=480):
+    """Two key frames that see a common scene from two maps that differ by a similarity, for the loop-closing matchers (SearchBySim3,
+    SearchByProjection(KF, Scw), Fuse(KF, Scw)). Key frame 1 lives in map 1 (metric), key frame 2 in map 2, whose unit is s12 metres (1.3;
+    1 with fix_scale) and whose axes are rotated and shifted: X_c1 = s12 R12 X_c2 + t12. Feature i < n_common of both key frames is the
+    same scene point. numpy only.
+
+    kf1, kf2: dict(kps, desc, pose12, has_point, pts_f [n,8] from local_points_f32, pts_desc [n,32] = the key point's descriptor with a
+    few flipped bits, already [n]). Some common pairs are `already` matched; `siblings` common features of each key frame get a second
+    feature a few pixels away with a similar descriptor and a copy of the map point (several candidates under TH_LOW, and one-way matches
+    that are not mutual); n_special own-only features per reason get a map point that is behind the other camera, outside its image,
+    outside its distance range, or seen from behind (the viewing-angle gate).
+    loop: the points of map 2 that Scw [12] projects into key frame 1: pts_f [P,8], pts_desc [P,32], valid [P], feat_taken [n1] (the
+    features of key frame 1 that are matched on entry; their points are not valid), source [P] = the feature of key frame 2 or -1.
+    duplicates=k appends k noisy copies of loop points whose feature is free, so that several points contend for one feature;
+    cluster=c puts c features with near-identical descriptors at one place of key frame 1 and c + 4 copies of one point on them.
+    fuse: n_kf key frames near key frame 1 (the first is key frame 1) over the loop points: frames [(kps, desc)], Scw [n_kf,12], valid
+    [n_kf,P]."""
+    rng = np.random.Generator(np.random.PCG64(seed + 717171))
+    fx, fy, cx, cy = [float(np.float32(v)) for v in (EUROC_K["fx"], EUROC_K["fy"], EUROC_K["cx"], EUROC_K["cy"])]
+    sf = (np.float32(1.2) ** np.arange(nlevels)).astype(np.float32)
+    lsf = np.log(1.2)
+    s12 = 1.0 if fix_scale else 1.3
+    R1 = _rotvec_to_R(rng.normal(0, 0.03, 3)); t1 = rng.normal(0, 0.05, 3)
+    R2 = _rotvec_to_R(np.array([0.02, 0.16, -0.03]) + rng.normal(0, 0.01, 3)) @ R1; t2 = R2 @ (-np.array([0.9, 0.1, 0.3])) + rng.normal(0, 0.02, 3)
+    Rd = _rotvec_to_R(rng.normal(0, 0.4, 3)); td = rng.normal(0, 1.0, 3)
+    to_w2 = lambda Xw: (Xw @ Rd.T + td) / s12                          # map 2 from the metric world (= map 1)
+    R2w = R2 @ Rd.T; t2w = (t2 - R2w @ td) / s12                       # key frame 2 in map 2
+    R12 = R1 @ R2.T; t12 = t1 - R12 @ t2
+    proj = lambda Xc: np.stack([fx * Xc[:, 0] / Xc[:, 2] + cx, fy * Xc[:, 1] / Xc[:, 2] + cy], 1)
+    inside = lambda uv, z: (z > 0.5) & (uv[:, 0] > 20) & (uv[:, 0] < w - 20) & (uv[:, 1] > 20) & (uv[:, 1] < h - 20)
+    cloud = lambda m: np.stack([rng.uniform(-5, 5, m), rng.uniform(-3.5, 3.5, m), rng.uniform(3, 12, m)], 1)
+    X = cloud(6 * n_common)
+    c1, c2 = X @ R1.T + t1, X @ R2.T + t2
+    X = X[inside(proj(c1), c1[:, 2]) & inside(proj(c2), c2[:, 2])][:n_common]
+    nc = len(X)
+    assert nc == n_common, "not enough points visible in both cameras"
+    base = rng.integers(0, 256, (nc, 32), dtype=np.uint8)
+    coin = lambda: rng.integers(0, 2, nc)
+
+    def view(R, t, n, n_sib, octave_of):
+        """A key frame at (R, t) (metric): the common features, then n_sib siblings, then own-only features. octave_of(dist): the octaves
+        of the common features from their distances, or None for random ones."""
+        Xc = X @ R.T + t
+        uv, dist = proj(Xc), np.linalg.norm(Xc, axis=1)
+        k = np.zeros(n, KP_NP)
+        k["x"][:nc] = uv[:, 0] + rng.normal(0, 0.5, nc); k["y"][:nc] = uv[:, 1] + rng.normal(0, 0.5, nc)
+        k["x"][nc:] = rng.uniform(20, w - 20, n - nc); k["y"][nc:] = rng.uniform(20, h - 20, n - nc)
+        k["octave"] = rng.integers(0, nlevels, n)
+        if octave_of is not None:
+            k["octave"][:nc] = np.clip(octave_of(dist), 0, nlevels - 1)
+        d = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+        d[:nc] = _flip_bits(rng, base, 8)
+        sib = rng.permutation(nc)[:n_sib]
+        js = nc + np.arange(len(sib))
+        k["x"][js] = k["x"][sib] + rng.uniform(1.5, 3.5, len(sib)) * rng.choice([-1, 1], len(sib)); k["y"][js] = k["y"][sib] + rng.uniform(-2, 2, len(sib))
+        k["octave"][js] = k["octave"][sib]
+        d[js] = _flip_bits(rng, base[sib], 20)
+        k["angle"] = rng.uniform(0, 360, n); k["size"] = 31 * sf[k["octave"]]; k["class_id"] = -1
+        return k, d, dist, sib, js
+    # a point of octave o1 at distance d1 is predicted in key frame 2 at level ceil(o1 + log(d1 s12 / d2) / log 1.2), d2 metric; and back
+    k1, d1, dist1, sib1, js1 = view(R1, t1, n1, siblings, None)
+    k2, d2, dist2, sib2, js2 = view(R2, t2, n2, siblings, lambda dd: np.ceil(k1["octave"][:nc] + np.log(dist1 * s12 / dd) / lsf) - coin())
+    pose1 = np.concatenate([R1.ravel(), t1]); pose2 = np.concatenate([R2w.ravel(), t2w])
+
+    def points(k, d, n, pose, Xw_common, sib, js, unit, own_world_from_other_cam, unit_other):
+        """The map points of one key frame's features in its own map (unit metres per map unit): the common points, copies for the siblings,
+        own-only points on the key point's ray, and the special ones, which are chosen in the OTHER camera's frame (metric)."""
+        Rw, tw = pose[:9].reshape(3, 3), pose[9:]
+        own = np.arange(nc + len(sib), n)
+        Pw = np.zeros((n, 3))
+        Pw[:nc] = Xw_common
+        Pw[js] = Xw_common[sib] + rng.normal(0, 0.004, (len(sib), 3))
+        ray = np.stack([(k["x"][own] - cx) / fx, (k["y"][own] - cy) / fy, np.ones(len(own))], 1) * (rng.uniform(3, 12, len(own)) / unit)[:, None]
+        Pw[own] = (ray - tw) @ Rw
+        pts_f = local_points_f32(k["octave"], pose, Pw, sf)
+        has = np.zeros(n, np.uint8); has[:nc] = 1; has[js] = 1; has[own] = rng.random(len(own)) < 0.6
+        sp = own[has[own] == 1][:4 * n_special]
+        kinds = np.repeat(np.arange(4), n_special)[:len(sp)]
+        zc = rng.uniform(3, 10, len(sp))
+        Xo = np.stack([rng.uniform(-0.3, 0.3, len(sp)) * zc, rng.uniform(-0.2, 0.2, len(sp)) * zc, zc], 1)
+        Xo[kinds == 0, 2] *= -1                                        # behind the other camera
+        Xo[kinds == 1, 0] = zc[kinds == 1] * (w + 60 - cx) / fx        # right of its image
+        f = local_points_f32(k["octave"][sp], pose, own_world_from_other_cam(Xo), sf)
+        d_other = (np.linalg.norm(Xo, axis=1) / unit_other).astype(np.float32)
+        f[:, 6] = d_other * np.float32(0.4); f[:, 7] = d_other * np.float32(1.5)
+        f[kinds == 2, 6] = d_other[kinds == 2] * np.float32(2.0); f[kinds == 2, 7] = d_other[kinds == 2] * np.float32(6.0)     # too close
+        f[kinds == 3, 3:6] *= -1                                       # the normal points away from both cameras
+        pts_f[sp] = f
+        return pts_f.astype(np.float32), _flip_bits(rng, d, 3), has, sp, kinds
+    pf1, pd1, has1, sp1, kinds1 = points(k1, d1, n1, pose1, X, sib1, js1, 1.0, lambda Xc2: (Xc2 - t2) @ R2, s12)
+    pf2, pd2, has2, sp2, kinds2 = points(k2, d2, n2, pose2, to_w2(X), sib2, js2, s12, lambda Xc1: to_w2((Xc1 - t1) @ R1), 1.0)
+    truth = np.full(n1, -1, np.int64); truth[:nc] = np.arange(nc)
+    al1 = np.zeros(n1, np.uint8); al2 = np.zeros(n2, np.uint8)
+    am = rng.permutation(nc)[:max(30, nc // 15)]
+    am = am[~np.isin(am, sib1) & ~np.isin(am, sib2)]
+    al1[am] = 1; al2[am] = 1
+
+    # ---- the loop points: map 2's points, which Scw = S12 * T2w projects into key frame 1
+    Scw = np.concatenate([s12 * R12 @ R2w, (s12 * R12 @ t2w + t12)[:, None]], 1).astype(np.float32).ravel()
+    src = np.nonzero(has2)[0]
+    lp_f = [pf2[src], local_points_f32(rng.integers(0, nlevels, n_extra), pose2, to_w2(cloud(n_extra)), sf)]
+    lp_d = [pd2[src], rng.integers(0, 256, (n_extra, 32), dtype=np.uint8)]
+    source = [src, np.full(n_extra, -1, np.int64)]
+    free = src[(src < nc) & (al2[src] == 0)]                           # common points whose feature of key frame 1 is free on entry
+    if duplicates:
+        pick = rng.choice(free, duplicates, replace=duplicates > len(free))
+        f = pf2[pick].copy(); f[:, :3] += rng.normal(0, 0.002, (duplicates, 3)).astype(np.float32)
+        lp_f.append(f); lp_d.append(_flip_bits(rng, pd2[pick], 3)); source.append(pick)
+    if cluster:
+        inner = free[(k1["octave"][free] >= min(1, nlevels - 1)) & (k1["octave"][free] <= max(nlevels - 2, 0))]
+        j = int(inner[0])                                              # feature j of both key frames
+        cl = np.arange(n1 - cluster, n1)                               # the last own-only features of key frame 1 move onto it
+        k1["x"][cl] = k1["x"][j] + rng.uniform(-2.5, 2.5, cluster); k1["y"][cl] = k1["y"][j] + rng.uniform(-2.5, 2.5, cluster)
+        k1["octave"][cl] = k1["octave"][j]; k1["size"][cl] = k1["size"][j]
+        d1[cl] = _flip_bits(rng, np.repeat(d1[j:j + 1], cluster, 0), 4)
+        has1[cl] = 0
+        lp_f.append(np.repeat(pf2[j:j + 1], cluster + 4, 0)); lp_d.append(_flip_bits(rng, np.repeat(pd2[j:j + 1], cluster + 4, 0), 2))
+        source.append(np.full(cluster + 4, j, np.int64))
+    lp_f, lp_d, source = np.concatenate(lp_f).astype(np.float32), np.concatenate(lp_d), np.concatenate(source)
+    valid = np.ones(len(lp_f), np.uint8)
+    valid[(source >= 0) & (al2[np.maximum(source, 0)] == 1)] = 0       # in spAlreadyFound
+    valid[rng.random(len(valid)) < 0.02] = 0                           # bad
+
+    # ---- Fuse: key frames near key frame 1, each with its own corrected Scw, over the one list
+    frames, Scws, valids = [(k1, d1)], [Scw], [valid.copy()]
+    for b in range(1, n_kf):
+        Rb = _rotvec_to_R(rng.normal(0, 0.02, 3)) @ R1; tb = t1 + rng.normal(0, 0.08, 3)
+        kb, db, _, _, _ = view(Rb, tb, n1, 0, lambda dd: np.ceil(k2["octave"][:nc] - np.log(dd * s12 / dist2) / lsf) - coin())
+        Rb2 = Rb @ R2.T; tb2 = tb - Rb2 @ t2
+        frames.append((kb, db)); Scws.append(np.concatenate([s12 * Rb2 @ R2w, (s12 * Rb2 @ t2w + tb2)[:, None]], 1).astype(np.float32).ravel())
+        v = valid.copy(); v[rng.random(len(v)) < 0.15] = 0             # already in key frame b
+        valids.append(v)
+    side = lambda k, d, pose, has, pf, pd, al: dict(kps=k, desc=d, pose12=pose.astype(np.float32), has_point=has, pts_f=pf, pts_desc=pd, already=al)
+    return dict(kf1=side(k1, d1, pose1, has1, pf1, pd1, al1), kf2=side(k2, d2, pose2, has2, pf2, pd2, al2), truth12=truth,
+                R12=R12.astype(np.float32), t12=t12.astype(np.float32), s12=np.float32(s12), intr4=np.array([fx, fy, cx, cy], np.float32), sf=sf,
+                bounds4=np.array([0, w, 0, h], np.float32),
+                loop=dict(pts_f=lp_f, pts_desc=lp_d, valid=valid, Scw=Scw, feat_taken=al1.copy(), source=source),
+                fuse=dict(frames=frames, Scw=np.stack(Scws), valid=np.stack(valids)))
