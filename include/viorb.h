@@ -930,6 +930,10 @@ int viorb_debug_gba_last_trials(uint8_t* accepted, int cap, int* n);
  * key-frame grid, in a header of their own. */
 #include "viorb_sim3_match.h"
 
+/* The essential-graph optimisation of loop closing (Optimizer::OptimizeEssentialGraph): a Sim3 pose graph on the global adjustments'
+ * factorisation, in a header of its own. */
+#include "viorb_essential_graph.h"
+
 /* ---- Place recognition: BowVector, ORBVocabulary::score and KeyFrameDatabase (reference src/KeyFrameDatabase.cc:40-309) ------------
  * The question relocalisation (src/Tracking.cc:2134) and loop detection (src/LoopClosing.cc:148-165) begin with: which stored key frames
  * look like this one? Integer, float-compare and ordered-sum arithmetic only: every output equals the reference's bit for bit.

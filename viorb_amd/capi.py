@@ -74,6 +74,11 @@ class GbaConfig(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("robust", C.c_int32)]
 
 
+class EgConfig(C.Structure):
+    """viorb_eg_config (include/viorb_essential_graph.h)."""
+    _fields_ = [("iterations", C.c_int32), ("fix_scale", C.c_int32)]
+
+
 class TwoViewConfig(C.Structure):
     """viorb_two_view_config (include/viorb_two_view.h)."""
     _fields_ = [("sigma", C.c_float), ("iterations", C.c_int32), ("min_parallax_deg", C.c_float), ("min_triangulated", C.c_int32),
@@ -361,6 +366,16 @@ SIGNATURES_SIM3_MATCH = {
     "viorb_debug_claim_in_order": (i32, [vp, vp, i32, i32, vp, i32, vp, vp]),
 }
 
+# mirrors include/viorb_essential_graph.h (the essential-graph optimisation); tests/test_essential_graph_ref.py checks names and argument
+# counts against it
+SIGNATURES_ESSENTIAL_GRAPH = {
+    "viorb_essential_graph_workspace_bytes": (sz, [i32, i32, i32]),
+    "viorb_optimize_essential_graph": (i32, [PP(EgConfig), vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp]),
+    "viorb_optimize_essential_graph_device": (i32, [PP(EgConfig), vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "viorb_debug_sim3_log": (i32, [vp, vp]),
+    "viorb_debug_essential_graph_edge": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+}
+
 _lib = None
 
 
@@ -381,7 +396,7 @@ def lib():
             pass
         L = C.CDLL(SO_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GLOBAL_BA_SE3.items()) + list(SIGNATURES_TWO_VIEW.items()) \
-                + list(SIGNATURES_SIM3.items()) + list(SIGNATURES_SIM3_MATCH.items()):
+                + list(SIGNATURES_SIM3.items()) + list(SIGNATURES_SIM3_MATCH.items()) + list(SIGNATURES_ESSENTIAL_GRAPH.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

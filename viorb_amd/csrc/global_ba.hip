@@ -493,7 +493,7 @@ int gba_step(const GbaDev& D, double lambda, hipStream_t st) {
     VIORB_LAUNCH(k_gba_update, gba_blocks(std::max(D.nk, D.np), 256), 256, 0, st, D, lambda);
     return VIORB_OK;
 }
-const GbaOps g_gba_navstate_ops = {GBA_MAX_FREE_KF, gba_setup, gba_errors, gba_linearise, gba_reduce, gba_step};
+const GbaOps g_gba_navstate_ops = {GBA_MAX_FREE_KF, gba_setup, gba_errors, gba_linearise, gba_reduce, gba_step, 0.0};
 void gba_navstate_shape(GbaDev& D, int nk, int np, int ne) { D.nk = nk; D.np = np; D.ne = ne; D.blk = 12; D.kf_w = 22; D.obs_w = 3; D.rows = 2; }
 } // namespace
 
@@ -511,8 +511,10 @@ int gba_run(const viorb_gba_config* cfg, GbaDev& D, const GbaOps& ops, void* wor
     const int* hst = reinterpret_cast<const int*>(pinned);
     if (hst[GBA_ST_INVALID]) {
         const int bad = hst[GBA_ST_INVALID];
-        set_error("invalid argument: global BA graph (%s%s%s%s%s)", (bad & GBA_BAD_PREV) ? " prev[i] >= i" : "", (bad & GBA_BAD_EDGE) ? " edge index out of range or edges not sorted by point" : "",
-                  (bad & GBA_BAD_COV) ? " singular pre-integration covariance" : "", (bad & GBA_BAD_SIGMA) ? " invSigma2 <= 0" : "", (bad & GBA_BAD_BF) ? " stereo edge with bf <= 0" : "");
+        set_error("invalid argument: global BA graph (%s%s%s%s%s%s%s%s%s)", (bad & GBA_BAD_PREV) ? " prev[i] >= i" : "", (bad & GBA_BAD_EDGE) ? " edge index out of range or edges not sorted by point" : "",
+                  (bad & GBA_BAD_COV) ? " singular pre-integration covariance" : "", (bad & GBA_BAD_SIGMA) ? " invSigma2 <= 0" : "", (bad & GBA_BAD_BF) ? " stereo edge with bf <= 0" : "",
+                  (bad & GBA_BAD_EG_EDGE) ? " Sim3 edge index out of range or i == j" : "", (bad & GBA_BAD_EG_POSE) ? " Sim3 pose not finite or scale <= 0" : "",
+                  (bad & GBA_BAD_EG_GAUGE) ? " no fixed vertex" : "", (bad & GBA_BAD_EG_REF) ? " point_ref out of range" : "");
         return VIORB_ERR_INVALID_ARG;
     }
     D.nfree = hst[GBA_ST_NFREE]; D.n = D.blk * D.nfree; D.ld = gba_ld(D.n);
@@ -536,7 +538,7 @@ int gba_run(const viorb_gba_config* cfg, GbaDev& D, const GbaOps& ops, void* wor
     VIORB_TRY(ops.linearise(D, st));
     VIORB_LAUNCH(k_gba_max_diag, gba_blocks((size_t)D.n + 3 * (size_t)D.np, 256 * 8), 256, 0, st, D);
     if (int rc = read_scal()) return rc;
-    gba_lm L; L.cur = pinned[GBA_S_CHI]; L.lambda = 1e-5 * pinned[GBA_S_MAXDIAG]; L.ni = 2;
+    gba_lm L; L.cur = pinned[GBA_S_CHI]; L.lambda = ops.lambda_init > 0 ? ops.lambda_init : 1e-5 * pinned[GBA_S_MAXDIAG]; L.ni = 2;
     const double chi_before = L.cur;
     int its = 0, trials = 0, nfail = 0, nbad = 0;
     gba_trials().clear();

@@ -4,6 +4,8 @@
 // IMU factors), global_ba_se3.hip the vision-only one (6 coordinates, monocular and stereo edges). The kernels named here live in
 // global_ba.hip; the other translation unit reaches them through these host functions only. The Schur complement, the back-substitution
 // and the point blocks differ between the two only in the block order and the residual rows: one template body each, below.
+// essential_graph.hip is a third client of the loop and the Cholesky chain: a Sim3 pose graph (7 coordinates, kf_w = 8) with np = ne = 0
+// here, whose edges live in arrays of its own behind GbaDev::ext.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <vector>
@@ -15,7 +17,8 @@ namespace viorb {
 enum { GBA_S_CHI = 0, GBA_S_SCALE, GBA_S_FAIL, GBA_S_MAXDIAG, GBA_S_N = 8 };
 enum { GBA_ST_INVALID = 0, GBA_ST_NFREE, GBA_ST_N = 4 };
 // bits of status[GBA_ST_INVALID]
-enum { GBA_BAD_PREV = 1, GBA_BAD_EDGE = 2, GBA_BAD_COV = 4, GBA_BAD_SIGMA = 8, GBA_BAD_BF = 16 };
+enum { GBA_BAD_PREV = 1, GBA_BAD_EDGE = 2, GBA_BAD_COV = 4, GBA_BAD_SIGMA = 8, GBA_BAD_BF = 16,
+       GBA_BAD_EG_EDGE = 32, GBA_BAD_EG_POSE = 64, GBA_BAD_EG_GAUGE = 128, GBA_BAD_EG_REF = 256 };     // the essential-graph solve's (essential_graph.hip)
 
 struct GbaDev {
     int nk, np, ne, nfree, n, ld, robust;
@@ -37,6 +40,7 @@ struct GbaDev {
     int* status;                        // GBA_ST_*
     uint8_t* included;                  // [np]
     double cam[16], gw[3];              // NavState solve: cam[16], gw; SE3 solve: cam[0..4] = fx fy cx cy bf
+    const void* ext;                    // host pointer to a solve's own arrays (essential graph: its EgDev); no kernel reads it
 };
 
 // ---- kernel bodies both solves instantiate with their block order BLK (12 / 6) and residual rows ROWS (2 / 3); the __global__
@@ -123,6 +127,7 @@ inline unsigned gba_blocks(size_t n, unsigned per) { return (unsigned)std::max<s
 // The launches a solve supplies to gba_run. setup: free ranks (fidx, status[GBA_ST_NFREE]) and the solve's own argument checks;
 // errors: err[] and the robust chi2 into scal[GBA_S_CHI]; linearise: Jacobians, Hll / bl, Hd / bp; reduce: Dinv, S = Hpp + lambda I,
 // the right-hand side and the Schur complement; step: point increments, the retraction of every vertex and scal[GBA_S_SCALE].
+// lambda_init: setUserLambdaInit; zero = g2o's own rule, 1e-5 * the largest diagonal entry.
 struct GbaOps {
     int max_free;
     int (*setup)(const GbaDev&, hipStream_t);
@@ -130,6 +135,7 @@ struct GbaOps {
     int (*linearise)(const GbaDev&, hipStream_t);
     int (*reduce)(const GbaDev&, double lambda, hipStream_t);
     int (*step)(const GbaDev&, double lambda, hipStream_t);
+    double lambda_init;
 };
 
 // Lays the work arrays out in a workspace by D.nk / np / ne / blk / kf_w / rows; S (the only array whose size depends on the number of

@@ -158,7 +158,7 @@ int gse3_step(const GbaDev& D, double lambda, hipStream_t st) {
     VIORB_LAUNCH(k_gse3_update, gba_blocks(std::max(D.nk, D.np), 256), 256, 0, st, D, lambda);
     return VIORB_OK;
 }
-const GbaOps g_gse3_ops = {GBA_SE3_MAX_FREE_KF, gse3_setup, gse3_errors, gse3_linearise, gse3_reduce, gse3_step};
+const GbaOps g_gse3_ops = {GBA_SE3_MAX_FREE_KF, gse3_setup, gse3_errors, gse3_linearise, gse3_reduce, gse3_step, 0.0};
 
 void gse3_shape(GbaDev& D, int nk, int np, int ne) {
     D.nk = nk; D.np = np; D.ne = ne; D.blk = 6; D.kf_w = 7; D.obs_w = 4; D.rows = 3;

@@ -12,6 +12,10 @@
 //   bundle_adjustment                 Optimizer::BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust)
 //   global_bundle_adjustment          Optimizer::GlobalBundleAdjustemnt(pMap, nIterations, pbStopFlag, nLoopKF, bRobust)
 //                                                                                                 src/Optimizer.cc:3551-3747  -> viorb_global_ba_se3
+//   optimize_sim3                     Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale)
+//                                                                                                 src/Optimizer.cc:4589-4784  -> viorb_optimize_sim3
+//   optimize_essential_graph          Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections,
+//                                     bFixScale, pLC)                                             src/Optimizer.cc:4313-4587  -> viorb_optimize_essential_graph
 //
 // The window solves take `stop_mirror`: the reference's pbStopFlag is a bool*, the C ABI polls a `const volatile int*` — an int that
 // LocalMapping::InterruptBA sets next to mbAbortBA (one line there). A failure of the GPU library throws (viorb_shim::check).
@@ -21,9 +25,11 @@
 #include <vector>
 #include <list>
 #include <map>
+#include <set>
 #include <mutex>
 #include <algorithm>
 #include <stdexcept>
+#include <type_traits>
 #include "viorb_tracking_shim.h"
 
 namespace viorb_shim {
@@ -407,6 +413,114 @@ inline int optimize_sim3(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT
     for (int i = 0; i < N; i++) if (valid[i] && !keep[i]) vpMatches1[i] = static_cast<MapPointT*>(0);
     if (info[0] - info[1] >= 10) sim3_set(g2oS12, So);            // :4754 returns before g2oS12 is written
     return nIn;
+}
+
+// Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:4313-4587) over viorb_optimize_essential_graph. The flat snapshot is built here
+// with the reference's edge selection: a vertex per good key frame (the CorrectedSim3 entry, else (Rcw, tcw, 1); pLoopKF fixed), the
+// LoopConnections edges first (minFeat = 100 unless the pair is (pCurKF, pLoopKF); they fill sInsertedEdges, :4385-4413), then per key
+// frame its spanning-tree edge, its loop edges to older key frames and its covisibility edges of weight >= minFeat to older key frames
+// that are neither parent, child nor loop edge nor in sInsertedEdges (:4416-4516); the measurement of those comes from NonCorrectedSim3
+// where there is an entry (Smeas). An endpoint without a vertex (a bad key frame, which the reference would hand to setVertex as NULL)
+// throws. Written back under pMap->mMutexMapUpdate: SetPose, UpdateNavStatePVRFromTcw(Tiw, Tbc), SetWorldPos, UpdateNormalAndDepth
+// (mnCorrectedReference where mnCorrectedByKF == pCurKF->mnId, else the reference key frame, :4558-4567) and
+// pLC->SetMapUpdateFlagInTracking(true). sim3_get(const Sim3&, double[8]) gives r(x y z w) t s of a g2o::Sim3; pose_to_sim3(Rcw, tcw,
+// double[8]) is g2o::Sim3(Converter::toMatrix3d(Rcw), Converter::toVector3d(tcw), 1.0); to_pose(const double[12]) is Converter::toCvSE3
+// of R (row-major) and t. Returns info[6] of the C ABI through `info` when it is not NULL.
+template <class MapT, class KeyFrameT, class KeyFrameAndPoseT, class ConnectionsT, class LoopClosingT, class GetS, class PoseToS, class ToPose>
+inline void optimize_essential_graph(MapT* pMap, KeyFrameT* pLoopKF, KeyFrameT* pCurKF, const KeyFrameAndPoseT& NonCorrectedSim3,
+                                     const KeyFrameAndPoseT& CorrectedSim3, const ConnectionsT& LoopConnections, const bool& bFixScale, LoopClosingT* pLC,
+                                     const cv::Mat& Tbc, GetS sim3_get, PoseToS pose_to_sim3, ToPose to_pose, double* info = 0) {
+    const auto vpKFs = pMap->GetAllKeyFrames();
+    const auto vpMPs = pMap->GetAllMapPoints();
+    const int minFeat = 100;
+    std::vector<KeyFrameT*> kfs_v;
+    for (size_t i = 0; i < vpKFs.size(); i++) if (!vpKFs[i]->isBad()) kfs_v.push_back(vpKFs[i]);
+    if (kfs_v.empty()) return;
+    const int nk = (int)kfs_v.size();
+    std::map<const KeyFrameT*, int> kf_index;
+    std::vector<double> Scw((size_t)nk * 8), Smeas((size_t)nk * 8); std::vector<unsigned char> fixed(nk, 0);
+    for (int k = 0; k < nk; k++) {
+        KeyFrameT* pKF = kfs_v[k];
+        kf_index[pKF] = k;
+        typename KeyFrameAndPoseT::const_iterator it = CorrectedSim3.find(pKF);
+        if (it != CorrectedSim3.end()) sim3_get(it->second, &Scw[(size_t)k * 8]);
+        else pose_to_sim3(pKF->GetRotation(), pKF->GetTranslation(), &Scw[(size_t)k * 8]);
+        typename KeyFrameAndPoseT::const_iterator itn = NonCorrectedSim3.find(pKF);
+        if (itn != NonCorrectedSim3.end()) sim3_get(itn->second, &Smeas[(size_t)k * 8]);
+        else for (int c = 0; c < 8; c++) Smeas[(size_t)k * 8 + c] = Scw[(size_t)k * 8 + c];
+        fixed[k] = pKF == pLoopKF;
+    }
+    std::vector<int32_t> edge_idx; std::vector<unsigned char> edge_corrected;
+    auto vertex = [&](const KeyFrameT* pKF) -> int {
+        typename std::map<const KeyFrameT*, int>::const_iterator kit = kf_index.find(pKF);
+        if (kit == kf_index.end()) throw std::runtime_error("OptimizeEssentialGraph: the end of an edge has no vertex (a bad key frame, or one the map does not hold)");
+        return kit->second;
+    };
+    auto add_edge = [&](const KeyFrameT* pKFi, const KeyFrameT* pKFj, int corrected) {
+        const int i = vertex(pKFi), j = vertex(pKFj);
+        edge_idx.push_back(i); edge_idx.push_back(j); edge_corrected.push_back((unsigned char)corrected);
+    };
+    std::set<std::pair<long unsigned int, long unsigned int> > sInsertedEdges;
+    for (typename ConnectionsT::const_iterator mit = LoopConnections.begin(); mit != LoopConnections.end(); ++mit) {      // (:4385-4413)
+        KeyFrameT* pKF = mit->first;
+        const long unsigned int nIDi = pKF->mnId;
+        for (auto sit = mit->second.begin(); sit != mit->second.end(); ++sit) {
+            const long unsigned int nIDj = (*sit)->mnId;
+            if ((nIDi != pCurKF->mnId || nIDj != pLoopKF->mnId) && pKF->GetWeight(*sit) < minFeat) continue;
+            add_edge(pKF, *sit, 1);
+            sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+        }
+    }
+    for (int k = 0; k < nk; k++) {                                                                                     // (:4416-4516)
+        KeyFrameT* pKF = kfs_v[k];
+        KeyFrameT* pParentKF = pKF->GetParent();
+        if (pParentKF) add_edge(pKF, pParentKF, 0);
+        const std::set<KeyFrameT*> sLoopEdges = pKF->GetLoopEdges();
+        for (typename std::set<KeyFrameT*>::const_iterator sit = sLoopEdges.begin(); sit != sLoopEdges.end(); ++sit)
+            if ((*sit)->mnId < pKF->mnId) add_edge(pKF, *sit, 0);
+        const std::vector<KeyFrameT*> vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);
+        for (typename std::vector<KeyFrameT*>::const_iterator vit = vpConnectedKFs.begin(); vit != vpConnectedKFs.end(); ++vit) {
+            KeyFrameT* pKFn = *vit;
+            if (!pKFn || pKFn == pParentKF || pKF->hasChild(pKFn) || sLoopEdges.count(pKFn)) continue;
+            if (pKFn->isBad() || !(pKFn->mnId < pKF->mnId)) continue;
+            if (sInsertedEdges.count(std::make_pair(std::min(pKF->mnId, pKFn->mnId), std::max(pKF->mnId, pKFn->mnId)))) continue;
+            add_edge(pKF, pKFn, 0);
+        }
+    }
+    typedef typename std::remove_pointer<typename std::remove_reference<decltype(vpMPs[0])>::type>::type MapPointT;
+    std::vector<MapPointT*> pts_v;
+    for (size_t i = 0; i < vpMPs.size(); i++) if (!vpMPs[i]->isBad()) pts_v.push_back(vpMPs[i]);
+    const int np = (int)pts_v.size();
+    std::vector<float> points((size_t)(np + 1) * 3), points_out((size_t)(np + 1) * 3); std::vector<int32_t> point_ref(np + 1, -1);
+    for (int p = 0; p < np; p++) {                                                                                     // (:4558-4574)
+        MapPointT* pMP = pts_v[p];
+        const cv::Mat Pw = pMP->GetWorldPos();
+        for (int c = 0; c < 3; c++) points[(size_t)p * 3 + c] = Pw.template at<float>(c);
+        if (pMP->mnCorrectedByKF == pCurKF->mnId) {
+            point_ref[p] = -1;                                       // vScw is indexed by id: find the key frame with that id
+            for (int k = 0; k < nk; k++) if (kfs_v[k]->mnId == (long unsigned int)pMP->mnCorrectedReference) { point_ref[p] = k; break; }
+            if (point_ref[p] < 0) throw std::runtime_error("OptimizeEssentialGraph: mnCorrectedReference of a map point has no vertex");
+        } else point_ref[p] = vertex(pMP->GetReferenceKeyFrame());
+    }
+    const int ne = (int)edge_corrected.size();
+    std::vector<double> Scw_out((size_t)nk * 8), Tcw_out((size_t)nk * 12); double info_[6];
+    viorb_eg_config cfg; cfg.iterations = 20; cfg.fix_scale = bFixScale ? 1 : 0;
+    check(viorb_optimize_essential_graph(&cfg, &Scw[0], &Smeas[0], &fixed[0], nk, ne ? &edge_idx[0] : 0, ne ? &edge_corrected[0] : 0, ne, &points[0], &point_ref[0], np,
+                                         &Scw_out[0], &Tcw_out[0], &points_out[0], info_), "Optimizer::OptimizeEssentialGraph");
+    if (info) for (int k = 0; k < 6; k++) info[k] = info_[k];
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
+    for (int k = 0; k < nk; k++) {                                                                                     // (:4527-4548)
+        const cv::Mat Tiw = to_pose(&Tcw_out[(size_t)k * 12]);
+        kfs_v[k]->SetPose(Tiw);
+        kfs_v[k]->UpdateNavStatePVRFromTcw(Tiw, Tbc);
+    }
+    for (int p = 0; p < np; p++) {                                                                                     // (:4575-4580)
+        cv::Mat Pw(3, 1, CV_32F);
+        for (int c = 0; c < 3; c++) Pw.template at<float>(c) = points_out[(size_t)p * 3 + c];
+        pts_v[p]->SetWorldPos(Pw);
+        pts_v[p]->UpdateNormalAndDepth();
+    }
+    if (pLC) pLC->SetMapUpdateFlagInTracking(true);
 }
 
 } // namespace viorb_shim

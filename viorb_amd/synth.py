@@ -1284,3 +1284,90 @@ def make_sim3_match_problem(seed, n1=1000, n2=1000, n_common=500, fix_scale=Fals
                 bounds4=np.array([0, w, 0, h], np.float32),
                 loop=dict(pts_f=lp_f, pts_desc=lp_d, valid=valid, Scw=Scw, feat_taken=al1.copy(), source=source),
                 fuse=dict(frames=frames, Scw=np.stack(Scws), valid=np.stack(valids)))
+
+
+def make_essential_graph_problem(seed, N=20, fix_scale=False, rot_drift=0.004, trans_drift=0.01, scale_drift=0.01, n_corrected=3, n_covis=3,
+                                 loop_edges=0, duplicate_pair=False, extra_fixed=(), consistent=False, n_points=0, skip_frac=0.1, radius=5.0, turn=1.0):
+    """A closed trajectory for the essential-graph solve (Optimizer::OptimizeEssentialGraph): N key frames on a circle, key frame 0 the
+    fixed loop key frame, the odometry between successive key frames drifting in rotation (rot_drift radians per step, a bias plus
+    noise), translation (trans_drift of a step) and, without fix_scale, scale (scale_drift per step), so that key frame N - 1 does not
+    meet key frame 0 again. The last key frame and n_corrected - 1 of its predecessors carry corrected poses in Scw (the loop's Sim3 for
+    the last one, Sic * Scw for the others, as LoopClosing::CorrectLoop propagates it) and their drifted ones in Smeas; every other row
+    of Scw is the drifted pose (R, t, 1) and equals its row of Smeas. Edges (vertex 0 = i, vertex 1 = j): a spanning-tree edge (k, k - 1)
+    of every key frame, covisibility edges to the predecessors k - 2 .. k - n_covis, `loop_edges` older loop edges between distant key
+    frames (all edge_corrected = 0), and LoopConnections edges from every corrected key frame to key frames 0 and 1 (edge_corrected =
+    1). duplicate_pair: the pair (N - 1, N - 2) a second time as a LoopConnections edge. extra_fixed: further fixed vertices (with 1
+    among them the spanning-tree edge (1, 0) joins two fixed vertices). consistent: no drift and no correction, so every error is zero
+    from the start. turn: 1 = the camera follows the tangent (a full revolution of yaw), less = it sways by that many radians. n_points float32 points, each seen from a reference key frame (point_ref), skip_frac of them with point_ref = -1.
+    Returns Scw, Smeas [N,8] = r(x y z w) t s, fixed [N], edge_idx [E,2], edge_corrected [E], points [P,3], point_ref [P], fix_scale and
+    the drift-free Scw_true. numpy only."""
+    rng = np.random.Generator(np.random.PCG64(seed + 626262))
+    if consistent:
+        rot_drift = trans_drift = scale_drift = 0.0; n_corrected = 0
+    n_corrected = min(n_corrected, N - 1)
+
+    def pose(k):                                                   # camera k: on the circle, looking along the tangent, Tcw = (R, t)
+        a = 2 * np.pi * k / max(N, 8)
+        Rwc = _rotvec_to_R(np.array([0, 0, turn * a if turn == 1.0 else turn * np.sin(a)])) @ _rotvec_to_R(np.array([0.05 * np.sin(3 * a), 0.03 * np.cos(2 * a), 0]))
+        twc = np.array([radius * np.cos(a), radius * np.sin(a), 0.2 * np.sin(2 * a)])
+        return Rwc.T, -Rwc.T @ twc
+    true = [pose(k) for k in range(N)]
+    bias = rng.normal(0, 1, 3); bias /= max(np.linalg.norm(bias), 1e-12)
+    drift = [true[0]]
+    sc = 1.0
+    for k in range(1, N):
+        Rrel = true[k][0] @ true[k - 1][0].T                        # T_k,k-1
+        trel = true[k][1] - Rrel @ true[k - 1][1]
+        if not fix_scale:
+            sc *= 1.0 + scale_drift
+        Rrel = _rotvec_to_R(rot_drift * (bias + 0.5 * rng.normal(0, 1, 3))) @ Rrel
+        trel = sc * trel * (1 + trans_drift * rng.normal(0, 1, 3))
+        drift.append((Rrel @ drift[-1][0], Rrel @ drift[-1][1] + trel))
+    row = lambda R, t, s: np.concatenate([_R_to_quat(R), t, [s]])
+    Smeas = np.stack([row(R, t, 1.0) for R, t in drift])
+    Scw = Smeas.copy()
+    if n_corrected:
+        c = N - 1
+        s = 1.0 if fix_scale else 1.0 / sc                          # the drifted map around the last key frame is sc times too large
+        Rc, tc = true[c][0], true[c][1]
+        Scw[c] = row(Rc, tc, s)                                     # the loop's Sim3: a world point X of the old map is s Rc X + tc in c
+        for i in range(N - n_corrected, N - 1):                     # Sic * Scw with Sic = Tiw Twc of the drifted poses
+            Ric = drift[i][0] @ drift[c][0].T
+            tic = drift[i][1] - Ric @ drift[c][1]
+            Scw[i] = row(Ric @ Rc, Ric @ tc + tic, s)
+    fixed = np.zeros(N, np.uint8); fixed[0] = 1
+    for v in extra_fixed:
+        fixed[int(v)] = 1
+    edges, corr = [], []
+    corrected = list(range(N - n_corrected, N))
+    for k in corrected:                                             # LoopConnections first, as the reference adds them
+        for j in (0, 1):
+            if j < k and j not in corrected:
+                edges.append((k, j)); corr.append(1)
+    if duplicate_pair and N >= 3:
+        edges.append((N - 1, N - 2)); corr.append(1)
+    inserted = set(edges)                                           # sInsertedEdges: a covisibility edge of such a pair is left out
+    far = [(k, k - max(7, N // 4)) for k in range(N - 1, 0, -1) if k - max(7, N // 4) >= 0]
+    far = [far[q] for q in rng.permutation(len(far))[:loop_edges]] if loop_edges else []
+    for k in range(1, N):
+        edges.append((k, k - 1)); corr.append(0)
+        for (a, b) in far:
+            if a == k:
+                edges.append((a, b)); corr.append(0)
+        for d in range(2, n_covis + 1):
+            if k - d >= 0 and (k, k - d) not in inserted:
+                edges.append((k, k - d)); corr.append(0)
+    P, ref = np.zeros((n_points, 3), np.float32), np.zeros(n_points, np.int32)
+    for p in range(n_points):
+        r = int(rng.integers(0, N))
+        Xc = np.array([rng.uniform(-2, 2), rng.uniform(-1, 1), rng.uniform(2, 8)])
+        R, t, s = _quat_to_R(Scw[r, :4]), Scw[r, 4:7], Scw[r, 7]
+        P[p] = (R.T @ (Xc - t) / s).astype(np.float32)              # the point as the input map holds it: Srw^-1 of its camera position
+        ref[p] = -1 if rng.uniform() < skip_frac else r
+    return dict(Scw=Scw, Smeas=Smeas, fixed=fixed, edge_idx=np.array(edges, np.int32).reshape(-1, 2), edge_corrected=np.array(corr, np.uint8),
+                points=P, point_ref=ref, fix_scale=bool(fix_scale), Scw_true=np.stack([row(R, t, 1.0) for R, t in true]))
+
+
+def _quat_to_R(q):
+    from scipy.spatial.transform import Rotation
+    return Rotation.from_quat(q).as_matrix()
