@@ -930,6 +930,10 @@ int viorb_debug_gba_last_trials(uint8_t* accepted, int cap, int* n);
  * key-frame grid, in a header of their own. */
 #include "viorb_sim3_match.h"
 
+/* The monocular matcher of map initialisation (ORBmatcher::SearchForInitialization), whose matches feed viorb_two_view_init_device, and
+ * KeyFrame::ComputeSceneMedianDepth, in a header of their own. */
+#include "viorb_search_init.h"
+
 /* The essential-graph optimisation of loop closing (Optimizer::OptimizeEssentialGraph): a Sim3 pose graph on the global adjustments'
  * factorisation, in a header of its own. */
 #include "viorb_essential_graph.h"

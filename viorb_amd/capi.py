@@ -127,6 +127,14 @@ class S3mSide(C.Structure):
     _fields_ = [("kf", S3mKeyframes)] + [(n, C.c_void_p) for n in ("pose12", "has_point", "pts_f", "pts_desc", "already")]
 
 
+SEARCH_INIT_OUTPUT_FIELDS = ("matches21", "matched_distance", "rot_hist", "reason", "xy1", "xy2", "sweeps")
+
+
+class SearchInitOutputs(C.Structure):
+    """viorb_search_init_outputs (include/viorb_search_init.h)."""
+    _fields_ = [(n, C.c_void_p) for n in SEARCH_INIT_OUTPUT_FIELDS]
+
+
 class TrackerConfig(C.Structure):
     """viorb_tracker_config (include/viorb.h)."""
     _fields_ = [("extractor", ExtractorParams), ("frontend", FrontendConfig), ("width", C.c_int32), ("height", C.c_int32), ("batch", C.c_int32),
@@ -366,6 +374,21 @@ SIGNATURES_SIM3_MATCH = {
     "viorb_debug_claim_in_order": (i32, [vp, vp, i32, i32, vp, i32, vp, vp]),
 }
 
+# mirrors include/viorb_search_init.h (the monocular matcher and the scene depth); tests/test_search_init_ref.py checks names and argument
+# counts against it
+SIGNATURES_SEARCH_INIT = {
+    "viorb_search_init_workspace_bytes": (sz, [i32, i32]),
+    "viorb_search_init_shape": (i32, [vp]),
+    "viorb_search_for_initialization_device": (i32, [vp, vp, vp, PP(S3mKeyframes), vp, i32, i32, vp, i32, f32, i32, vp, vp, PP(SearchInitOutputs),
+                                                     vp, sz, vp]),
+    "viorb_search_for_initialization": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, f32, i32, vp, vp, PP(SearchInitOutputs)]),
+    "viorb_scene_median_depth_device": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "viorb_scene_median_depth": (i32, [vp, vp, vp, i32, i32, vp, vp]),
+    "viorb_debug_search_init_ordered": (i32, [vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp]),
+    "viorb_debug_search_init_window": (i32, [vp, i32, vp, vp, vp, f32, f32, f32, i32, vp, vp]),
+    "viorb_debug_scene_depth": (f32, [vp, vp]),
+}
+
 # mirrors include/viorb_essential_graph.h (the essential-graph optimisation); tests/test_essential_graph_ref.py checks names and argument
 # counts against it
 SIGNATURES_ESSENTIAL_GRAPH = {
@@ -396,7 +419,8 @@ def lib():
             pass
         L = C.CDLL(SO_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GLOBAL_BA_SE3.items()) + list(SIGNATURES_TWO_VIEW.items()) \
-                + list(SIGNATURES_SIM3.items()) + list(SIGNATURES_SIM3_MATCH.items()) + list(SIGNATURES_ESSENTIAL_GRAPH.items()):
+                + list(SIGNATURES_SIM3.items()) + list(SIGNATURES_SIM3_MATCH.items()) + list(SIGNATURES_ESSENTIAL_GRAPH.items()) \
+                + list(SIGNATURES_SEARCH_INIT.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

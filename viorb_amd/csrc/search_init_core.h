@@ -1,0 +1,167 @@
+// viorb_amd/csrc/search_init_core.h — the arithmetic of the monocular matcher ORBmatcher::SearchForInitialization and of
+// KeyFrame::ComputeSceneMedianDepth, shared by the HIP kernels of search_init.hip and by the host-only hooks viorb_debug_search_init_*
+// (the CPU test-suite compares them with tests/search_init_ref.py without a GPU; tests/cpp/search_init_core_host_test.cpp runs them under
+// the address and undefined-behaviour sanitizers).
+//
+// What is restated (reference file:line):
+//   ORBmatcher::SearchForInitialization        src/ORBmatcher.cc:405-520  (inner loop :436-457, accept :459-471, bin :475-480)
+//   Frame::GetFeaturesInArea (cell rectangle)  src/Frame.cc:507-526
+//   ORBmatcher::ComputeThreeMaxima             src/ORBmatcher.cc:1602-1643
+//   KeyFrame::ComputeSceneMedianDepth          src/KeyFrame.cc:970-1000
+// Everything is integer arithmetic, float compares and individually rounded float products; nothing depends on contraction.
+#pragma once
+#include <limits.h>
+#include "two_view_core.h"          // tv_float_key / tv_key_float: the order-preserving float map of the radix select
+
+namespace viorb {
+
+// reason[i]: the statement of the reference that ended point i (VIORB_SI_* of include/viorb_search_init.h)
+enum { SI_MATCHED = 0, SI_NOT_CANDIDATE = 1, SI_NO_FEATURE_IN_WINDOW = 2, SI_ABOVE_THRESHOLD = 3, SI_RATIO = 4, SI_DISPLACED = 5, SI_ROTATION = 6 };
+enum { SI_GRID_COLS = 64, SI_GRID_ROWS = 48, SI_GRID_CELLS = SI_GRID_COLS * SI_GRID_ROWS, SI_TH_LOW = 50, SI_HISTO = 30 };
+// the state of a point in the ordered phase: distance << 16 | feature when the point is accepted (:461), SI_NONE otherwise
+static const uint32_t SI_NONE = 0xffffffffu;
+
+struct SiCam { float minX, maxX, minY, maxY, wInv, hInv; };
+// nMinCellX nMaxCellX nMinCellY nMaxCellY; empty: one of the four early returns fired
+struct SiRect { int x0, x1, y0, y1; bool empty; };
+
+// (int) of a float as x86 converts it: a value no int holds gives INT_MIN (a prev_matched far outside the image)
+MAP_HD int si_to_int(float q) { return (q > -2147483648.0f && q < 2147483648.0f) ? (int)q : INT_MIN; }
+
+// Frame::GetFeaturesInArea :512-526: the float expressions, floor / ceil, the clamps and the early returns in the reference's order
+MAP_HD void si_window(const SiCam& C, float x, float y, float r, SiRect& R) {
+    R.x0 = R.y0 = 0; R.x1 = R.y1 = -1; R.empty = true;
+    const int a = si_to_int(floorf((x - C.minX - r) * C.wInv));
+    R.x0 = a < 0 ? 0 : a;
+    if (R.x0 >= SI_GRID_COLS) return;
+    const int b = si_to_int(ceilf((x - C.minX + r) * C.wInv));
+    R.x1 = b > SI_GRID_COLS - 1 ? SI_GRID_COLS - 1 : b;
+    if (R.x1 < 0) return;
+    const int c = si_to_int(floorf((y - C.minY - r) * C.hInv));
+    R.y0 = c < 0 ? 0 : c;
+    if (R.y0 >= SI_GRID_ROWS) return;
+    const int d = si_to_int(ceilf((y - C.minY + r) * C.hInv));
+    R.y1 = d > SI_GRID_ROWS - 1 ? SI_GRID_ROWS - 1 : d;
+    if (R.y1 < 0) return;
+    R.empty = false;
+}
+
+// The level filter of GetFeaturesInArea(x, y, r, level1, level1) for a point that passed :422 (level1 <= 0): bCheckLevels is
+// (level1 > 0) || (level1 >= 0), so level 0 admits level-0 features only and a negative level (no extractor produces one) admits all.
+MAP_HD bool si_level_ok(int level1, int octave2) { return level1 < 0 || octave2 == level1; }
+
+// A candidate that can be left out of a point's list without changing any result. It is never the accepted best (distance > TH_LOW), and
+// as second best it passes the ratio test of every best <= TH_LOW ((float)d * ratio > TH_LOW >= best), exactly as the larger second best
+// or the INT_MAX that takes its place does ((float)d' * ratio >= (float)d * ratio for d' >= d and ratio > 0: float products are monotone).
+// When it would be the best, the point ends above the threshold with or without it.
+MAP_HD bool si_keep(int d, float nnratio) { return d <= SI_TH_LOW || !((float)d * nnratio > (float)SI_TH_LOW); }
+
+// The inner loop :436-457 over the candidates one at a time, in visiting order; seen = vMatchedDistance[i2] as this point sees it.
+struct SiPick { int best, dist, dist2; };
+MAP_HD void si_pick_init(SiPick& P) { P.best = -1; P.dist = INT_MAX; P.dist2 = INT_MAX; }
+MAP_HD void si_pick_visit(SiPick& P, int d, int f, int seen) {
+    if (seen <= d) return;                                   // :444, for best and second best alike
+    if (d < P.dist) { P.dist2 = P.dist; P.dist = d; P.best = f; }
+    else if (d < P.dist2) P.dist2 = d;
+}
+// :459-461. The state word of the point, and why it is not accepted.
+MAP_HD uint32_t si_decide(const SiPick& P, float nnratio, int& why) {
+    if (!(P.dist <= SI_TH_LOW)) { why = SI_ABOVE_THRESHOLD; return SI_NONE; }
+    if (!((float)P.dist < (float)P.dist2 * nnratio)) { why = SI_RATIO; return SI_NONE; }
+    why = SI_MATCHED;
+    return ((uint32_t)P.dist << 16) | (uint32_t)P.best;
+}
+
+// vMatchedDistance[f] as point p sees it, from the points accepted on f (a linked list head[f] -> next[..], in any order): the distance of
+// the latest of them below p, INT_MAX when there is none.
+MAP_HD int si_seen(const int* head, const int* next, const uint32_t* st, int f, int p) {
+    int bq = -1;
+    for (int q = head[f]; q >= 0; q = next[q]) if (q < p && q > bq) bq = q;
+    return bq < 0 ? INT_MAX : (int)(st[bq] >> 16);
+}
+
+// :475-480: rot in float, + 360 when negative, round half away from zero of rot * (1.0f / 30), 30 wraps to 0
+MAP_HD int si_rot_bin(float angle1, float angle2) {
+    const float factor = 1.0f / SI_HISTO;
+    float rot = angle1 - angle2;
+    if (rot < 0.0f) rot += 360.0f;
+    const float b = roundf(rot * factor);
+    // 30 wraps to 0; the reference asserts the range (angles are in [0, 360)), a value outside it (a NaN angle) goes to bin 0 here
+    return (b >= 0.0f && b < (float)SI_HISTO) ? (int)b : 0;
+}
+
+// ComputeThreeMaxima (:1602-1643) over the bins' sizes: keep[i] = bin i is one of ind1 ind2 ind3
+MAP_HD void si_three_maxima(const int* hist, int* keep) {
+    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
+    for (int i = 0; i < SI_HISTO; i++) {
+        const int sz = hist[i];
+        if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
+        else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
+        else if (sz > max3) { max3 = sz; ind3 = i; }
+    }
+    if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
+    else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
+    for (int i = 0; i < SI_HISTO; i++) keep[i] = (i == ind1 || i == ind2 || i == ind3);
+}
+
+// The ordered phase (:418-487) as a fixed-point iteration. st[p] is point p's state; a sweep evaluates every point against the states of
+// the previous sweep (st -> st2), so the points of a sweep are independent and the result does not depend on their order. Point p reads
+// only the states of points q < p that hold a feature of p's list, so after k sweeps every point whose chain of such predecessors is
+// shorter than k has the state the literal loop gives it; a sweep that changes nothing is the loop's result. Sweeps <= longest chain + 1
+// <= npts + 1. cand [npts][lcap] = distance << 16 | feature in visiting order, cand_n [npts] <= lcap. head [nfeat], next [npts],
+// st / st2 [npts] are scratch; the final states are in st. Returns the number of sweeps. This is the serial form of k_si_ordered.
+inline int si_ordered_sweeps(const uint32_t* cand, const int32_t* cand_n, int npts, int lcap, int nfeat, float nnratio, uint32_t* st, uint32_t* st2,
+                             int* why, int* head, int* next) {
+    for (int p = 0; p < npts; p++) { st[p] = SI_NONE; why[p] = SI_ABOVE_THRESHOLD; }
+    int sweeps = 0;
+    for (;;) {
+        sweeps++;
+        for (int f = 0; f < nfeat; f++) head[f] = -1;
+        for (int p = 0; p < npts; p++) if (st[p] != SI_NONE) { const int f = (int)(st[p] & 0xffffu); next[p] = head[f]; head[f] = p; }
+        bool changed = false;
+        for (int p = 0; p < npts; p++) {
+            const int n = cand_n[p] < lcap ? cand_n[p] : lcap;
+            SiPick P;
+            si_pick_init(P);
+            for (int k = 0; k < n; k++) {
+                const uint32_t e = cand[(size_t)p * lcap + k];
+                const int f = (int)(e & 0xffffu), d = (int)(e >> 16);
+                if (f < nfeat) si_pick_visit(P, d, f, si_seen(head, next, st, f, p));
+            }
+            st2[p] = si_decide(P, nnratio, why[p]);
+            changed |= st2[p] != st[p];
+        }
+        for (int p = 0; p < npts; p++) st[p] = st2[p];
+        if (!changed) return sweeps;
+    }
+}
+
+// What the main loop leaves behind, from the final states: vnMatches21 / vMatchedDistance = the latest point accepted on a feature and its
+// distance; vnMatches12[p] = its feature while no later point was accepted on it. Returns nmatches before the rotation step.
+inline int si_after_loop(const uint32_t* st, int npts, int nfeat, int32_t* matches12, int32_t* matches21, int32_t* matched_distance) {
+    for (int f = 0; f < nfeat; f++) { matches21[f] = -1; matched_distance[f] = INT_MAX; }
+    for (int p = 0; p < npts; p++) if (st[p] != SI_NONE) { const int f = (int)(st[p] & 0xffffu); matches21[f] = p; matched_distance[f] = (int)(st[p] >> 16); }
+    int nm = 0;
+    for (int p = 0; p < npts; p++) {
+        const bool hit = st[p] != SI_NONE && matches21[st[p] & 0xffffu] == p;
+        matches12[p] = hit ? (int)(st[p] & 0xffffu) : -1;
+        nm += hit;
+    }
+    return nm;
+}
+
+// KeyFrame::ComputeSceneMedianDepth :992: Rcw2.dot(x3Dw) + zcw, the dot accumulated in double (Mat::dot), zcw added in double, to float
+MAP_HD float si_depth(const float* pose12, const float* X) {
+    const double dot = ((double)pose12[6] * (double)X[0] + (double)pose12[7] * (double)X[1]) + (double)pose12[8] * (double)X[2];
+    return (float)(dot + (double)pose12[11]);
+}
+
+// One step of the radix select over order-preserving keys: the digit of the k-th smallest among the keys that share `prefix`, from their
+// histogram; k becomes the rank inside that digit.
+MAP_HD int si_select_digit(const int* hist256, int& k) {
+    int d = 0;
+    while (d < 255 && k >= hist256[d]) { k -= hist256[d]; d++; }
+    return d;
+}
+
+} // namespace viorb

@@ -7,6 +7,7 @@
 //                           for all neighbours in one call                                              src/LocalMapping.cc:1242-1464
 //   update_map_points       MapPoint::ComputeDistinctiveDescriptors + MapPoint::UpdateNormalAndDepth for a list of points
 //                                                                                                       src/MapPoint.cc:249-314, 337-378
+//   compute_scene_median_depth   KeyFrame::ComputeSceneMedianDepth(q)                                         src/KeyFrame.cc:970-1000
 //   try_init_vio            LocalMapping::TryInitVIO steps 1-3: gyro bias, scale, gravity, accelerometer bias  src/LocalMapping.cc:279-504
 //   try_init_vio_apply      the NavState / pose / map-point write-back once bVIOInited                         src/LocalMapping.cc:585-786
 //
@@ -41,6 +42,22 @@ template <class KeyFrameT> inline viorb_mapping_camera mapping_camera(const KeyF
     c.nlevels = pKF->mnScaleLevels;
     for (int l = 0; l < 16; l++) { const int k = l < c.nlevels ? l : c.nlevels - 1; c.scale_factors[l] = pKF->mvScaleFactors[k]; c.level_sigma2[l] = pKF->mvLevelSigma2[k]; }
     return c;
+}
+
+// KeyFrame::ComputeSceneMedianDepth(q) (src/KeyFrame.cc:970-1000): the body becomes `return viorb_shim::compute_scene_median_depth(this, q);`.
+// Every feature with a map point counts, bad or not, as in the reference. -1 for a key frame without a point.
+template <class KeyFrameT> inline float compute_scene_median_depth(KeyFrameT* pKF, int q) {
+    const int n = pKF->N;
+    std::vector<float> X((size_t)(n + 1) * 3, 0.f); std::vector<unsigned char> has(n + 1, 0);
+    for (int i = 0; i < n; i++) {
+        if (!pKF->GetMapPoint(i)) continue;
+        const cv::Mat Pw = pKF->GetMapPoint(i)->GetWorldPos();
+        has[i] = 1; for (int c = 0; c < 3; c++) X[(size_t)i * 3 + c] = Pw.at<float>(c);
+    }
+    float pose[12], median = -1.f; int32_t nd = 0;
+    flatten_pose(pKF->GetPose(), pose);
+    check(viorb_scene_median_depth(pose, &X[0], &has[0], n, q, &median, &nd), "ComputeSceneMedianDepth");
+    return median;
 }
 
 // vF12[j] = ComputeF12(pCur, vpNeighKFs[j]) (3 x 3 CV_32F), vMedianDepth[j] = vpNeighKFs[j]->ComputeSceneMedianDepth(2) (unused when

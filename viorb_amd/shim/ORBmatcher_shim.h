@@ -14,6 +14,7 @@
 //   search_by_sim3                   ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th)       :1102-1326
 //   search_by_projection_sim3        ORBmatcher::SearchByProjection(KeyFrame*, Scw, vpPoints, vpMatched, th)    :290-403
 //   fuse_sim3                        ORBmatcher::Fuse(KeyFrame*, Scw, vpPoints, th, vpReplacePoint)             :977-1100
+//   search_for_initialization        ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize)   :405-520
 //
 // Two accessors the reference does not have are needed on MapPoint (its mfMinDistance / mfMaxDistance are protected and the existing
 // getters return them scaled by 0.8 / 1.2): `float GetMinDistance()` and `float GetMaxDistance()`, returning the raw members under
@@ -325,6 +326,27 @@ inline int fuse_sim3(KeyFrameT* pKF, const cv::Mat& Scw, const std::vector<MapPo
         }
     }
     return nFused;
+}
+
+// ---- the monocular matcher of map initialisation (include/viorb_search_init.h) ----------------------------------------------------------
+// ORBmatcher::SearchForInitialization(Frame &F1, Frame &F2, vector<cv::Point2f> &vbPrevMatched, vector<int> &vnMatches12, int windowSize):
+// nnratio = mfNNratio, check_ori = mbCheckOrientation. vnMatches12 is assigned anew (:408), vbPrevMatched is overwritten where a point
+// ends matched (:515-517), nmatches is returned. PointVec: vector<cv::Point2f> (any element with float x, y).
+template <class FrameT, class PointVec>
+inline int search_for_initialization(FrameT& F1, FrameT& F2, PointVec& vbPrevMatched, std::vector<int>& vnMatches12, int windowSize, float nnratio,
+                                     bool check_ori) {
+    const int n1 = (int)F1.mvKeysUn.size(), n2 = (int)F2.mvKeysUn.size();
+    std::vector<viorb_keypoint> k1, k2;
+    flatten_keys(F1.mvKeysUn, n1, k1); flatten_keys(F2.mvKeysUn, n2, k2);
+    std::vector<float> prev((size_t)(n1 + 1) * 2, 0.f);
+    for (int i = 0; i < n1; i++) { prev[2 * i] = vbPrevMatched[i].x; prev[2 * i + 1] = vbPrevMatched[i].y; }
+    const float bounds[4] = {F2.mnMinX, F2.mnMaxX, F2.mnMinY, F2.mnMaxY};
+    std::vector<int32_t> m12(n1 + 1, -1); int nmatches = 0;
+    check(viorb_search_for_initialization(&k1[0], F1.mDescriptors.data, n1, &k2[0], F2.mDescriptors.data, n2, &prev[0], bounds, windowSize, nnratio,
+                                          check_ori ? 1 : 0, &m12[0], &nmatches, 0), "SearchForInitialization");
+    vnMatches12.assign(m12.begin(), m12.begin() + n1);
+    for (int i = 0; i < n1; i++) if (m12[i] >= 0) { vbPrevMatched[i].x = prev[2 * i]; vbPrevMatched[i].y = prev[2 * i + 1]; }
+    return nmatches;
 }
 
 } // namespace viorb_shim

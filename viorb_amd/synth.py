@@ -1286,6 +1286,79 @@ def make_sim3_match_problem(seed, n1=1000, n2=1000, n_common=500, fix_scale=Fals
                 fuse=dict(frames=frames, Scw=np.stack(Scws), valid=np.stack(valids)))
 
 
+def make_search_init_problem(seed, n_scene=400, shared=0.8, siblings=40, twins=30, wrong_angles=0.1, upper_share=0.2, geometry=False,
+                             flow=(14.0, -9.0), w=752, h=480):
+    """Two monocular frames of a common scene with a flow between them, for ORBmatcher::SearchForInitialization: kps1 / kps2 (capi.KP_DTYPE
+    with octaves and angles), desc1 / desc2 [n,32], prev_matched [n1,2] = the key points of frame 1 (as Tracking sets mvbPrevMatched),
+    bounds4, truth12 [n1] (the feature of frame 2 that shows the same scene point, or -1). Frame 1 sees `shared` of the n_scene scene
+    features, frame 2 all of them; descriptors differ by 0..30 bit flips, a share by 45..80 (above TH_LOW).
+    siblings: extra points of frame 1 beside a scene point with its descriptor but for a few bits: they compete for one feature of frame 2
+    (displacements, order dependence). twins: extra features of frame 2 beside a scene feature with its descriptor but for 0..4 bits:
+    second-best distances that fail the ratio test, and exact ties. wrong_angles: the share of frame-2 features turned by 60..300 degrees
+    (removed by the rotation histogram). upper_share: the share of scene features above pyramid level 0.
+    geometry=True: the positions and true matches are those of make_two_view_init_problem(seed, n1=n_scene, n2=n_scene,
+    n_matches=shared * n_scene) (K4, R21, t21 in the result) and upper_share only applies to unmatched key points, so that the matches
+    initialise. Both frames are shuffled at the end. numpy only."""
+    from . import capi
+    rng = np.random.Generator(np.random.PCG64(seed + 515151))
+    ns = int(round(shared * n_scene))
+    extra = {}
+    if geometry:
+        TV = make_two_view_init_problem(seed, n1=n_scene, n2=n_scene, n_matches=ns, outlier_share=0.0)
+        xy1, xy2 = TV["xy1"].astype(np.float64), TV["xy2"].astype(np.float64)
+        pair = TV["matches12"].astype(np.int64)
+        keep1 = np.nonzero(pair >= 0)[0]                                   # frame 1: the matched key points (siblings are added below)
+        xy1, pair = xy1[keep1], pair[keep1]
+        extra = dict(K4=TV["K4"], R21=TV["R21"], t21=TV["t21"])
+    else:
+        xy2 = np.stack([rng.uniform(15, w - 15, n_scene), rng.uniform(15, h - 15, n_scene)], 1)
+        pair = rng.permutation(n_scene)[:ns]
+        xy1 = xy2[pair] - np.array(flow) + rng.normal(0, 3.0, (ns, 2))
+    n2 = len(xy2)
+    oct2 = np.where(rng.random(n2) < upper_share, rng.integers(1, 4, n2), 0)
+    if geometry:
+        oct2[pair] = 0
+    ang2 = rng.uniform(0, 360, n2)
+    desc2 = rng.integers(0, 256, (n2, 32)).astype(np.uint8)
+    # frame 1: the scene point's descriptor with flips, its octave (a few a level off), its angle less a roll
+    flips = np.where(rng.random(ns) < 0.12, rng.integers(45, 81, ns), rng.integers(0, 31, ns))
+    desc1 = np.stack([_flip_bits(rng, desc2[p], int(k))[0] for p, k in zip(pair, flips)])
+    oct1 = oct2[pair].copy()
+    off = rng.random(ns) < (0.0 if geometry else 0.03)
+    oct1[off] = 1 - np.minimum(oct1[off], 1)
+    ang1 = (ang2[pair] - 6.0 + rng.normal(0, 2.0, ns)) % 360.0
+    turned = rng.random(ns) < wrong_angles
+    ang1[turned] = (ang1[turned] + rng.uniform(60, 300, turned.sum())) % 360.0
+    truth = pair.copy()
+    # siblings of frame 1
+    src = rng.integers(0, ns, siblings)
+    s_xy = xy1[src] + rng.uniform(-10, 10, (siblings, 2))
+    s_desc = np.stack([_flip_bits(rng, desc1[s], int(k))[0] for s, k in zip(src, rng.integers(0, 7, siblings))]) if siblings else np.zeros((0, 32), np.uint8)
+    xy1 = np.concatenate([xy1, s_xy]); desc1 = np.concatenate([desc1, s_desc]); oct1 = np.concatenate([oct1, np.zeros(siblings, np.int64)])
+    ang1 = np.concatenate([ang1, (ang1[src] + rng.normal(0, 2.0, siblings)) % 360.0]); truth = np.concatenate([truth, np.full(siblings, -1)])
+    # twins of frame 2
+    tsrc = pair[rng.integers(0, ns, twins)]
+    t_xy = xy2[tsrc] + rng.uniform(-30, 30, (twins, 2))
+    t_desc = np.stack([_flip_bits(rng, desc2[s], int(k))[0] for s, k in zip(tsrc, rng.integers(0, 5, twins))]) if twins else np.zeros((0, 32), np.uint8)
+    xy2 = np.concatenate([xy2, t_xy]); desc2 = np.concatenate([desc2, t_desc]); oct2 = np.concatenate([oct2, np.zeros(twins, np.int64)])
+    ang2 = np.concatenate([ang2, (ang2[tsrc] + rng.normal(0, 2.0, twins)) % 360.0])
+    xy1[:, 0] = np.clip(xy1[:, 0], 1, w - 2); xy1[:, 1] = np.clip(xy1[:, 1], 1, h - 2)
+    xy2[:, 0] = np.clip(xy2[:, 0], 1, w - 2); xy2[:, 1] = np.clip(xy2[:, 1], 1, h - 2)
+    p1, p2 = rng.permutation(len(xy1)), rng.permutation(len(xy2))
+    inv2 = np.empty(len(xy2), np.int64); inv2[p2] = np.arange(len(xy2))
+
+    def frame(xy, octave, angle, desc, perm):
+        k = np.zeros(len(perm), capi.KP_DTYPE)
+        k["x"], k["y"], k["octave"], k["angle"] = xy[perm, 0], xy[perm, 1], octave[perm], angle[perm]
+        k["size"] = np.floor(31.0 * 1.2 ** octave[perm]); k["response"] = rng.uniform(20, 120, len(perm)); k["class_id"] = -1
+        return k, np.ascontiguousarray(desc[perm])
+    k1, d1 = frame(xy1, oct1, ang1, desc1, p1)
+    k2, d2 = frame(xy2, oct2, ang2, desc2, p2)
+    truth = np.where(truth >= 0, inv2[np.maximum(truth, 0)], -1)[p1].astype(np.int32)
+    return dict(kps1=k1, desc1=d1, kps2=k2, desc2=d2, prev_matched=np.stack([k1["x"], k1["y"]], 1).astype(np.float32), truth12=truth,
+                bounds4=np.array([0, w, 0, h], np.float32), window_size=100, nnratio=0.9, **extra)
+
+
 def make_essential_graph_problem(seed, N=20, fix_scale=False, rot_drift=0.004, trans_drift=0.01, scale_drift=0.01, n_corrected=3, n_covis=3,
                                  loop_edges=0, duplicate_pair=False, extra_fixed=(), consistent=False, n_points=0, skip_frac=0.1, radius=5.0, turn=1.0):
     """A closed trajectory for the essential-graph solve (Optimizer::OptimizeEssentialGraph): N key frames on a circle, key frame 0 the
