@@ -3,6 +3,7 @@ import ctypes as C
 import numpy as np
 import pytest
 from viorb_amd.synth import make_vocabulary, descriptors_near_words
+import kf_matcher_cases as K
 
 pytestmark = pytest.mark.gpu
 
@@ -58,7 +59,10 @@ def _pair(oracle, voc, seed, nK, nF, n_common, noise):
 
 @pytest.mark.parametrize("seed,k,L,nK,nF,ori", [(0, 6, 5, 300, 340, True), (1, 6, 5, 1000, 1000, False), (2, 10, 6, 1000, 970, True),
                                                  (3, 10, 4, 500, 600, True), (4, 10, 6, 2000, 2000, True), (5, 4, 5, 64, 1, True),
-                                                 (6, 8, 5, 8000, 7600, True)])      # more keypoints than the work arrays fit in LDS (k_search_by_bow<true>)
+                                                 (6, 8, 5, 8000, 7600, True),       # more keypoints than the work arrays fit in LDS (k_search_by_bow<true>)
+                                                 (7, 8, 5, 3000, 2900, True),       # the first size whose LDS plan lies between 64 and 160 KB
+                                                 (8, 8, 5, 7112, 7112, True),       # the last size in LDS (bow_search_lds_bytes = 163 832 of 163 840 B) ...
+                                                 (9, 8, 5, 7113, 7113, True)])      # ... and the first one in global scratch
 def test_search_by_bow_bit_exact(oracle, seed, k, L, nK, nF, ori):
     """(k=10, L=4: levelsup 4 puts every feature under the root, the search degenerates to greedy brute force.)"""
     from viorb_amd import SearchByBoW
@@ -69,6 +73,19 @@ def test_search_by_bow_bit_exact(oracle, seed, k, L, nK, nF, ori):
     assert n == n_ref and np.array_equal(m, m_ref)
     if min(nK, nF) >= 300:
         assert n > 0.1 * min(nK, nF)
+
+
+@pytest.mark.parametrize("ori", [False, True])
+@pytest.mark.parametrize("name", sorted(K.BOW_CASES))
+def test_search_by_bow_case(oracle, name, ori):
+    """The hand-built cases (tests/kf_matcher_cases.py): ties, the ratio test at equality, TH_LOW, exclusivity, the map-point flag, a node of
+    70 frame features. tests/test_kf_matcher_cases.py proves on the CPU which rule each decides."""
+    from viorb_amd import SearchByBoW
+    c = K.BOW_CASES[name]()
+    kd, ka, kn, kh, fd, fa, fn = c["args"]
+    n_ref, m_ref = oracle.search_by_bow(kd, ka, kn, kh, fd, fa, fn, c["ratio"], ori)
+    n, m = SearchByBoW(_kps(ka), kd, kn, kh, _kps(fa), fd, fn, c["ratio"], ori)
+    assert n == n_ref and np.array_equal(m, m_ref)
 
 
 def test_search_by_bow_batched_device(oracle):

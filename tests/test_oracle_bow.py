@@ -1,14 +1,10 @@
 """Pins the oracle's DBoW2 transform and SearchByBoW restatements (oracle/bow.cpp) with literal numpy/pure-Python
-re-derivations (the reference has no vectors for them: parity unpinned, see oracle/bow.h)."""
+re-derivations (the reference has no vectors for them: parity unpinned, see oracle/bow.h). The SearchByBoW literal lives in tests/bow_ref.py."""
 import numpy as np
 import pytest
 from viorb_amd.synth import make_vocabulary, descriptors_near_words
-
-POP = np.array([bin(i).count("1") for i in range(256)], np.int32)
-
-
-def ham(a, b):
-    return int(POP[np.bitwise_xor(a, b)].sum())
+from bow_ref import literal_search
+from kf_matcher_ref import ham
 
 
 def descend(voc, d, levelsup):
@@ -46,47 +42,6 @@ def test_transform_matches_literal_descent(oracle, k, L, levelsup):
     assert np.array_equal(r["bow_vals"], np.array([bow[kk] / norm for kk in keys]))
     if L - levelsup <= 0:
         assert (r["node"] == 0).all()
-
-
-def literal_search(kd, ka, kn, kh, fd, fa, fn, ratio, ori):
-    nF = len(fd); match = [-1] * nF; hist = [[] for _ in range(30)]; nm = 0
-    nodes = sorted(set(int(x) for x in kn if x >= 0) & set(int(x) for x in fn if x >= 0))
-    for nd in nodes:
-        for i in np.nonzero(kn == nd)[0]:
-            if not kh[i]:
-                continue
-            b1, b2, bi = 256, 256, -1
-            for j in np.nonzero(fn == nd)[0]:
-                if match[j] >= 0:
-                    continue
-                d = ham(kd[i], fd[j])
-                if d < b1:
-                    b2, b1, bi = b1, d, j
-                elif d < b2:
-                    b2 = d
-            if b1 <= 50 and np.float32(b1) < np.float32(ratio) * np.float32(b2):
-                match[bi] = int(i); nm += 1
-                if ori:
-                    rot = np.float32(ka[i]) - np.float32(fa[bi])
-                    if rot < 0:
-                        rot = np.float32(rot + np.float32(360.0))
-                    v = float(np.float32(rot * np.float32(1.0 / 30)))
-                    b = int(np.floor(v + 0.5))
-                    hist[0 if b == 30 else b].append(bi)
-    if ori:
-        cnt = [len(h) for h in hist]
-        order = sorted(range(30), key=lambda i: (-cnt[i], i))
-        m1, m2, m3 = cnt[order[0]], cnt[order[1]], cnt[order[2]]
-        keep = [order[0]] if m1 > 0 else []
-        if m1 > 0 and m2 > 0 and not (m2 < 0.1 * m1):
-            keep.append(order[1])
-            if m3 > 0 and not (m3 < 0.1 * m1):
-                keep.append(order[2])
-        for b in range(30):
-            if b not in keep:
-                for j in hist[b]:
-                    match[j] = -1; nm -= 1
-    return nm, np.array(match, np.int32)
 
 
 @pytest.mark.parametrize("seed,ori", [(0, True), (1, False), (2, True)])

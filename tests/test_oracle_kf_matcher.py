@@ -1,77 +1,9 @@
 """Pins the oracle's SearchForTriangulation and Fuse restatements (oracle/kf_matcher.cpp) with literal numpy / pure-Python
-re-derivations (no reference vectors exist: parity unpinned, see oracle/kf_matcher.h)."""
+re-derivations (no reference vectors exist: parity unpinned, see oracle/kf_matcher.h). The literals live in tests/kf_matcher_ref.py."""
 import numpy as np
 import pytest
 from viorb_amd.synth import make_two_view_problem, local_points_f32
-
-POP = np.array([bin(i).count("1") for i in range(256)], np.int32)
-f32 = np.float32
-
-
-def ham(a, b):
-    return int(POP[np.bitwise_xor(a, b)].sum())
-
-
-def literal_triangulation(p, only_stereo, ori):
-    k1, k2, F = p["k1"], p["k2"], p["F12"].reshape(3, 3)
-    R2, t2 = p["pose2"][:9].reshape(3, 3), p["pose2"][9:]
-    C2 = np.array([f32(f32(f32(R2[r, 0] * p["Cw1"][0]) + f32(R2[r, 1] * p["Cw1"][1])) + f32(R2[r, 2] * p["Cw1"][2])) for r in range(3)], f32)
-    C2 = (C2.astype(np.float64) + t2.astype(np.float64)).astype(f32)
-    fx, fy, cx, cy = p["intr4"]
-    invz = f32(1.0) / C2[2]
-    ex = f32(f32(f32(fx * C2[0]) * invz) + cx); ey = f32(f32(f32(fy * C2[1]) * invz) + cy)
-    m12 = np.full(len(k1), -1, np.int64); hist = [[] for _ in range(30)]; nm = 0
-    for nd in sorted(set(int(x) for x in p["node1"] if x >= 0) & set(int(x) for x in p["node2"] if x >= 0)):
-        for i1 in np.nonzero(p["node1"] == nd)[0]:
-            if p["hp1"][i1]:
-                continue
-            s1 = p["ur1"][i1] >= 0
-            if only_stereo and not s1:
-                continue
-            x1, y1 = k1["x"][i1], k1["y"][i1]
-            a = f32(f32(f32(x1 * F[0, 0]) + f32(y1 * F[1, 0])) + F[2, 0]); b = f32(f32(f32(x1 * F[0, 1]) + f32(y1 * F[1, 1])) + F[2, 1])
-            c = f32(f32(f32(x1 * F[0, 2]) + f32(y1 * F[1, 2])) + F[2, 2])
-            best, bi = 50, -1
-            for i2 in np.nonzero(p["node2"] == nd)[0]:
-                if p["hp2"][i2]:
-                    continue
-                s2 = p["ur2"][i2] >= 0
-                if only_stereo and not s2:
-                    continue
-                d = ham(p["d1"][i1], p["d2"][i2])
-                if d > 50 or d > best:
-                    continue
-                x2, y2, o2 = k2["x"][i2], k2["y"][i2], k2["octave"][i2]
-                if not s1 and not s2:
-                    dx, dy = f32(ex - x2), f32(ey - y2)
-                    if f32(f32(dx * dx) + f32(dy * dy)) < f32(f32(100) * p["sf"][o2]):
-                        continue
-                num = f32(f32(f32(a * x2) + f32(b * y2)) + c); den = f32(f32(a * a) + f32(b * b))
-                if den == 0:
-                    continue
-                if float(f32(f32(num * num) / den)) < 3.84 * float(p["level_sigma2"][o2]):
-                    bi, best = int(i2), d
-            if bi >= 0:
-                m12[i1] = bi; nm += 1
-                if ori:
-                    rot = f32(k1["angle"][i1] - k2["angle"][bi])
-                    if rot < 0:
-                        rot = f32(rot + f32(360))
-                    bn = int(np.floor(float(f32(rot * f32(1.0 / 30))) + 0.5))
-                    hist[0 if bn == 30 else bn].append(int(i1))
-    if ori:
-        cnt = [len(hh) for hh in hist]; order = sorted(range(30), key=lambda i: (-cnt[i], i))
-        m1, m2, m3 = cnt[order[0]], cnt[order[1]], cnt[order[2]]
-        keep = [order[0]] if m1 > 0 else []
-        if m1 > 0 and m2 > 0 and not (m2 < 0.1 * m1):
-            keep.append(order[1])
-            if m3 > 0 and not (m3 < 0.1 * m1):
-                keep.append(order[2])
-        for bn in range(30):
-            if bn not in keep:
-                for j in hist[bn]:
-                    m12[j] = -1; nm -= 1
-    return nm, m12
+from kf_matcher_ref import literal_triangulation, literal_fuse
 
 
 @pytest.mark.parametrize("seed,stereo,only_stereo,ori", [(0, 0.0, False, True), (1, 0.4, False, False), (2, 0.6, True, True)])
@@ -117,74 +49,6 @@ def test_fuse_finds_the_planted_points(oracle):
     hit = bi[valid == 1] == partner[valid == 1]
     assert n == (bi >= 0).sum() and hit.mean() > 0.6, (n, hit.mean())     # level gate + chi gate reject some; none may land elsewhere
     assert ((bi[valid == 1] == -1) | hit).mean() > 0.97
-
-
-def literal_fuse(p, pts_f, valid, desc, intr5, th):
-    """Pure-Python restatement of ORBmatcher::Fuse (float32 arithmetic spelled out; candidates in KeyFrame::GetFeaturesInArea order)."""
-    k2 = p["k2"]; n = len(k2)
-    R, t = p["pose2"][:9].reshape(3, 3), p["pose2"][9:]
-    fx, fy, cx, cy, bf = [f32(v) for v in intr5]
-    minX, maxX, minY, maxY = f32(0), f32(752), f32(0), f32(480)
-    wInv, hInv = f32(64) / f32(maxX - minX), f32(48) / f32(maxY - minY)
-    # grid (Frame::AssignFeaturesToGrid: round() to cell, insertion order)
-    grid = [[[] for _ in range(48)] for _ in range(64)]
-    for i in range(n):
-        gx = int(np.floor(float(f32(f32(k2["x"][i] - minX) * wInv)) + 0.5)); gy = int(np.floor(float(f32(f32(k2["y"][i] - minY) * hInv)) + 0.5))
-        if 0 <= gx < 64 and 0 <= gy < 48:
-            grid[gx][gy].append(i)
-    Ow = np.array([-f32(f32(f32(R[0, r] * t[0]) + f32(R[1, r] * t[1])) + f32(R[2, r] * t[2])) for r in range(3)], f32)
-    log_sf = f32(np.log(np.float64(p["sf"][1])))
-    out = np.full(len(pts_f), -1, np.int64)
-    for i in range(len(pts_f)):
-        if not valid[i]:
-            continue
-        X = pts_f[i, :3]; nrm = pts_f[i, 3:6]; mind, maxd = pts_f[i, 6], pts_f[i, 7]
-        pc = [f32((np.float64(f32(f32(f32(R[r, 0] * X[0]) + f32(R[r, 1] * X[1])) + f32(R[r, 2] * X[2]))) + np.float64(t[r]))) for r in range(3)]
-        if pc[2] < 0:
-            continue
-        invz = f32(1) / pc[2]
-        u = f32(f32(fx * f32(pc[0] * invz)) + cx); v = f32(f32(fy * f32(pc[1] * invz)) + cy)
-        if not (u >= minX and u < maxX and v >= minY and v < maxY):
-            continue
-        ur = f32(u - f32(bf * invz))
-        PO = (X - Ow).astype(f32)
-        dist = f32(np.sqrt(np.float64(PO[0]) ** 2 + np.float64(PO[1]) ** 2 + np.float64(PO[2]) ** 2))
-        if dist < f32(f32(0.8) * mind) or dist > f32(f32(1.2) * maxd):
-            continue
-        if float(np.float64(PO[0]) * nrm[0] + np.float64(PO[1]) * nrm[1] + np.float64(PO[2]) * nrm[2]) < 0.5 * float(dist):
-            continue
-        lvl = int(np.ceil(f32(f32(np.log(np.float64(f32(maxd / dist)))) / log_sf)))
-        lvl = 0 if lvl < 0 else (7 if lvl >= 8 else lvl)
-        r = f32(f32(th) * p["sf"][lvl])
-        x0 = max(0, int(np.floor(f32(f32(f32(u - minX) - r) * wInv)))); x1 = min(63, int(np.ceil(f32(f32(f32(u - minX) + r) * wInv))))
-        y0 = max(0, int(np.floor(f32(f32(f32(v - minY) - r) * hInv)))); y1 = min(47, int(np.ceil(f32(f32(f32(v - minY) + r) * hInv))))
-        if x0 >= 64 or x1 < 0 or y0 >= 48 or y1 < 0:
-            continue
-        best, bi = 256, -1
-        for ix in range(x0, x1 + 1):
-            for iy in range(y0, y1 + 1):
-                for idx in grid[ix][iy]:
-                    kx, ky, kl = k2["x"][idx], k2["y"][idx], int(k2["octave"][idx])
-                    if not (abs(f32(kx - u)) < r and abs(f32(ky - v)) < r):
-                        continue
-                    if kl < lvl - 1 or kl > lvl:
-                        continue
-                    ex, ey = f32(u - kx), f32(v - ky)
-                    if p["ur2"][idx] >= 0:
-                        er = f32(ur - p["ur2"][idx])
-                        e2 = f32(f32(f32(ex * ex) + f32(ey * ey)) + f32(er * er))
-                        if float(f32(e2 * p["inv_level_sigma2"][kl])) > 7.8:
-                            continue
-                    else:
-                        e2 = f32(f32(ex * ex) + f32(ey * ey))
-                        if float(f32(e2 * p["inv_level_sigma2"][kl])) > 5.99:
-                            continue
-                    d = ham(desc[i], p["d2"][idx])
-                    if d < best:
-                        best, bi = d, idx
-        if best <= 50:
-            out[i] = bi
-    return int((out >= 0).sum()), out
 
 
 @pytest.mark.parametrize("seed,stereo,th", [(11, 0.0, 3.0), (12, 0.5, 6.0)])

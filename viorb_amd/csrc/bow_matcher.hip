@@ -60,7 +60,10 @@ struct BowSearchArgs {
     int cap; float nnratio; int check_ori;
     unsigned char* work; size_t work_bytes;      // k_search_by_bow<true>: the work arrays in global memory (more than ~7100 keypoints)
 };
-__host__ __device__ inline size_t bow_search_lds_bytes(int cap) { return (size_t)cap * (4 + 4 + 4 + 2 + 4 * 2 + 1) + 256; }
+// LDS of one workgroup: the work arrays (dynamic) and the kernel's own __shared__ scalars and histograms (static, BOW_SEARCH_STATIC_LDS).
+// The launch asks for the dynamic part only: a workgroup's limit of 160 KiB counts both.
+#define BOW_SEARCH_STATIC_LDS 256
+__host__ __device__ inline size_t bow_search_lds_bytes(int cap) { return (size_t)cap * (4 + 4 + 4 + 2 + 4 * 2 + 1) + BOW_SEARCH_STATIC_LDS; }
 
 template <bool GW>
 __global__ __launch_bounds__(256) void k_search_by_bow(BowSearchArgs A) {
@@ -74,6 +77,7 @@ __global__ __launch_bounds__(256) void k_search_by_bow(BowSearchArgs A) {
     unsigned short* s_list = s_leader + cap;                           // [4][cap] frame features of the node a wave works on
     unsigned char* s_bin = reinterpret_cast<unsigned char*>(s_list + 4 * cap);     // [cap]
     __shared__ int s_nlead, s_hist[BOW_HISTO], s_keep[BOW_HISTO], s_nm;
+    static_assert((2 * BOW_HISTO + 2) * sizeof(int) <= BOW_SEARCH_STATIC_LDS, "static LDS of k_search_by_bow");
     const int nK = min(A.kf_count[b], cap), nF = min(A.f_count[b], cap);
     const size_t o = (size_t)b * cap;
     for (int i = t; i < cap; i += blockDim.x) { s_knode[i] = i < nK ? A.kf_node[o + i] : -1; s_fnode[i] = i < nF ? A.f_node[o + i] : -1; s_match[i] = -1; s_bin[i] = 0; }
@@ -358,7 +362,8 @@ int viorb_search_by_bow_device(const viorb_keypoint* kf_kps, const uint8_t* kf_d
     VIORB_REQUIRE(cap >= 1 && cap <= 65535 && batch >= 1, "1 <= cap <= 65535");
     const size_t lds = bow_search_lds_bytes(cap);
     const bool gw = lds > 160 * 1024;                                    // more keypoints than the work arrays fit in LDS (~7100): global memory
-    if (!gw && lds > 64 * 1024) VIORB_HIP_TRY(raise_dynamic_lds(reinterpret_cast<const void*>(k_search_by_bow<false>), lds));
+    const size_t dyn = lds - BOW_SEARCH_STATIC_LDS;
+    if (!gw && lds > 64 * 1024) VIORB_HIP_TRY(raise_dynamic_lds(reinterpret_cast<const void*>(k_search_by_bow<false>), dyn));
     BowSearchArgs A;
     A.kf_kps = kf_kps; A.kf_desc = kf_desc; A.kf_node = kf_node; A.kf_has_point = kf_has_point; A.kf_count = kf_count;
     A.f_kps = f_kps; A.f_desc = f_desc; A.f_node = f_node; A.f_count = f_count; A.match = match; A.nmatches = nmatches;
@@ -381,7 +386,7 @@ int viorb_search_by_bow_device(const viorb_keypoint* kf_kps, const uint8_t* kf_d
         A.work = sc.p; A.work_bytes = per;
         hipLaunchKernelGGL(k_search_by_bow<true>, dim3(batch), dim3(256), 0, (hipStream_t)stream, A);
     } else
-    hipLaunchKernelGGL(k_search_by_bow<false>, dim3(batch), dim3(256), lds, (hipStream_t)stream, A);
+    hipLaunchKernelGGL(k_search_by_bow<false>, dim3(batch), dim3(256), dyn, (hipStream_t)stream, A);
     VIORB_HIP_TRY(hipGetLastError());
     return VIORB_OK;
 }
