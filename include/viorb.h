@@ -655,8 +655,9 @@ int viorb_fuse(const viorb_keypoint* kps, const uint8_t* desc, const float* urig
  * The piece of LocalMapping::Run between SearchForTriangulation and Fuse: triangulate and vet the matched pairs, and give every new
  * (or changed) map point its representative descriptor, normal and depth range, in the pts_f[p][8] / pts_desc[p][32] layout that
  * viorb_fuse, viorb_frontend_fuse_device and the local-point search read. The map graph itself (new MapPoint, AddObservation,
- * covisibility, culling) stays with the caller, who passes flat snapshots. One camera per call: every key frame of a map shares
- * fx fy cx cy mb mbf and the scale tables, as the reference's single Tracking object gives them. */
+ * covisibility) stays with the caller, who passes flat snapshots (the decisions of the two culling routines are the library's:
+ * viorb_culling.h). One camera per call: every key frame of a map shares fx fy cx cy mb mbf and the scale tables, as the reference's
+ * single Tracking object gives them. */
 typedef struct viorb_mapping_camera {
     float   fx, fy, cx, cy;               /* KeyFrame::fx.. (invfx = 1.0f / fx as Frame computes it) */
     float   mb, mbf;                      /* KeyFrame::mb, mbf (unused when every uright < 0) */
@@ -937,6 +938,10 @@ int viorb_debug_gba_last_trials(uint8_t* accepted, int cap, int* n);
 /* The essential-graph optimisation of loop closing (Optimizer::OptimizeEssentialGraph): a Sim3 pose graph on the global adjustments'
  * factorisation, in a header of its own. */
 #include "viorb_essential_graph.h"
+
+/* The two culling routines of the mapping thread (LocalMapping::KeyFrameCulling, ordered and exact, and LocalMapping::MapPointCulling),
+ * in a header of their own. */
+#include "viorb_culling.h"
 
 /* ---- Place recognition: BowVector, ORBVocabulary::score and KeyFrameDatabase (reference src/KeyFrameDatabase.cc:40-309) ------------
  * The question relocalisation (src/Tracking.cc:2134) and loop detection (src/LoopClosing.cc:148-165) begin with: which stored key frames

@@ -1,7 +1,7 @@
 """ctypes declarations of include/viorb.h and of the headers it includes, viorb_global_ba_se3.h, viorb_two_view.h and viorb_sim3.h (kept 1:1; tests/test_host_hooks.py checks that every
 declared entry point of viorb.h is exported, has a signature here and that the argument counts agree; tests/test_global_ba_se3_ref.py
 does the same for SIGNATURES_GLOBAL_BA_SE3, tests/test_two_view_ref.py for SIGNATURES_TWO_VIEW, tests/test_sim3_ref.py for SIGNATURES_SIM3,
-tests/test_sim3_match_ref.py for SIGNATURES_SIM3_MATCH)."""
+tests/test_sim3_match_ref.py for SIGNATURES_SIM3_MATCH, tests/test_kf_culling_ref.py for SIGNATURES_CULLING)."""
 import ctypes as C
 import os
 import numpy as np
@@ -133,6 +133,23 @@ SEARCH_INIT_OUTPUT_FIELDS = ("matches21", "matched_distance", "rot_hist", "reaso
 class SearchInitOutputs(C.Structure):
     """viorb_search_init_outputs (include/viorb_search_init.h)."""
     _fields_ = [(n, C.c_void_p) for n in SEARCH_INIT_OUTPUT_FIELDS]
+
+
+CULL_MAP_INTS = ("batch", "n_kf", "n_cand", "n_kp", "n_pt", "n_obs")
+CULL_MAP_ARRAYS = ("kf_start", "kf_flags", "kf_time", "kf_prev", "kf_next", "cur_kf", "vins_inited", "th_depth", "cand_start", "cand_kf", "kp_start",
+                   "kp_point", "kp_octave", "kp_depth", "pt_start", "pt_nobs", "pt_bad", "obs_start", "obs")
+CULL_RESULT_FIELDS = ("cand_reason", "cand_redundant", "cand_mps", "cand_recounted", "culled_order", "n_culled", "status", "kf_bad", "kf_to_be_erased",
+                      "kf_prev_out", "kf_next_out", "kf_repreint", "pt_nobs_out", "pt_bad_out", "obs_alive")
+
+
+class CullMap(C.Structure):
+    """viorb_cull_map (include/viorb_culling.h)."""
+    _fields_ = [(n, C.c_int32) for n in CULL_MAP_INTS] + [(n, C.c_void_p) for n in CULL_MAP_ARRAYS]
+
+
+class CullResult(C.Structure):
+    """viorb_cull_result (include/viorb_culling.h)."""
+    _fields_ = [(n, C.c_void_p) for n in CULL_RESULT_FIELDS]
 
 
 class TrackerConfig(C.Structure):
@@ -399,6 +416,18 @@ SIGNATURES_ESSENTIAL_GRAPH = {
     "viorb_debug_essential_graph_edge": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
 }
 
+# mirrors include/viorb_culling.h (key-frame and map-point culling); tests/test_kf_culling_ref.py checks names and argument counts against it
+SIGNATURES_CULLING = {
+    "viorb_key_frame_culling_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "viorb_key_frame_culling_device": (i32, [PP(CullMap), i32, PP(CullResult), vp, sz, vp]),
+    "viorb_key_frame_culling": (i32, [PP(CullMap), i32, PP(CullResult)]),
+    "viorb_key_frame_culling_shape": (i32, [vp]),
+    "viorb_map_point_culling_device": (i32, [vp] * 7 + [i32, i32, i32, vp, vp]),
+    "viorb_map_point_culling": (i32, [vp] * 5 + [i32, i32, i32, vp]),
+    "viorb_debug_key_frame_culling_host": (i32, [PP(CullMap), i32, PP(CullResult)]),
+    "viorb_debug_map_point_code": (i32, [i32] * 7),
+}
+
 _lib = None
 
 
@@ -420,7 +449,7 @@ def lib():
         L = C.CDLL(SO_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GLOBAL_BA_SE3.items()) + list(SIGNATURES_TWO_VIEW.items()) \
                 + list(SIGNATURES_SIM3.items()) + list(SIGNATURES_SIM3_MATCH.items()) + list(SIGNATURES_ESSENTIAL_GRAPH.items()) \
-                + list(SIGNATURES_SEARCH_INIT.items()):
+                + list(SIGNATURES_SEARCH_INIT.items()) + list(SIGNATURES_CULLING.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -8,6 +8,9 @@
 //   update_map_points       MapPoint::ComputeDistinctiveDescriptors + MapPoint::UpdateNormalAndDepth for a list of points
 //                                                                                                       src/MapPoint.cc:249-314, 337-378
 //   compute_scene_median_depth   KeyFrame::ComputeSceneMedianDepth(q)                                         src/KeyFrame.cc:970-1000
+//   key_frame_culling       LocalMapping::KeyFrameCulling: the candidate loop, then the reference's own SetBadFlag on what it culls
+//                                                                                                       src/LocalMapping.cc:1665-1824
+//   map_point_culling       LocalMapping::MapPointCulling over mlpRecentAddedMapPoints                  src/LocalMapping.cc:1198-1233
 //   try_init_vio            LocalMapping::TryInitVIO steps 1-3: gyro bias, scale, gravity, accelerometer bias  src/LocalMapping.cc:279-504
 //   try_init_vio_apply      the NavState / pose / map-point write-back once bVIOInited                         src/LocalMapping.cc:585-786
 //
@@ -16,6 +19,11 @@
 // on MapPoint for update_map_points (mDescriptor, mNormalVector, mfMinDistance and mfMaxDistance are protected):
 //   void SetDescriptorNormalAndDepth(const cv::Mat& desc, const cv::Mat& normal, float minDist, float maxDist)
 // storing the four members under mMutexFeatures / mMutexPos — a five-line addition to include/MapPoint.h.
+// The culling templates read GetVectorCovisibleKeyFrames, GetMapPointMatches, GetPrevKeyFrame, GetNextKeyFrame, mnId, mTimeStamp, mThDepth,
+// mvKeysUn, mvuRight, mvDepth, SetBadFlag of KeyFrame and Observations, GetObservations, isBad, GetFound, mnFirstKFid, SetBadFlag of
+// MapPoint, and need two one-line accessors for protected members:
+//   bool KeyFrame::GetNotErase()   returning mbNotErase under mMutexConnections   (include/KeyFrame.h)
+//   int  MapPoint::GetVisible()    returning mnVisible under mMutexFeatures       (include/MapPoint.h, beside GetFound)
 #ifndef VIORB_LOCALMAPPING_SHIM_H
 #define VIORB_LOCALMAPPING_SHIM_H
 
@@ -166,6 +174,125 @@ inline void update_map_points(const std::vector<MapPointT*>& vpMPs) {
         for (int c = 0; c < 3; c++) nrm.at<float>(c) = pf[(size_t)p * 8 + 3 + c];
         pts[p]->SetDescriptorNormalAndDepth(d, nrm, pf[(size_t)p * 8 + 6], pf[(size_t)p * 8 + 7]);
     }
+}
+
+// ---- LocalMapping::KeyFrameCulling / MapPointCulling (include/viorb_culling.h) -----------------------------------------------------------------
+// What key_frame_culling saw and decided, for logging and for tests: the snapshot's key frames and points in slot order, the reason of
+// every candidate (VIORB_KFC_*) and the state the library's loop leaves, which is what the SetBadFlag calls then produce in the map.
+template <class KeyFrameT, class MapPointT> struct CullingReport {
+    std::vector<KeyFrameT*> kfs, candidates, culled;               // culled: in cull order (the AppendIMUDataToFront order of their next)
+    std::vector<MapPointT*> pts;
+    std::vector<int32_t> reason, redundant, mps, kf_prev_out, kf_next_out, pt_nobs_out;
+    std::vector<uint8_t> kf_repreint, pt_bad_out;
+};
+
+// The body of LocalMapping::KeyFrameCulling between the two SetFlagCopyInitKFs calls becomes
+//   viorb_shim::key_frame_culling<KeyFrame, MapPoint>(mpCurrentKeyFrame, mbMonocular, GetVINSInited());
+// The snapshot holds mpCurrentKeyFrame, the candidates (GetVectorCovisibleKeyFrames, in that order), their prev and next, and every key
+// frame that observes a point of a candidate; a link that leaves the snapshot is passed as -1 (only candidates' links are followed, and
+// those are inside). The ordered loop runs in the library; pKF->SetBadFlag() is then called on the _CULLED and _DEFERRED candidates in
+// the loop's order, so the spanning tree, the connections, the IMU append of `next` and the database erase stay the reference's.
+// Returns the number of culled key frames; a failure throws.
+template <class KeyFrameT, class MapPointT>
+inline int key_frame_culling(KeyFrameT* pCur, bool bMonocular, bool bVINSInited, CullingReport<KeyFrameT, MapPointT>* report = 0) {
+    const std::vector<KeyFrameT*> cands = pCur->GetVectorCovisibleKeyFrames();
+    std::map<KeyFrameT*, int> kf_slot; std::vector<KeyFrameT*> kfs;
+    std::map<MapPointT*, int> pt_slot; std::vector<MapPointT*> pts;
+    struct Add { static int kf(std::map<KeyFrameT*, int>& m, std::vector<KeyFrameT*>& v, KeyFrameT* k) {
+        typename std::map<KeyFrameT*, int>::iterator it = m.find(k);
+        if (it != m.end()) return it->second;
+        m[k] = (int)v.size(); v.push_back(k); return (int)v.size() - 1; } };
+    Add::kf(kf_slot, kfs, pCur);
+    std::vector<int32_t> cand_kf, kp_start(1, 0), kp_point, pt_nobs, obs_start(1, 0); std::vector<uint8_t> kp_octave, pt_bad; std::vector<float> kp_depth; std::vector<uint32_t> obs;
+    for (size_t j = 0; j < cands.size(); j++) {
+        KeyFrameT* pKF = cands[j];
+        cand_kf.push_back(Add::kf(kf_slot, kfs, pKF));
+        if (pKF->GetPrevKeyFrame()) Add::kf(kf_slot, kfs, pKF->GetPrevKeyFrame());
+        if (pKF->GetNextKeyFrame()) Add::kf(kf_slot, kfs, pKF->GetNextKeyFrame());
+        const std::vector<MapPointT*> vpMapPoints = pKF->GetMapPointMatches();
+        for (size_t i = 0; i < vpMapPoints.size(); i++) {
+            MapPointT* pMP = vpMapPoints[i];
+            int p = -1;
+            if (pMP) {
+                typename std::map<MapPointT*, int>::iterator it = pt_slot.find(pMP);
+                if (it != pt_slot.end()) p = it->second;
+                else {
+                    p = (int)pts.size(); pt_slot[pMP] = p; pts.push_back(pMP);
+                    pt_nobs.push_back(pMP->Observations()); pt_bad.push_back(pMP->isBad() ? 1 : 0);
+                    const std::map<KeyFrameT*, size_t> observations = pMP->GetObservations();
+                    for (typename std::map<KeyFrameT*, size_t>::const_iterator mit = observations.begin(); mit != observations.end(); ++mit) {
+                        const int slot = Add::kf(kf_slot, kfs, mit->first);
+                        if (slot >= 65535) throw std::runtime_error("KeyFrameCulling: more than 65535 key frames in the snapshot");
+                        obs.push_back((uint32_t)slot | ((uint32_t)(mit->first->mvKeysUn[mit->second].octave & 0xff) << 16) | (mit->first->mvuRight[mit->second] >= 0 ? 1u << 24 : 0u));
+                    }
+                    obs_start.push_back((int32_t)obs.size());
+                }
+            }
+            kp_point.push_back(p); kp_octave.push_back((uint8_t)pKF->mvKeysUn[i].octave); kp_depth.push_back(bMonocular ? 0.f : pKF->mvDepth[i]);
+        }
+        kp_start.push_back((int32_t)kp_point.size());
+    }
+    const size_t nk = kfs.size(), nc = cands.size(), np = pts.size();
+    std::vector<uint8_t> kf_flags(nk); std::vector<double> kf_time(nk); std::vector<int32_t> kf_prev(nk, -1), kf_next(nk, -1);
+    for (size_t k = 0; k < nk; k++) {
+        kf_flags[k] = (uint8_t)((kfs[k]->mnId == 0 ? VIORB_CULL_KF_FIRST : 0) | (kfs[k]->GetNotErase() ? VIORB_CULL_KF_NOT_ERASE : 0));
+        kf_time[k] = kfs[k]->mTimeStamp;
+        typename std::map<KeyFrameT*, int>::iterator it = kf_slot.find(kfs[k]->GetPrevKeyFrame());
+        if (kfs[k]->GetPrevKeyFrame() && it != kf_slot.end()) kf_prev[k] = it->second;
+        it = kf_slot.find(kfs[k]->GetNextKeyFrame());
+        if (kfs[k]->GetNextKeyFrame() && it != kf_slot.end()) kf_next[k] = it->second;
+    }
+    // every array at least one element long: the library refuses a null pointer whatever the count
+    cand_kf.resize(std::max<size_t>(nc, 1)); kp_point.resize(std::max<size_t>(kp_point.size(), 1), -1); kp_octave.resize(kp_point.size()); kp_depth.resize(kp_point.size());
+    pt_nobs.resize(std::max<size_t>(np, 1)); pt_bad.resize(pt_nobs.size()); obs.resize(std::max<size_t>(obs.size(), 1));
+    const int32_t kf_start[2] = {0, (int32_t)nk}, cand_start[2] = {0, (int32_t)nc}, pt_start[2] = {0, (int32_t)np}, cur_kf = 0;
+    const uint8_t vins = bVINSInited ? 1 : 0; const float th = pCur->mThDepth;
+    viorb_cull_map m;
+    m.batch = 1; m.n_kf = (int32_t)nk; m.n_cand = (int32_t)nc; m.n_kp = kp_start.back(); m.n_pt = (int32_t)np; m.n_obs = obs_start.back();
+    m.kf_start = kf_start; m.kf_flags = &kf_flags[0]; m.kf_time = &kf_time[0]; m.kf_prev = &kf_prev[0]; m.kf_next = &kf_next[0];
+    m.cur_kf = &cur_kf; m.vins_inited = &vins; m.th_depth = &th;
+    m.cand_start = cand_start; m.cand_kf = &cand_kf[0]; m.kp_start = &kp_start[0]; m.kp_point = &kp_point[0]; m.kp_octave = &kp_octave[0]; m.kp_depth = &kp_depth[0];
+    m.pt_start = pt_start; m.pt_nobs = &pt_nobs[0]; m.pt_bad = &pt_bad[0]; m.obs_start = &obs_start[0]; m.obs = &obs[0];
+    CullingReport<KeyFrameT, MapPointT> local;
+    CullingReport<KeyFrameT, MapPointT>& R = report ? *report : local;
+    R.kfs = kfs; R.candidates = cands; R.pts = pts; R.culled.clear();
+    R.reason.assign(std::max<size_t>(nc, 1), 0); R.redundant = R.mps = R.reason; R.kf_prev_out.assign(nk, 0); R.kf_next_out = R.kf_prev_out; R.kf_repreint.assign(nk, 0);
+    R.pt_nobs_out.assign(std::max<size_t>(np, 1), 0); R.pt_bad_out.assign(std::max<size_t>(np, 1), 0);
+    std::vector<int32_t> order(std::max<size_t>(nc, 1), -1);
+    int32_t n_culled = 0, status = 0;
+    viorb_cull_result r;
+    std::memset(&r, 0, sizeof(r));
+    r.cand_reason = &R.reason[0]; r.cand_redundant = &R.redundant[0]; r.cand_mps = &R.mps[0]; r.culled_order = &order[0]; r.n_culled = &n_culled; r.status = &status;
+    r.kf_prev_out = &R.kf_prev_out[0]; r.kf_next_out = &R.kf_next_out[0]; r.kf_repreint = &R.kf_repreint[0]; r.pt_nobs_out = &R.pt_nobs_out[0]; r.pt_bad_out = &R.pt_bad_out[0];
+    check(viorb_key_frame_culling(&m, bMonocular ? 1 : 0, &r), "KeyFrameCulling");
+    if (status != VIORB_OK) throw std::runtime_error("KeyFrameCulling: the library refused the snapshot");
+    R.reason.resize(nc); R.redundant.resize(nc); R.mps.resize(nc); R.pt_nobs_out.resize(np); R.pt_bad_out.resize(np);
+    for (int32_t k = 0; k < n_culled; k++) R.culled.push_back(cands[order[k]]);
+    for (size_t j = 0; j < nc; j++)
+        if (R.reason[j] == VIORB_KFC_CULLED || R.reason[j] == VIORB_KFC_DEFERRED) cands[j]->SetBadFlag();
+    return n_culled;
+}
+
+// The loop of LocalMapping::MapPointCulling becomes
+//   viorb_shim::map_point_culling(mlpRecentAddedMapPoints, mpCurrentKeyFrame->mnId, mbMonocular);
+// The branch of every point is decided in the library; SetBadFlag and the list erase are applied here as :1214-1231 do. ListT =
+// std::list<MapPoint*>. Returns the number of points set bad.
+template <class ListT>
+inline int map_point_culling(ListT& mlpRecentAddedMapPoints, unsigned long nCurrentKFid, bool bMonocular) {
+    const size_t n = mlpRecentAddedMapPoints.size();
+    if (n == 0) return 0;
+    std::vector<uint8_t> bad; std::vector<int32_t> found, visible, first, nobs, code(n, 0);
+    for (typename ListT::iterator lit = mlpRecentAddedMapPoints.begin(); lit != mlpRecentAddedMapPoints.end(); ++lit) {
+        bad.push_back((*lit)->isBad() ? 1 : 0); found.push_back((*lit)->GetFound()); visible.push_back((*lit)->GetVisible());
+        first.push_back((int32_t)(*lit)->mnFirstKFid); nobs.push_back((*lit)->Observations());
+    }
+    check(viorb_map_point_culling(&bad[0], &found[0], &visible[0], &first[0], &nobs[0], (int)n, (int)nCurrentKFid, bMonocular ? 1 : 0, &code[0]), "MapPointCulling");
+    int n_bad = 0; size_t i = 0;
+    for (typename ListT::iterator lit = mlpRecentAddedMapPoints.begin(); lit != mlpRecentAddedMapPoints.end(); i++) {
+        if (code[i] == VIORB_MPC_CULL_FOUND_RATIO || code[i] == VIORB_MPC_CULL_FEW_OBS) { (*lit)->SetBadFlag(); n_bad++; }
+        if (code[i] == VIORB_MPC_KEEP) ++lit; else lit = mlpRecentAddedMapPoints.erase(lit);
+    }
+    return n_bad;
 }
 
 // ---- LocalMapping::TryInitVIO -------------------------------------------------------------------------------------------------

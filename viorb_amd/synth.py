@@ -1444,3 +1444,65 @@ def make_essential_graph_problem(seed, N=20, fix_scale=False, rot_drift=0.004, t
 def _quat_to_R(q):
     from scipy.spatial.transform import Rotation
     return Rotation.from_quat(q).as_matrix()
+
+
+def make_culling_problem(seed, n_kf=None, n_cand=None, max_kps=300, min_kps=0, n_pts=None, obs_range=None, stereo=0.3, not_erase=0.1, gap=0.1, same_octave=None, stray=0.02):
+    """One stream's snapshot for key-frame culling (the scene dict of viorb_amd/culling.py): a chain of n_kf key frames in time order with the
+    current one last, n_pts points each observed by obs_range = (lo, hi) key frames near one another (octaves 0-7 around the point's own,
+    a share `stereo` of stereo observations), n_cand candidates in random order whose keypoint tables hold their observations cut to at
+    min_kps..max_kps entries, with empty entries, a few entries whose point does not observe the candidate, a few points listed twice and
+    depths on both sides of th_depth. `gap`: the share of long intervals (time-gap skips); `not_erase`: the share of mbNotErase;
+    `stray`: the share of table entries without an observation (they occur after MapPoint::Replace)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    nk = int(n_kf or rng.integers(5, 41))
+    nc = min(int(n_cand or rng.integers(1, 31)), nk - 1)
+    npt = int(n_pts or rng.integers(50, 601))
+    lo, hi = obs_range or [(1, 12), (4, 6), (5, 12), (4, 5)][int(rng.integers(0, 4))]
+    same = float(rng.choice([0.5, 0.9, 1.0])) if same_octave is None else same_octave
+    dt = np.where(rng.random(nk) < gap, rng.uniform(0.3, 0.6, nk), rng.uniform(0.03, 0.15, nk))
+    t = 100.0 + np.cumsum(dt)
+    s = dict(cur=nk - 1, vins_inited=bool(rng.random() < 0.4), th_depth=40.0)
+    flags = np.where(rng.random(nk) < not_erase, 2, 0).astype(np.uint8)
+    if rng.random() < 0.5:
+        flags[0] |= 1
+    s["kf_flags"], s["kf_time"] = flags, t
+    s["kf_prev"], s["kf_next"] = np.arange(-1, nk - 1, dtype=np.int32), np.concatenate([np.arange(1, nk), [-1]]).astype(np.int32)
+    per_kf = [[] for _ in range(nk)]                       # (point, octave) of every observation of a key frame
+    obs_start, obs, nobs = [0], [], []
+    for p in range(npt):
+        k = min(int(rng.integers(lo, hi + 1)), nk)
+        c = int(rng.integers(0, nk))
+        w0 = min(max(c - k, 0), max(nk - 2 * k, 0))
+        slots = np.sort(rng.choice(np.arange(w0, min(w0 + 2 * k, nk)), size=k, replace=False))
+        base = int(rng.integers(0, 8))
+        n = 0
+        for sl in slots:
+            o = base if rng.random() < same else int(np.clip(base + rng.integers(-2, 3), 0, 7))
+            st = bool(rng.random() < stereo)
+            obs.append((int(sl) & 0xffff) | (o << 16) | ((1 << 24) if st else 0))
+            per_kf[int(sl)].append((p, o))
+            n += 2 if st else 1
+        obs_start.append(len(obs)); nobs.append(n)
+    s["pt_nobs"], s["pt_bad"] = np.array(nobs, np.int32), (rng.random(npt) < 0.02).astype(np.uint8)
+    s["obs_start"], s["obs"] = np.array(obs_start, np.int32), np.array(obs, np.uint32)
+    cand = rng.permutation(nk - 1)[:nc]
+    kp_start, point, octave = [0], [], []
+    for c in cand:
+        rows = [per_kf[int(c)][i] for i in rng.permutation(len(per_kf[int(c)]))][:int(rng.integers(min_kps, max_kps + 1))]
+        for (p, o) in rows:
+            r = rng.random()
+            if r < 0.15 and len(point) - kp_start[-1] < max_kps - 1:
+                point.append(-1); octave.append(int(rng.integers(0, 8)))
+            elif r < 0.15 + stray and len(point) - kp_start[-1] < max_kps - 1:       # a table entry whose point has no observation of this key frame
+                point.append(int(rng.integers(0, npt))); octave.append(int(rng.integers(0, 8)))
+            elif r < 0.16 + stray and len(point) - kp_start[-1] < max_kps - 1:       # the point at two keypoints
+                point.append(p); octave.append(int(np.clip(o + 1, 0, 7)))
+            point.append(p); octave.append(o)
+        del point[kp_start[-1] + max_kps:], octave[kp_start[-1] + max_kps:]
+        kp_start.append(len(point))
+    n = len(point)
+    depth = np.where(rng.random(n) < 0.05, rng.uniform(40, 80, n), rng.uniform(0.5, 40, n))
+    depth[rng.random(n) < 0.02] = -1.0
+    s["cand_kf"], s["kp_start"] = cand.astype(np.int32), np.array(kp_start, np.int32)
+    s["kp_point"], s["kp_octave"], s["kp_depth"] = np.array(point, np.int32), np.array(octave, np.uint8), depth.astype(np.float32)
+    return s
