@@ -1,6 +1,7 @@
 // tests/cpp/search_init_core_host_test.cpp — the host build of viorb_amd/csrc/search_init_core.h on a few fixed cases, as a stand-alone
 // program that tests/test_search_init_host_sanitized.py compiles with -fsanitize=address,undefined and runs as a child process. It
-// prints one checksum line; the test requires a clean exit. No GPU, no library: only the header.
+// prints one checksum line; the test requires a clean exit. No GPU, no library: only the header. What the header takes from match_core.h
+// (window, rotation bin, three maxima) is exercised by tests/cpp/match_core_host_test.cpp.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -62,23 +63,8 @@ int main() {
         if (run_lists(down, one, n, 1, 1, 0.9f) > n + 1) fail("descending staircase");
         if (run_lists(up, two, n, 2, n + 1, 0.9f) != n + 1) fail("ascending staircase takes one sweep per link");
     }
-    // windows at and beyond the borders, conversions no int holds
+    // pruning rule, depth and the select (the windows, the bins and the three maxima: match_core_host_test.cpp)
     {
-        SiCam C = {0.f, 752.f, 0.f, 480.f, 64.f / 752.f, 48.f / 480.f};
-        const float xs[] = {0.f, 751.9f, -100.f, -100.5f, 852.f, 1e12f, -1e12f, 3e38f, -3e38f, 376.f};
-        for (float x : xs) for (float y : xs) for (float r : {100.f, 10.f}) {
-            SiRect R; si_window(C, x, y, r, R);
-            if (!R.empty && (R.x0 < 0 || R.x1 >= SI_GRID_COLS || R.y0 < 0 || R.y1 >= SI_GRID_ROWS || R.x0 > R.x1 + 1 || R.y0 > R.y1 + 1)) fail("cell rectangle out of the grid");
-            sum += R.empty ? 1 : (R.x1 - R.x0) * (R.y1 - R.y0);
-        }
-    }
-    // bins, maxima, pruning rule, depth and the select
-    {
-        int hist[SI_HISTO] = {0}, keep[SI_HISTO];
-        for (int i = 0; i < 5000; i++) { const int b = si_rot_bin((float)(rnd() % 36000) / 100.f, (float)(rnd() % 36000) / 100.f); if (b < 0 || b > 12) fail("bin"); hist[b]++; }
-        hist[si_rot_bin(NAN, 0.f)]++; hist[si_rot_bin(1e30f, 0.f)]++; hist[si_rot_bin(-1e30f, 0.f)]++;
-        si_three_maxima(hist, keep);
-        for (int i = 0; i < SI_HISTO; i++) sum += keep[i] * (i + 1);
         for (int d = 0; d <= 256; d++) sum += si_keep(d, 0.9f) + 2 * si_keep(d, 1e-9f) + 4 * si_keep(d, 1e9f);
         const int n = 1000;
         std::vector<float> z(n);

@@ -1,0 +1,20 @@
+"""match_core.h compiled for the host with the address and undefined-behaviour sanitizers, as a stand-alone program
+(tests/cpp/match_core_host_test.cpp) run as a child process: the grid window against Frame::GetFeaturesInArea on windows at and beyond
+every border and on values no int holds, the window walk against the literal cell loop and on corrupted grids, the descriptor distance
+against a bit loop, the rotation bin against its unclamped form and the three maxima against ComputeThreeMaxima. A clean exit is
+required. The sanitizer runtimes are linked statically into the program; nothing sanitised is loaded into this process."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_match_core_host_program_runs_clean_under_asan_and_ubsan(tmp_path):
+    exe = str(tmp_path / "match_core_host_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wno-unknown-pragmas", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-static-libasan", "-static-libubsan",
+                           "-I", os.path.join(ROOT, "viorb_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "match_core_host_test.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    print(r.stdout, r.stderr)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.startswith("checksum ") and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr

@@ -1,7 +1,7 @@
 """search_init_core.h compiled for the host with the address and undefined-behaviour sanitizers, as a stand-alone program
 (tests/cpp/search_init_core_host_test.cpp) run as a child process: the sweeps of the ordered phase against the literal loop on random
-candidate lists and both staircases, windows at and beyond the image borders, the bins, the three maxima and the radix select of the
-scene depth. A clean exit is required. The sanitizer runtimes are linked statically into the program; nothing sanitised is loaded into
+candidate lists and both staircases, the pruning rule and the radix select of the scene depth (the windows, the bins and the three maxima
+moved to tests/test_match_core_host_sanitized.py with their code). A clean exit is required. The sanitizer runtimes are linked statically into the program; nothing sanitised is loaded into
 this process."""
 import os
 import subprocess

@@ -11,12 +11,9 @@
 #include <vector>
 #include <algorithm>
 #include "viorb_common.h"
-#include "orb_math.h"
+#include "match_core.h"
 
 namespace viorb {
-
-#define BOW_HISTO 30
-#define BOW_TH_LOW 50
 
 struct BowVoc { const int* child_start; const int* child_ids; const uint8_t* desc; const int* word_id; const double* weight; int n_nodes, L; };
 
@@ -26,10 +23,8 @@ __global__ __launch_bounds__(256) void k_bow_transform(BowVoc V, const uint8_t* 
     const int b = g / cap, i = g - b * cap;
     const bool live = b < batch && i < count[b];
     // (all 16 lanes of a group take the same path; dead groups still run the shuffles below with harmless values)
-    uint32_t f[8];
     const uint4* fp = reinterpret_cast<const uint4*>(desc + (size_t)32 * (live ? g : 0));
     const uint4 f0 = fp[0], f1 = fp[1];
-    f[0] = f0.x; f[1] = f0.y; f[2] = f0.z; f[3] = f0.w; f[4] = f1.x; f[5] = f1.y; f[6] = f1.z; f[7] = f1.w;
     const int nid_level = V.L - levelsup;
     int cur = 0, nid = 0;
     for (int lvl = 1; lvl <= 64; lvl++) {                     // a well-formed tree ends at lvl == L; 64 bounds a malformed one
@@ -38,10 +33,7 @@ __global__ __launch_bounds__(256) void k_bow_transform(BowVoc V, const uint8_t* 
         uint32_t best = 0xFFFFFFFFu;                           // (distance << 20) | position: min = first minimum, as 'd < best_d'
         for (int p = c0 + sub; p < c1; p += 16) {
             const int id = V.child_ids[p];
-            const uint4* cp = reinterpret_cast<const uint4*>(V.desc + (size_t)32 * id);
-            const uint4 a = cp[0], c = cp[1];
-            const int d = __popc(f[0] ^ a.x) + __popc(f[1] ^ a.y) + __popc(f[2] ^ a.z) + __popc(f[3] ^ a.w) +
-                          __popc(f[4] ^ c.x) + __popc(f[5] ^ c.y) + __popc(f[6] ^ c.z) + __popc(f[7] ^ c.w);
+            const int d = desc_distance(f0, f1, V.desc + (size_t)32 * id);
             const uint32_t key = ((uint32_t)d << 20) | (uint32_t)(p - c0);
             best = key < best ? key : best;
         }
@@ -76,12 +68,12 @@ __global__ __launch_bounds__(256) void k_search_by_bow(BowSearchArgs A) {
     unsigned short* s_leader = reinterpret_cast<unsigned short*>(s_match + cap);   // [cap] first key-frame feature of each node
     unsigned short* s_list = s_leader + cap;                           // [4][cap] frame features of the node a wave works on
     unsigned char* s_bin = reinterpret_cast<unsigned char*>(s_list + 4 * cap);     // [cap]
-    __shared__ int s_nlead, s_hist[BOW_HISTO], s_keep[BOW_HISTO], s_nm;
-    static_assert((2 * BOW_HISTO + 2) * sizeof(int) <= BOW_SEARCH_STATIC_LDS, "static LDS of k_search_by_bow");
+    __shared__ int s_nlead, s_hist[HISTO_LENGTH], s_keep[HISTO_LENGTH], s_nm;
+    static_assert((2 * HISTO_LENGTH + 2) * sizeof(int) <= BOW_SEARCH_STATIC_LDS, "static LDS of k_search_by_bow");
     const int nK = min(A.kf_count[b], cap), nF = min(A.f_count[b], cap);
     const size_t o = (size_t)b * cap;
     for (int i = t; i < cap; i += blockDim.x) { s_knode[i] = i < nK ? A.kf_node[o + i] : -1; s_fnode[i] = i < nF ? A.f_node[o + i] : -1; s_match[i] = -1; s_bin[i] = 0; }
-    if (t < BOW_HISTO) { s_hist[t] = 0; s_keep[t] = 1; }
+    if (t < HISTO_LENGTH) { s_hist[t] = 0; s_keep[t] = 1; }
     if (t == 0) { s_nlead = 0; s_nm = 0; }
     __syncthreads();
     for (int i = t; i < nK; i += blockDim.x) {
@@ -93,7 +85,6 @@ __global__ __launch_bounds__(256) void k_search_by_bow(BowSearchArgs A) {
     __syncthreads();
     const int nlead = s_nlead;
     unsigned short* list = s_list + (size_t)wv * cap;
-    const float factor = 1.0f / BOW_HISTO;
     for (int g = wv; g < nlead; g += 4) {
         const int i0 = s_leader[g], nd = s_knode[i0];
         // frame features of this node, ascending (the order of FeatureVector's index vector)
@@ -122,8 +113,7 @@ __global__ __launch_bounds__(256) void k_search_by_bow(BowSearchArgs A) {
                     if (s_match[idx] >= 0) continue;
                     const uint4* fp = reinterpret_cast<const uint4*>(A.f_desc + (o + idx) * 32);
                     const uint4 a = fp[0], e = fp[1];
-                    const int d = __popc(k0.x ^ a.x) + __popc(k0.y ^ a.y) + __popc(k0.z ^ a.z) + __popc(k0.w ^ a.w) +
-                                  __popc(k1.x ^ e.x) + __popc(k1.y ^ e.y) + __popc(k1.z ^ e.z) + __popc(k1.w ^ e.w);
+                    const int d = desc_distance(k0, k1, a, e);
                     const uint32_t key = ((uint32_t)d << 16) | (uint32_t)c;
                     if (key < best) { d2 = (int)(best >> 16); best = key; } else if (d < d2) d2 = d;
                 }
@@ -134,15 +124,11 @@ __global__ __launch_bounds__(256) void k_search_by_bow(BowSearchArgs A) {
                     best = lo; d2 = min(min(d2, od2), (int)(hi >> 16));
                 }
                 const int b1 = (int)(best >> 16);
-                if (b1 <= BOW_TH_LOW && (float)b1 < A.nnratio * (float)d2) {
+                if (b1 <= TH_LOW && (float)b1 < A.nnratio * (float)d2) {
                     const int idx = list[best & 0xFFFFu];
                     if (lane == 0) {
                         s_match[idx] = k;
-                        float rot = A.kf_kps[o + k].angle - A.f_kps[o + idx].angle;
-                        if (rot < 0.0f) rot += 360.0f;
-                        int bin = (int)roundf(rot * factor);
-                        if (bin == BOW_HISTO) bin = 0;
-                        s_bin[idx] = (unsigned char)bin;
+                        s_bin[idx] = (unsigned char)rot_bin(A.kf_kps[o + k].angle, A.f_kps[o + idx].angle);
                     }
                     __threadfence_block();
                     __builtin_amdgcn_wave_barrier();
@@ -155,20 +141,7 @@ __global__ __launch_bounds__(256) void k_search_by_bow(BowSearchArgs A) {
     for (int j = t; j < nF; j += blockDim.x) if (s_match[j] >= 0) { mine++; if (A.check_ori) atomicAdd(&s_hist[s_bin[j]], 1); }
     if (mine) atomicAdd(&s_nm, mine);
     __syncthreads();
-    if (A.check_ori && t == 0) {                                       // ComputeThreeMaxima, src/ORBmatcher.cc:1602-1643
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int i = 0; i < BOW_HISTO; i++) {
-            const int sz = s_hist[i];
-            if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
-            else if (sz > max3) { max3 = sz; ind3 = i; }
-        }
-        if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-        else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-        int removed = 0;
-        for (int i = 0; i < BOW_HISTO; i++) { const int keep = (i == ind1 || i == ind2 || i == ind3); s_keep[i] = keep; if (!keep) removed += s_hist[i]; }
-        s_nm -= removed;
-    }
+    if (A.check_ori && t == 0) s_nm -= three_maxima(s_hist, s_keep);
     __syncthreads();
     for (int j = t; j < cap; j += blockDim.x) {
         const int m = j < nF ? s_match[j] : -1;
@@ -198,13 +171,13 @@ __global__ __launch_bounds__(1024) void k_search_triangulation(TriArgs A) {
     const int b = blockIdx.x, t = threadIdx.x, cap = A.cap, sn = A.sort_n;
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);          // [sn] ((node + 1) << 32 | index), absent nodes sort first
     unsigned char* s_bin = reinterpret_cast<unsigned char*>(keys + sn);              // [cap]
-    __shared__ int s_hist[BOW_HISTO], s_keep[BOW_HISTO], s_nm;
+    __shared__ int s_hist[HISTO_LENGTH], s_keep[HISTO_LENGTH], s_nm;
     __shared__ float s_e[2];
     const int N1 = min(A.n1[b], cap), N2 = min(A.n2[b], cap);
     const size_t o = (size_t)b * cap;
     for (int i = t; i < sn; i += blockDim.x)
         keys[i] = i < N2 ? (((unsigned long long)(unsigned)(A.node2[o + i] + 1) << 32) | (unsigned)i) : ~0ull;
-    if (t < BOW_HISTO) { s_hist[t] = 0; s_keep[t] = 1; }
+    if (t < HISTO_LENGTH) { s_hist[t] = 0; s_keep[t] = 1; }
     if (t == 0) {
         s_nm = 0;
         const float* P = A.pose2 + (size_t)b * 12; const float* C = A.Cw1 + (size_t)b * 3;
@@ -226,7 +199,6 @@ __global__ __launch_bounds__(1024) void k_search_triangulation(TriArgs A) {
         }
     const float ex = s_e[0], ey = s_e[1];
     const float* F = A.F12 + (size_t)b * 9;
-    const float factor = 1.0f / BOW_HISTO;
     for (int i1 = t; i1 < cap; i1 += blockDim.x) {
         int bestIdx2 = -1;
         if (i1 < N1) {
@@ -241,7 +213,7 @@ __global__ __launch_bounds__(1024) void k_search_triangulation(TriArgs A) {
                 const unsigned long long want = (unsigned long long)(unsigned)(nd + 1) << 32;
                 int lo = 0, hi = N2;
                 while (lo < hi) { const int mid = (lo + hi) >> 1; if (keys[mid] < want) lo = mid + 1; else hi = mid; }
-                int bestDist = BOW_TH_LOW;
+                int bestDist = TH_LOW;
                 for (int k = lo; k < N2 && (keys[k] >> 32) == (unsigned)(nd + 1); k++) {
                     const int i2 = (int)(keys[k] & 0xffffffffu);
                     if (A.hp2[o + i2]) continue;
@@ -249,9 +221,8 @@ __global__ __launch_bounds__(1024) void k_search_triangulation(TriArgs A) {
                     if (A.only_stereo && !st2) continue;
                     const uint4* p2 = reinterpret_cast<const uint4*>(A.d2 + (o + i2) * 32);
                     const uint4 ea = p2[0], eb = p2[1];
-                    const int dist = __popc(da.x ^ ea.x) + __popc(da.y ^ ea.y) + __popc(da.z ^ ea.z) + __popc(da.w ^ ea.w) +
-                                     __popc(db.x ^ eb.x) + __popc(db.y ^ eb.y) + __popc(db.z ^ eb.z) + __popc(db.w ^ eb.w);
-                    if (dist > BOW_TH_LOW || dist > bestDist) continue;
+                    const int dist = desc_distance(da, db, ea, eb);
+                    if (dist > TH_LOW || dist > bestDist) continue;
                     const viorb_keypoint kp2 = A.k2[o + i2];
                     if (!st1 && !st2) {
                         const float dx = ex - kp2.x, dy = ey - kp2.y;
@@ -263,10 +234,7 @@ __global__ __launch_bounds__(1024) void k_search_triangulation(TriArgs A) {
                     if ((double)dsqr < 3.84 * (double)A.level_sigma2[kp2.octave]) { bestIdx2 = i2; bestDist = dist; }
                 }
                 if (bestIdx2 >= 0) {
-                    float rot = kp1.angle - A.k2[o + bestIdx2].angle;
-                    if (rot < 0.0f) rot += 360.0f;
-                    int bin = (int)roundf(rot * factor);
-                    if (bin == BOW_HISTO) bin = 0;
+                    const int bin = rot_bin(kp1.angle, A.k2[o + bestIdx2].angle);
                     s_bin[i1] = (unsigned char)bin;
                     atomicAdd(&s_nm, 1);
                     if (A.check_ori) atomicAdd(&s_hist[bin], 1);
@@ -277,20 +245,7 @@ __global__ __launch_bounds__(1024) void k_search_triangulation(TriArgs A) {
     }
     __syncthreads();
     if (A.check_ori) {
-        if (t == 0) {                                                // ComputeThreeMaxima, src/ORBmatcher.cc:1602-1643
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < BOW_HISTO; i++) {
-                const int sz = s_hist[i];
-                if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
-                else if (sz > max3) { max3 = sz; ind3 = i; }
-            }
-            if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-            int removed = 0;
-            for (int i = 0; i < BOW_HISTO; i++) { const int keep = (i == ind1 || i == ind2 || i == ind3); s_keep[i] = keep; if (!keep) removed += s_hist[i]; }
-            s_nm -= removed;
-        }
+        if (t == 0) s_nm -= three_maxima(s_hist, s_keep);
         __syncthreads();
         for (int i1 = t; i1 < N1; i1 += blockDim.x)
             if (A.match12[o + i1] >= 0 && !s_keep[s_bin[i1]]) A.match12[o + i1] = -1;

@@ -152,11 +152,6 @@ CullOut cull_out(const viorb_cull_result* r) {
     return R;
 }
 
-template <class T> int cull_down(T* host, const T* dev, size_t n) {
-    if (host && n) VIORB_HIP_TRY(hipMemcpy(host, dev, sizeof(T) * n, hipMemcpyDeviceToHost));
-    return VIORB_OK;
-}
-
 int mpc_check(const void* bad, const void* found, const void* visible, const void* first, const void* nobs, const void* code) {
     VIORB_REQUIRE(bad && found && visible && first && nobs && code, "null array");
     return VIORB_OK;
@@ -217,14 +212,14 @@ int viorb_key_frame_culling(const viorb_cull_map* map, int monocular, const vior
     VIORB_TRY(viorb_key_frame_culling_device(&D, monocular, &O, dw, wb, nullptr));
     VIORB_HIP_TRY(hipDeviceSynchronize());
     if (result) {
-        VIORB_TRY(cull_down(result->cand_reason, O.cand_reason, nc)); VIORB_TRY(cull_down(result->cand_redundant, O.cand_redundant, nc));
-        VIORB_TRY(cull_down(result->cand_mps, O.cand_mps, nc)); VIORB_TRY(cull_down(result->cand_recounted, O.cand_recounted, nc));
-        VIORB_TRY(cull_down(result->culled_order, O.culled_order, nc)); VIORB_TRY(cull_down(result->n_culled, O.n_culled, nb));
-        VIORB_TRY(cull_down(result->status, O.status, nb)); VIORB_TRY(cull_down(result->kf_bad, O.kf_bad, nk));
-        VIORB_TRY(cull_down(result->kf_to_be_erased, O.kf_to_be_erased, nk)); VIORB_TRY(cull_down(result->kf_prev_out, O.kf_prev_out, nk));
-        VIORB_TRY(cull_down(result->kf_next_out, O.kf_next_out, nk)); VIORB_TRY(cull_down(result->kf_repreint, O.kf_repreint, nk));
-        VIORB_TRY(cull_down(result->pt_nobs_out, O.pt_nobs_out, np)); VIORB_TRY(cull_down(result->pt_bad_out, O.pt_bad_out, np));
-        VIORB_TRY(cull_down(result->obs_alive, O.obs_alive, no));
+        VIORB_TRY(download(result->cand_reason, O.cand_reason, nc)); VIORB_TRY(download(result->cand_redundant, O.cand_redundant, nc));
+        VIORB_TRY(download(result->cand_mps, O.cand_mps, nc)); VIORB_TRY(download(result->cand_recounted, O.cand_recounted, nc));
+        VIORB_TRY(download(result->culled_order, O.culled_order, nc)); VIORB_TRY(download(result->n_culled, O.n_culled, nb));
+        VIORB_TRY(download(result->status, O.status, nb)); VIORB_TRY(download(result->kf_bad, O.kf_bad, nk));
+        VIORB_TRY(download(result->kf_to_be_erased, O.kf_to_be_erased, nk)); VIORB_TRY(download(result->kf_prev_out, O.kf_prev_out, nk));
+        VIORB_TRY(download(result->kf_next_out, O.kf_next_out, nk)); VIORB_TRY(download(result->kf_repreint, O.kf_repreint, nk));
+        VIORB_TRY(download(result->pt_nobs_out, O.pt_nobs_out, np)); VIORB_TRY(download(result->pt_bad_out, O.pt_bad_out, np));
+        VIORB_TRY(download(result->obs_alive, O.obs_alive, no));
     }
     return VIORB_OK;
 }
@@ -254,7 +249,7 @@ int viorb_map_point_culling(const uint8_t* bad, const int32_t* found, const int3
     if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
     VIORB_TRY(viorb_map_point_culling_device(db, df, dv, d1, dn, dc, dk, n, 1, monocular, dcode, nullptr));
     VIORB_HIP_TRY(hipDeviceSynchronize());
-    return cull_down(code, dcode, m);
+    return download(code, dcode, m);
 }
 
 // ---- host-only test hooks: culling_core.h compiled for the host ------------------------------------------------------------------------

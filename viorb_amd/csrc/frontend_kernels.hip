@@ -12,12 +12,12 @@
 #include <atomic>
 #include <algorithm>
 #include "viorb_common.h"
-#include "orb_math.h"
+#include "sim3_match_core.h"        // match_core.h, s3m_predict_level
 #include "vio_core.h"
 
 namespace viorb {
 
-enum { GRID_COLS = 64, GRID_ROWS = 48, GRID_CELLS = GRID_COLS * GRID_ROWS, TH_HIGH = 100, HISTO_LENGTH = 30, CAND_CAP = 128 };
+enum { CAND_CAP = 128 };
 
 // ---------------------------------------------------------------------------------------------
 // Frame grid as CSR. Cell index = ix*48 + iy (the reference's mGrid[ix][iy] storage order), entries
@@ -123,7 +123,7 @@ struct SearchArgs {
     int cap;
     int slot_n;               // candidates per point cached in LDS: SEARCH_SLOT, or 0 when the frame's arrays leave no room (cap > ~2400)
     unsigned char* work; size_t work_bytes;   // k_search_projection<true>: the per-stream work arrays in global memory (a frame with more keypoints than LDS holds)
-    float minX, maxX, minY, maxY, wInv, hInv, fx, fy, cx, cy, th;
+    GridCam g; float fx, fy, cx, cy, th;
     float scale[16];
     int check_ori;
     int skip_if_at_least;     // > 0: leave streams whose nmatches[b] is already >= this untouched (TrackWithIMU's retry with 2*th)
@@ -209,10 +209,10 @@ __global__ __launch_bounds__(SEARCH_THREADS) void k_search_projection(SearchArgs
     // The search window of last-frame point i (:1351-1395): projection, radius by octave, level range, grid window. Needs no LDS: the
     // window of a thread's first point is computed BEFORE the frame is staged, so its chain of dependent global loads (flags ->
     // position -> octave -> scale factor) runs beside the staging loads instead of after the barrier.
-    struct Window { float u, v, invz, radius; int x0, x1, y0, y1, minL, maxL; bool ok; };
+    struct Window { float u, v, invz, radius; GridRect rect; int minL, maxL; bool ok; };
     auto project = [&](int i) -> Window {
         Window W; W.ok = false;
-        W.u = W.v = W.invz = W.radius = 0.0f; W.x0 = W.y0 = 0; W.x1 = W.y1 = -1; W.minL = 0; W.maxL = -1;
+        W.u = W.v = W.invz = W.radius = 0.0f; W.rect.x0 = W.rect.y0 = 0; W.rect.x1 = W.rect.y1 = -1; W.rect.empty = true; W.minL = 0; W.maxL = -1;
         const int fl = lf[i];
         if ((fl & 1) && !(fl & 2)) {
             const float* X = A.last_Pw + ((size_t)b * cap + i) * 3;
@@ -221,17 +221,14 @@ __global__ __launch_bounds__(SEARCH_THREADS) void k_search_projection(SearchArgs
             for (int r = 0; r < 3; r++) { const float tt = P[3 * r] * X[0] + P[3 * r + 1] * X[1] + P[3 * r + 2] * X[2]; pc[r] = tt + P[9 + r]; }
             const float invz = 1.0f / pc[2];
             const float u = A.fx * pc[0] * invz + A.cx, v = A.fy * pc[1] * invz + A.cy;
-            if (!(invz < 0) && !(u < A.minX || u > A.maxX) && !(v < A.minY || v > A.maxY)) {
+            if (!(invz < 0) && !(u < A.g.minX || u > A.g.maxX) && !(v < A.g.minY || v > A.g.maxY)) {
                 const int oct = lk[i].octave;
                 const float radius = A.th * A.scale[oct];
                 // bForward: levels >= octave; bBackward: levels <= octave; else octave +- 1 (:1385-1390)
                 W.minL = motion == 1 ? oct : (motion == 2 ? 0 : oct - 1); W.maxL = motion == 1 ? -1 : (motion == 2 ? oct : oct + 1);
-                W.x0 = max(0, (int)floorf((u - A.minX - radius) * A.wInv));
-                W.x1 = min((int)GRID_COLS - 1, (int)ceilf((u - A.minX + radius) * A.wInv));
-                W.y0 = max(0, (int)floorf((v - A.minY - radius) * A.hInv));
-                W.y1 = min((int)GRID_ROWS - 1, (int)ceilf((v - A.minY + radius) * A.hInv));
+                grid_window(A.g, u, v, radius, W.rect);
                 W.u = u; W.v = v; W.invz = invz; W.radius = radius;
-                W.ok = W.x0 < GRID_COLS && W.x1 >= 0 && W.y0 < GRID_ROWS && W.y1 >= 0;
+                W.ok = !W.rect.empty;
             }
         }
         return W;
@@ -265,9 +262,9 @@ __global__ __launch_bounds__(SEARCH_THREADS) void k_search_projection(SearchArgs
         int nc = 0;
         if (!W.ok) return 0;
         const float u = W.u, v = W.v, radius = W.radius;
-        const int x1 = W.x1, y0 = W.y0, y1 = W.y1, minL = W.minL, maxL = W.maxL;
+        const int x1 = W.rect.x1, y0 = W.rect.y0, y1 = W.rect.y1, minL = W.minL, maxL = W.maxL;
         const bool check_levels = (minL > 0) || (maxL >= 0);
-        int ix = W.x0, p = 0, pend = 0;
+        int ix = W.rect.x0, p = 0, pend = 0;
         for (;;) {
             const int col = min(ix, x1) * GRID_ROWS;
             const int cbeg = cs[col + y0], cend = cs[col + y1 + 1];
@@ -301,8 +298,7 @@ __global__ __launch_bounds__(SEARCH_THREADS) void k_search_projection(SearchArgs
         return scan(project(i), [&](int k, int i2) {
             const uint4* dc = reinterpret_cast<const uint4*>(A.cur_desc + ((size_t)b * cap + i2) * 32);
             const uint4 ea = dc[0], eb = dc[1];
-            const int dist = __popc(da.x ^ ea.x) + __popc(da.y ^ ea.y) + __popc(da.z ^ ea.z) + __popc(da.w ^ ea.w) +
-                             __popc(db.x ^ eb.x) + __popc(db.y ^ eb.y) + __popc(db.z ^ eb.z) + __popc(db.w ^ eb.w);
+            const int dist = desc_distance(da, db, ea, eb);
             f(k, ((uint32_t)dist << 16) | (uint32_t)i2);
         });
     };
@@ -353,8 +349,7 @@ __global__ __launch_bounds__(SEARCH_THREADS) void k_search_projection(SearchArgs
 #pragma unroll
                 for (int u = 0; u < 8; u++) {
                     if (k0 + u >= ns) break;
-                    const int dist = __popc(da.x ^ ea[u].x) + __popc(da.y ^ ea[u].y) + __popc(da.z ^ ea[u].z) + __popc(da.w ^ ea[u].w) +
-                                     __popc(db.x ^ eb[u].x) + __popc(db.y ^ eb[u].y) + __popc(db.z ^ eb[u].z) + __popc(db.w ^ eb[u].w);
+                    const int dist = desc_distance(da, db, ea[u], eb[u]);
                     set_entry(i, k0 + u, ((uint32_t)dist << 16) | id[u]);
                 }
             }
@@ -411,7 +406,6 @@ __global__ __launch_bounds__(SEARCH_THREADS) void k_search_projection(SearchArgs
     // ---- phase C: histogram, maxima, final ownership
     for (int c = t; c < ncur; c += blockDim.x) { owner[c] = -1; rej[c] = 0; }
     __syncthreads();
-    const float factor = 1.0f / HISTO_LENGTH;
     {
         int my_n = 0;
         for (int i = t; i < nlast; i += blockDim.x) {
@@ -420,12 +414,7 @@ __global__ __launch_bounds__(SEARCH_THREADS) void k_search_projection(SearchArgs
             if (c >= 0) {
                 atomicMax(&owner[c], i);
                 my_n++;
-                if (A.check_ori) {
-                    float rot = lk[i].angle - cang[c];
-                    if (rot < 0.0f) rot += 360.0f;
-                    bin = (int)roundf(rot * factor);
-                    if (bin == HISTO_LENGTH) bin = 0;
-                }
+                if (A.check_ori) bin = rot_bin(lk[i].angle, cang[c]);
             }
             taken[i] = bin;                                        // remember the bin of point i (taken[] is free now)
             if (A.check_ori) {
@@ -441,20 +430,7 @@ __global__ __launch_bounds__(SEARCH_THREADS) void k_search_projection(SearchArgs
     }
     __syncthreads();
     if (A.check_ori) {
-        if (t == 0) {            // ComputeThreeMaxima
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int i = 0; i < HISTO_LENGTH; i++) {
-                const int sz = s_hist[i];
-                if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
-                else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
-                else if (sz > max3) { max3 = sz; ind3 = i; }
-            }
-            if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-            int removed = 0;
-            for (int i = 0; i < HISTO_LENGTH; i++) { const int keep = (i == ind1 || i == ind2 || i == ind3); s_keep[i] = keep; if (!keep) removed += s_hist[i]; }
-            s_nm -= removed;
-        }
+        if (t == 0) s_nm -= three_maxima(s_hist, s_keep);
         __syncthreads();
         for (int i = t; i < nlast; i += blockDim.x) {
             const int c = choice[i];
@@ -492,7 +468,7 @@ struct LocalSearchArgs {
     uint32_t* cand; int* cand_n;
     int cap, pcap, slot_n;    // slot_n: candidates per point cached in LDS (LOCAL_SLOT or 0)
     unsigned char* work; size_t work_bytes;   // k_search_local_points<true>: the per-stream work arrays in global memory
-    float minX, maxX, minY, maxY, wInv, hInv, fx, fy, cx, cy, th, nnratio, log_sf;
+    GridCam g; float fx, fy, cx, cy, th, nnratio, log_sf;
     float scale[16];
     int nlevels;
 };
@@ -530,10 +506,10 @@ __global__ __launch_bounds__(SEARCH_THREADS) void k_search_local_points(LocalSea
     // Frame::isInFrustum of local point i and its search window (ORBmatcher.cc:60-75); fr (when not null) receives mbTrackInView,
     // mTrackProjX, mTrackProjY, mTrackViewCos, mnTrackScaleLevel. Needs no LDS: a thread's first point is done BEFORE the frame is
     // staged, its chain of dependent global loads beside the staging loads (see k_search_projection).
-    struct Window { float u, v, xr, radius; int x0, x1, y0, y1, minL, maxL; bool ok; };
+    struct Window { float u, v, xr, radius; GridRect rect; int minL, maxL; bool ok; };
     auto frustum = [&](int i, float* fr) -> Window {
         Window W; W.ok = false;
-        W.u = W.v = W.xr = W.radius = 0.0f; W.x0 = W.y0 = 0; W.x1 = W.y1 = -1; W.minL = 0; W.maxL = -1;
+        W.u = W.v = W.xr = W.radius = 0.0f; W.rect.x0 = W.rect.y0 = 0; W.rect.x1 = W.rect.y1 = -1; W.rect.empty = true; W.minL = 0; W.maxL = -1;
         const int fl = pf[i];
         float fr_in = 0, fr_u = 0, fr_v = 0, fr_cos = 0, fr_lvl = 0, fr_xr = 0;
         if ((fl & 1) && !(fl & 2)) {
@@ -544,7 +520,7 @@ __global__ __launch_bounds__(SEARCH_THREADS) void k_search_local_points(LocalSea
             bool ok = !(pc[2] < 0.0f);
             const float invz = 1.0f / pc[2];
             const float u = A.fx * pc[0] * invz + A.cx, v = A.fy * pc[1] * invz + A.cy;
-            ok = ok && !(u < A.minX || u > A.maxX) && !(v < A.minY || v > A.maxY);
+            ok = ok && !(u < A.g.minX || u > A.g.maxX) && !(v < A.g.minY || v > A.g.maxY);
             const float maxD = 1.2f * X[7], minD = 0.8f * X[6];
             const float PO0 = X[0] - Ow[0], PO1 = X[1] - Ow[1], PO2 = X[2] - Ow[2];
             const float dist = (float)sqrt((double)PO0 * PO0 + (double)PO1 * PO1 + (double)PO2 * PO2);
@@ -561,12 +537,9 @@ __global__ __launch_bounds__(SEARCH_THREADS) void k_search_local_points(LocalSea
                 if (bFactor) rr *= A.th;
                 const float radius = rr * A.scale[lvl];
                 W.minL = lvl - 1; W.maxL = lvl;
-                W.x0 = max(0, (int)floorf((u - A.minX - radius) * A.wInv));
-                W.x1 = min((int)GRID_COLS - 1, (int)ceilf((u - A.minX + radius) * A.wInv));
-                W.y0 = max(0, (int)floorf((v - A.minY - radius) * A.hInv));
-                W.y1 = min((int)GRID_ROWS - 1, (int)ceilf((v - A.minY + radius) * A.hInv));
+                grid_window(A.g, u, v, radius, W.rect);
                 W.u = u; W.v = v; W.xr = xr; W.radius = radius;
-                W.ok = W.x0 < GRID_COLS && W.x1 >= 0 && W.y0 < GRID_ROWS && W.y1 >= 0;
+                W.ok = !W.rect.empty;
             }
         }
         if (fr) { fr[0] = fr_in; fr[1] = fr_u; fr[2] = fr_v; fr[3] = fr_cos; fr[4] = fr_lvl; if (A.frustum_xr) A.frustum_xr[(size_t)b * pcap + i] = fr_xr; }
@@ -598,9 +571,9 @@ __global__ __launch_bounds__(SEARCH_THREADS) void k_search_local_points(LocalSea
         int nc = 0;
         if (!W.ok) return 0;
         const float u = W.u, v = W.v, radius = W.radius;
-        const int x1 = W.x1, y0 = W.y0, y1 = W.y1, minL = W.minL, maxL = W.maxL;
+        const int x1 = W.rect.x1, y0 = W.rect.y0, y1 = W.rect.y1, minL = W.minL, maxL = W.maxL;
         const bool check_levels = (minL > 0) || (maxL >= 0);
-        int ix = W.x0, p = 0, pend = 0;
+        int ix = W.rect.x0, p = 0, pend = 0;
         for (;;) {
             const int col = min(ix, x1) * GRID_ROWS;
             const int cbeg = cs[col + y0], cend = cs[col + y1 + 1];
@@ -635,8 +608,7 @@ __global__ __launch_bounds__(SEARCH_THREADS) void k_search_local_points(LocalSea
         return scan(frustum(i, nullptr), [&](int k, uint32_t li) {
             const uint4* dc = reinterpret_cast<const uint4*>(A.cur_desc + ((size_t)b * cap + (li & 0xffff)) * 32);
             const uint4 ea = dc[0], eb = dc[1];
-            const int dist2 = __popc(da.x ^ ea.x) + __popc(da.y ^ ea.y) + __popc(da.z ^ ea.z) + __popc(da.w ^ ea.w) +
-                              __popc(db.x ^ eb.x) + __popc(db.y ^ eb.y) + __popc(db.z ^ eb.z) + __popc(db.w ^ eb.w);
+            const int dist2 = desc_distance(da, db, ea, eb);
             f(k, ((uint32_t)dist2 << 20) | li);
         });
     };
@@ -680,8 +652,7 @@ __global__ __launch_bounds__(SEARCH_THREADS) void k_search_local_points(LocalSea
 #pragma unroll
                 for (int u = 0; u < 8; u++) {
                     if (k0 + u >= ns) break;
-                    const int dist2 = __popc(da.x ^ ea[u].x) + __popc(da.y ^ ea[u].y) + __popc(da.z ^ ea[u].z) + __popc(da.w ^ ea[u].w) +
-                                      __popc(db.x ^ eb[u].x) + __popc(db.y ^ eb[u].y) + __popc(db.z ^ eb[u].z) + __popc(db.w ^ eb[u].w);
+                    const int dist2 = desc_distance(da, db, ea[u], eb[u]);
                     set_entry(i, k0 + u, ((uint32_t)dist2 << 20) | (id[u] & 0xfffffu));
                 }
             }
@@ -963,13 +934,13 @@ struct FuseArgs {
     const float* pose12; const float* pts_f; const uint8_t* pts_valid; const uint8_t* pts_desc; const int* pts_count;
     int* best_idx; int* nfused;
     int cap, pcap, nlevels;
-    float minX, maxX, minY, maxY, wInv, hInv, fx, fy, cx, cy, bf, th, log_sf;
+    GridCam g; float fx, fy, cx, cy, bf, th, log_sf;
     float scale[16], inv_sigma2[16];
 };
 __global__ __launch_bounds__(1024) void k_fuse(FuseArgs A) {
     __shared__ int s_n;
     const int b = blockIdx.x, t = threadIdx.x, cap = A.cap, pcap = A.pcap;
-    const int npts = min(A.pts_count[b], pcap);
+    const int npts = min(A.pts_count[b], pcap), n = min(max(A.count[b], 0), cap);
     const float* P = A.pose12 + (size_t)b * 12;
     const viorb_keypoint* kp = A.kps + (size_t)b * cap;
     const int* cs = A.cell_start + (size_t)b * (GRID_CELLS + 1);
@@ -991,7 +962,7 @@ __global__ __launch_bounds__(1024) void k_fuse(FuseArgs A) {
             const float invz = 1.0f / pc[2];
             const float x = pc[0] * invz, y = pc[1] * invz;
             const float u = A.fx * x + A.cx, v = A.fy * y + A.cy;
-            ok = ok && (u >= A.minX && u < A.maxX && v >= A.minY && v < A.maxY);
+            ok = ok && (u >= A.g.minX && u < A.g.maxX && v >= A.g.minY && v < A.g.maxY);
             const float ur = u - A.bf * invz;
             const float maxD = 1.2f * X[7], minD = 0.8f * X[6];
             const float PO0 = X[0] - Ow[0], PO1 = X[1] - Ow[1], PO2 = X[2] - Ow[2];
@@ -1000,44 +971,33 @@ __global__ __launch_bounds__(1024) void k_fuse(FuseArgs A) {
             const double dotp = (double)PO0 * X[3] + (double)PO1 * X[4] + (double)PO2 * X[5];
             ok = ok && !(dotp < 0.5 * (double)dist3D);
             if (ok) {
-                const float ratio = X[7] / dist3D;
-                int lvl = (int)ceilf(viorb_logf(ratio) / A.log_sf);
-                lvl = lvl < 0 ? 0 : (lvl >= A.nlevels ? A.nlevels - 1 : lvl);
+                const int lvl = s3m_predict_level(X[7], dist3D, A.log_sf, A.nlevels);
                 const float radius = A.th * A.scale[lvl];
-                const int x0 = max(0, (int)floorf((u - A.minX - radius) * A.wInv));
-                const int x1 = min((int)GRID_COLS - 1, (int)ceilf((u - A.minX + radius) * A.wInv));
-                const int y0 = max(0, (int)floorf((v - A.minY - radius) * A.hInv));
-                const int y1 = min((int)GRID_ROWS - 1, (int)ceilf((v - A.minY + radius) * A.hInv));
-                if (x0 < GRID_COLS && x1 >= 0 && y0 < GRID_ROWS && y1 >= 0) {
+                GridRect R;
+                grid_window(A.g, u, v, radius, R);
+                if (!R.empty) {
                     const uint4* dl = reinterpret_cast<const uint4*>(A.pts_desc + ((size_t)b * pcap + i) * 32);
                     const uint4 da = dl[0], db = dl[1];
                     int bestDist = 256;
-                    for (int ix = x0; ix <= x1; ix++) {
-                        const int pbeg = cs[ix * GRID_ROWS + y0], pend = cs[ix * GRID_ROWS + y1 + 1];
-                        for (int q = pbeg; q < pend; q++) {
-                            const int idx = ci[q];
-                            const viorb_keypoint k = kp[idx];
-                            if (!(fabsf(k.x - u) < radius && fabsf(k.y - v) < radius)) continue;
-                            const int kl = k.octave;
-                            if (kl < lvl - 1 || kl > lvl) continue;
-                            const float kr = A.uright[(size_t)b * cap + idx];
-                            const float ex = u - k.x, ey = v - k.y;
-                            if (kr >= 0) {
-                                const float er = ur - kr;
-                                const float e2 = ex * ex + ey * ey + er * er;
-                                if ((double)(e2 * A.inv_sigma2[kl]) > 7.8) continue;
-                            } else {
-                                const float e2 = ex * ex + ey * ey;
-                                if ((double)(e2 * A.inv_sigma2[kl]) > 5.99) continue;
-                            }
-                            const uint4* dc = reinterpret_cast<const uint4*>(A.desc + ((size_t)b * cap + idx) * 32);
-                            const uint4 ea = dc[0], eb = dc[1];
-                            const int dist = __popc(da.x ^ ea.x) + __popc(da.y ^ ea.y) + __popc(da.z ^ ea.z) + __popc(da.w ^ ea.w) +
-                                             __popc(db.x ^ eb.x) + __popc(db.y ^ eb.y) + __popc(db.z ^ eb.z) + __popc(db.w ^ eb.w);
-                            if (dist < bestDist) { bestDist = dist; best = idx; }
+                    grid_scan(R, cs, ci, n, cap, [&](int idx) {
+                        const viorb_keypoint k = kp[idx];
+                        if (!(fabsf(k.x - u) < radius && fabsf(k.y - v) < radius)) return;
+                        const int kl = k.octave;
+                        if (kl < lvl - 1 || kl > lvl) return;
+                        const float kr = A.uright[(size_t)b * cap + idx];
+                        const float ex = u - k.x, ey = v - k.y;
+                        if (kr >= 0) {
+                            const float er = ur - kr;
+                            const float e2 = ex * ex + ey * ey + er * er;
+                            if ((double)(e2 * A.inv_sigma2[kl]) > 7.8) return;
+                        } else {
+                            const float e2 = ex * ex + ey * ey;
+                            if ((double)(e2 * A.inv_sigma2[kl]) > 5.99) return;
                         }
-                    }
-                    if (bestDist > 50) best = -1;                       // TH_LOW
+                        const int dist = desc_distance(da, db, A.desc + ((size_t)b * cap + idx) * 32);
+                        if (dist < bestDist) { bestDist = dist; best = idx; }
+                    });
+                    if (bestDist > TH_LOW) best = -1;
                 }
             }
         }
@@ -1565,7 +1525,7 @@ using namespace viorb;
 struct viorb_frontend {
     viorb_frontend_config cfg;
     int max_batch = 0, cap = 0, device = 0, sort_n = 0;
-    float wInv = 0, hInv = 0;
+    GridCam g = {};                                           // the image bounds of cfg and the grid's cells per pixel
     uint32_t* d_cand = nullptr; int* d_cand_n = nullptr;
     float* d_pose_chi = nullptr;                              // k_pose_opt_vi_mp's per-edge chi2 scratch [max_batch][2][cap]
     uint32_t* d_lcand = nullptr; int* d_lcand_n = nullptr; int lcand_pcap = 0;
@@ -1630,9 +1590,8 @@ int viorb_frontend_create(const viorb_frontend_config* cfg, int max_batch, int c
     if (h->cfg.gyr_meas_cov <= 0) h->cfg.gyr_meas_cov = 2.0e-3 * 2.0e-3 * 200;     // reference src/IMU/imudata.cpp:36-37
     if (h->cfg.acc_meas_cov <= 0) h->cfg.acc_meas_cov = 8.0e-3 * 8.0e-3 * 200;
     if (h->cfg.acc_bias_rw2 <= 0) h->cfg.acc_bias_rw2 = 5e-3 * 5e-3;               // :32
-    // Frame.cc:184-185
-    h->wInv = static_cast<float>(GRID_COLS) / static_cast<float>(cfg->max_x - cfg->min_x);
-    h->hInv = static_cast<float>(GRID_ROWS) / static_cast<float>(cfg->max_y - cfg->min_y);
+    const float bounds4[4] = {cfg->min_x, cfg->max_x, cfg->min_y, cfg->max_y};
+    h->g = grid_cam(bounds4);
     int s = 64; while (s < cap) s <<= 1;
     h->sort_n = s;
     {   // the projection search's LDS plan limits cap to ~4900 — checked where it is launched: the other calls of the handle (grid, IMU
@@ -1687,7 +1646,7 @@ int viorb_frontend_grid_device(viorb_frontend* h, const viorb_keypoint* kps, con
     VIORB_REQUIRE(kps && count && cell_start && cell_idx, "null array");
     ProfScope ps("k_frame_grid", (hipStream_t)stream);
     hipLaunchKernelGGL(k_frame_grid, dim3(batch), dim3(256), (size_t)h->sort_n * 4, (hipStream_t)stream, kps, count, h->cap,
-                       h->cfg.min_x, h->cfg.min_y, h->wInv, h->hInv, cell_start, cell_idx, h->sort_n);
+                       h->g.minX, h->g.minY, h->g.wInv, h->g.hInv, cell_start, cell_idx, h->sort_n);
     VIORB_HIP_TRY(hipGetLastError());
     return VIORB_OK;
 }
@@ -1704,9 +1663,8 @@ int viorb_keyframe_grid_device(const viorb_keypoint* kps, const int32_t* count, 
     int sort_n = 64; while (sort_n < cap) sort_n <<= 1;
     const size_t lds = (size_t)sort_n * 4;                            // cap <= VIORB_S3M_MAX_FEATURES: at most 64 KiB
     if (lds > 48 * 1024) VIORB_HIP_TRY(raise_dynamic_lds(reinterpret_cast<const void*>(k_frame_grid), lds));
-    const float wInv = static_cast<float>(GRID_COLS) / static_cast<float>(bounds4[1] - bounds4[0]);
-    const float hInv = static_cast<float>(GRID_ROWS) / static_cast<float>(bounds4[3] - bounds4[2]);
-    VIORB_LAUNCH(k_frame_grid, batch, 256, lds, (hipStream_t)stream, kps, count, cap, bounds4[0], bounds4[2], wInv, hInv, cell_start, cell_idx, sort_n);
+    const GridCam g = grid_cam(bounds4);
+    VIORB_LAUNCH(k_frame_grid, batch, 256, lds, (hipStream_t)stream, kps, count, cap, g.minX, g.minY, g.wInv, g.hInv, cell_start, cell_idx, sort_n);
     return VIORB_OK;
 }
 
@@ -1794,7 +1752,7 @@ int viorb_frontend_search_projection_retry_device(viorb_frontend* h, const viorb
     A.pose12 = pose12; A.last_kps = last_kps; A.last_count = last_count; A.last_flags = last_flags; A.last_Pw = last_Pw;
     A.last_desc = last_desc; A.cur_match = cur_match; A.nmatches = nmatches; A.status = status;
     A.cand = h->d_cand; A.cand_n = h->d_cand_n; A.cap = h->cap;
-    A.minX = h->cfg.min_x; A.maxX = h->cfg.max_x; A.minY = h->cfg.min_y; A.maxY = h->cfg.max_y; A.wInv = h->wInv; A.hInv = h->hInv;
+    A.g = h->g;
     A.fx = h->cfg.fx; A.fy = h->cfg.fy; A.cx = h->cfg.cx; A.cy = h->cfg.cy; A.th = th;
     for (int i = 0; i < 16; i++) A.scale[i] = h->cfg.scale_factors[i];
     A.check_ori = h->cfg.check_orientation;
@@ -1876,7 +1834,7 @@ int viorb_frontend_search_local_points_device(viorb_frontend* h, const viorb_key
     A.match = match; A.nmatches = nmatches; A.status = status; A.frustum = frustum; A.cand = h->d_lcand; A.cand_n = h->d_lcand_n;
     A.cur_uright = g_stereo_local.cur_uright; A.bf = g_stereo_local.bf; A.frustum_xr = g_stereo_local.frustum_xr;
     A.cap = h->cap; A.pcap = pcap; A.slot_n = lslot;
-    A.minX = h->cfg.min_x; A.maxX = h->cfg.max_x; A.minY = h->cfg.min_y; A.maxY = h->cfg.max_y; A.wInv = h->wInv; A.hInv = h->hInv;
+    A.g = h->g;
     A.fx = h->cfg.fx; A.fy = h->cfg.fy; A.cx = h->cfg.cx; A.cy = h->cfg.cy; A.th = th; A.nnratio = nnratio;
     A.log_sf = (float)log((double)h->cfg.scale_factors[h->cfg.nlevels > 1 ? 1 : 0]);   // Frame::mfLogScaleFactor = log(mfScaleFactor), rounded once
     for (int i = 0; i < 16; i++) A.scale[i] = h->cfg.scale_factors[i];
@@ -2007,7 +1965,7 @@ int viorb_frontend_fuse_device(viorb_frontend* h, const viorb_keypoint* kps, con
     A.kps = kps; A.desc = desc; A.uright = uright; A.count = count; A.cell_start = cell_start; A.cell_idx = cell_idx; A.pose12 = pose12;
     A.pts_f = pts_f; A.pts_valid = pts_valid; A.pts_desc = pts_desc; A.pts_count = pts_count; A.best_idx = best_idx; A.nfused = nfused;
     A.cap = h->cap; A.pcap = pcap; A.nlevels = h->cfg.nlevels;
-    A.minX = h->cfg.min_x; A.maxX = h->cfg.max_x; A.minY = h->cfg.min_y; A.maxY = h->cfg.max_y; A.wInv = h->wInv; A.hInv = h->hInv;
+    A.g = h->g;
     A.fx = h->cfg.fx; A.fy = h->cfg.fy; A.cx = h->cfg.cx; A.cy = h->cfg.cy; A.bf = bf; A.th = th;
     A.log_sf = (float)log((double)h->cfg.scale_factors[h->cfg.nlevels > 1 ? 1 : 0]);
     for (int i = 0; i < 16; i++) { A.scale[i] = h->cfg.scale_factors[i]; A.inv_sigma2[i] = h->cfg.inv_level_sigma2[i]; }
@@ -2231,8 +2189,8 @@ static int host_frontend(const viorb_frontend_config& c, int cap, viorb_frontend
         if (cc.acc_bias_rw2 <= 0) cc.acc_bias_rw2 = 5e-3 * 5e-3;
         if (memcmp(&h->cfg, &cc, sizeof(cc)) == 0) { *out = h; return VIORB_OK; }      // same camera / tables as the previous call: nothing to upload
         h->cfg = cc;
-        h->wInv = static_cast<float>(GRID_COLS) / static_cast<float>(cc.max_x - cc.min_x);
-        h->hInv = static_cast<float>(GRID_ROWS) / static_cast<float>(cc.max_y - cc.min_y);
+        const float bounds4[4] = {cc.min_x, cc.max_x, cc.min_y, cc.max_y};
+        h->g = grid_cam(bounds4);
         VIORB_HIP_TRY(hipSetDevice(dev));
         VIORB_HIP_TRY(hipMemcpyAsync(h->d_cam, cc.cam, 16 * sizeof(double), hipMemcpyHostToDevice, nullptr));
         VIORB_HIP_TRY(hipMemcpyAsync(h->d_gw, cc.gravity, 3 * sizeof(double), hipMemcpyHostToDevice, nullptr));

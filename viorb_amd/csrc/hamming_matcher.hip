@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <vector>
 #include "viorb_common.h"
+#include "match_core.h"
 
 namespace viorb {
 
@@ -43,9 +44,7 @@ __global__ __launch_bounds__(BF_THREADS) void k_match_bruteforce(const uint8_t* 
 #pragma unroll 4
         for (int j = 0; j < m; j++) {
             const uint4 a = T[2 * j], c = T[2 * j + 1];                    // same address in every lane: broadcast
-            int d = __popc(q0.x ^ a.x);
-            d += __popc(q0.y ^ a.y); d += __popc(q0.z ^ a.z); d += __popc(q0.w ^ a.w);
-            d += __popc(q1.x ^ c.x); d += __popc(q1.y ^ c.y); d += __popc(q1.z ^ c.z); d += __popc(q1.w ^ c.w);
+            const int d = desc_distance(q0, q1, a, c);
             // if (d < d1) { d2 = d1; d1 = d; i1 = j } else if (d < d2) d2 = d;   branch-free
             const bool lt1 = d < d1;
             d2 = lt1 ? d1 : min(d2, d);

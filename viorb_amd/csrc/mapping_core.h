@@ -11,14 +11,9 @@
 // The 4 x 4 SVD is a one-sided Jacobi on the lane, held in double registers (see jacobi_rot).
 #pragma once
 #include <float.h>
-#include <math.h>
-#include <stdint.h>
+#include "orb_math.h"               // VIORB_HD, hamming256
 
-#if defined(__HIPCC__)
-#define MAP_HD __host__ __device__ __forceinline__
-#else
-#define MAP_HD inline
-#endif
+#define MAP_HD VIORB_HD
 
 namespace viorb {
 
@@ -205,13 +200,6 @@ MAP_HD void finish_point(const float* Pw, const float (&nsum)[3], int nobs, cons
     out8[0] = Pw[0]; out8[1] = Pw[1]; out8[2] = Pw[2];
     out8[3] = (float)((double)nsum[0] / (double)nobs); out8[4] = (float)((double)nsum[1] / (double)nobs); out8[5] = (float)((double)nsum[2] / (double)nobs);
     out8[6] = mind; out8[7] = maxd;
-}
-
-MAP_HD int hamming256(const uint32_t* a, const uint32_t* b) {
-    int d = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) d += __builtin_popcount(a[k] ^ b[k]);
-    return d;
 }
 
 } // namespace viorb

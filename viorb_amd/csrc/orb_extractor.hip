@@ -23,7 +23,7 @@
 #include <string>
 #include <algorithm>
 #include "viorb_common.h"
-#include "orb_math.h"
+#include "match_core.h"
 #include "octree_arrays.h"
 
 namespace viorb {
@@ -1701,7 +1701,7 @@ __global__ __launch_bounds__(1024) void k_stereo_match(StereoArgs A) {
     const float mb = A.bf / A.fx, minD = 0.f, maxD = A.bf / mb;
     const float rmax = 2.0f * A.scale[A.nlevels - 1];
     const int nRows = A.lv[0].h;
-    const int thOrbDist = (100 + 50) / 2;
+    const int thOrbDist = (TH_HIGH + TH_LOW) / 2;
     for (int iL = t; iL < cap; iL += blockDim.x) {
         float out_u = -1.f, out_d = -1.f; int out_sad = -1;
         if (iL < N) {
@@ -1726,9 +1726,8 @@ __global__ __launch_bounds__(1024) void k_stereo_match(StereoArgs A) {
                     if (!(kpR.x >= minU && kpR.x <= maxU)) continue;
                     const uint4* pr = reinterpret_cast<const uint4*>(dr + (size_t)iR * 32);
                     const uint4 ea = pr[0], eb = pr[1];
-                    const int dist = __popc(da.x ^ ea.x) + __popc(da.y ^ ea.y) + __popc(da.z ^ ea.z) + __popc(da.w ^ ea.w) +
-                                     __popc(db.x ^ eb.x) + __popc(db.y ^ eb.y) + __popc(db.z ^ eb.z) + __popc(db.w ^ eb.w);
-                    if (dist < 100) best = min(best, ((uint32_t)dist << 16) | (uint32_t)iR);
+                    const int dist = desc_distance(da, db, ea, eb);
+                    if (dist < TH_HIGH) best = min(best, ((uint32_t)dist << 16) | (uint32_t)iR);
                 }
                 if (best != 0xffffffffu && (int)(best >> 16) < thOrbDist) {
                     const int bestIdxR = (int)(best & 0xffff);

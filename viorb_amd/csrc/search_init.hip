@@ -21,23 +21,8 @@ struct SiArgs {
     const viorb_keypoint* kps1; const uint8_t* desc1; const int* n1; SiKf kf2; float* prev;
     uint32_t* cand; int* cand_n; int* why; uint32_t* st; uint32_t* st2; int* next;     // workspace: cand [batch][SI_LIST][cap], the rest [batch][cap]
     int* matches12; int* nmatches; viorb_search_init_outputs out;             // out: every pointer may be NULL
-    SiCam cam; float r, nnratio; int check_ori, cap;
+    GridCam cam; float r, nnratio; int check_ori, cap;
 };
-
-__device__ __forceinline__ int si_hamming(const uint4 da, const uint4 db, const uint8_t* row) {
-    const uint4* dc = reinterpret_cast<const uint4*>(row);
-    const uint4 ea = dc[0], eb = dc[1];
-    const unsigned long long a0 = ((unsigned long long)(da.y ^ ea.y) << 32) | (da.x ^ ea.x), a1 = ((unsigned long long)(da.w ^ ea.w) << 32) | (da.z ^ ea.z);
-    const unsigned long long b0 = ((unsigned long long)(db.y ^ eb.y) << 32) | (db.x ^ eb.x), b1 = ((unsigned long long)(db.w ^ eb.w) << 32) | (db.z ^ eb.z);
-    return __popcll(a0) + __popcll(a1) + __popcll(b0) + __popcll(b1);
-}
-
-// The entries [beg, end) of column ix of the window in the CSR: the cells of one column are adjacent in storage order ix*48 + iy.
-// Clamped into 0..cap so that a grid that was not built for these arrays cannot send a read out of them.
-__device__ __forceinline__ void si_column(const int* __restrict__ cs, int ix, int y0, int y1, int cap, int& beg, int& end) {
-    beg = min(max(cs[ix * SI_GRID_ROWS + y0], 0), cap);
-    end = min(max(cs[ix * SI_GRID_ROWS + y1 + 1], beg), cap);
-}
 
 // blockIdx = (chunk of SI_POINTS points, stream); one wavefront per point of frame 1. Writes the point's list (candidates si_keep admits,
 // in visiting order; the count goes on past SI_LIST and k_si_ordered rescans the window of such a point), its first reason, xy1 and xy2.
@@ -55,11 +40,11 @@ __global__ __launch_bounds__(SI_BLOCK) void k_si_candidates(SiArgs A) {
     const int level1 = i < n1 ? A.kps1[o].octave : 1;
     if (level1 <= 0) {                                               // :422
         const float x = A.prev[o * 2], y = A.prev[o * 2 + 1], r = A.r;
-        SiRect R;
-        si_window(A.cam, x, y, r, R);
+        GridRect R;
+        grid_window(A.cam, x, y, r, R);
         int nwin = 0;
         if (!R.empty && n2 > 0) {
-            const int* cs = A.kf2.cell_start + (size_t)b * (SI_GRID_CELLS + 1);
+            const int* cs = A.kf2.cell_start + (size_t)b * (GRID_CELLS + 1);
             const int* ci = A.kf2.cell_idx + (size_t)b * cap;
             const uint8_t* desc2 = A.kf2.desc + (size_t)b * cap * 32;
             const uint4* dl = reinterpret_cast<const uint4*>(A.desc1 + o * 32);
@@ -67,7 +52,7 @@ __global__ __launch_bounds__(SI_BLOCK) void k_si_candidates(SiArgs A) {
             uint32_t* list = A.cand + (size_t)b * SI_LIST * cap + i;
             // lane c holds column x0 + c of the window (at most 64 columns): its run of the CSR and the run's offset in the window's sequence
             int beg = 0, len = 0;
-            if (lane <= R.x1 - R.x0) { int end; si_column(cs, R.x0 + lane, R.y0, R.y1, cap, beg, end); len = end - beg; }
+            if (lane <= R.x1 - R.x0) { int end; grid_column(cs, R.x0 + lane, R.y0, R.y1, cap, beg, end); len = end - beg; }
             int incl = len;
 #pragma unroll
             for (int s = 1; s < SI_WAVE; s <<= 1) { const int v = __shfl_up(incl, s); if (lane >= s) incl += v; }
@@ -87,7 +72,7 @@ __global__ __launch_bounds__(SI_BLOCK) void k_si_candidates(SiArgs A) {
                         pass = si_level_ok(level1, k.octave) && fabsf(k.x - x) < r && fabsf(k.y - y) < r;
                     }
                 }
-                if (pass) d = si_hamming(da, db, desc2 + (size_t)idx * 32);
+                if (pass) d = desc_distance(da, db, desc2 + (size_t)idx * 32);
                 const bool keep = pass && si_keep(d, A.nnratio);
                 nwin += __popcll(__ballot(pass));
                 const unsigned long long km = __ballot(keep);
@@ -101,25 +86,13 @@ __global__ __launch_bounds__(SI_BLOCK) void k_si_candidates(SiArgs A) {
     if (lane == 0) { A.cand_n[o] = ncand; A.why[o] = why; }
 }
 
-// The workgroup's count of `flag`, returned to every thread. Every thread calls it.
-__device__ __forceinline__ int si_block_count(bool flag, int* s_part) {
-    const int lane = threadIdx.x & (SI_WAVE - 1), w = threadIdx.x / SI_WAVE, nw = (blockDim.x + SI_WAVE - 1) / SI_WAVE;
-    const int c = __popcll(__ballot(flag));
-    if (lane == 0) s_part[w] = c;
-    __syncthreads();
-    int total = 0;
-    for (int k = 0; k < nw; k++) total += s_part[k];
-    __syncthreads();
-    return total;
-}
-
 // One workgroup per stream: the sweeps of si_ordered_sweeps (search_init_core.h) with the points of a sweep in parallel, then what follows
 // the main loop. s_head[f] chains the points accepted on feature f (LDS exchange; the order of a chain does not matter to si_seen). The
 // states of a sweep are read from one array and written to the other, so a run does not depend on the order of the threads.
 __global__ __launch_bounds__(SI_ORDERED_THREADS) void k_si_ordered(SiArgs A) {
     extern __shared__ int s_head[];
     __shared__ int s_part[SI_ORDERED_THREADS / SI_WAVE];
-    __shared__ int s_hist[SI_HISTO], s_keep[SI_HISTO];
+    __shared__ int s_hist[HISTO_LENGTH], s_keep[HISTO_LENGTH];
     const int b = blockIdx.x, t = threadIdx.x, cap = A.cap;
     const int n1 = min(max(A.n1[b], 0), cap), n2 = min(max(A.kf2.count[b], 0), cap);
     const size_t ob = (size_t)b * cap;
@@ -132,7 +105,7 @@ __global__ __launch_bounds__(SI_ORDERED_THREADS) void k_si_ordered(SiArgs A) {
     uint32_t* cur = A.st + ob;
     uint32_t* nxt = A.st2 + ob;
     for (int p = t; p < cap; p += blockDim.x) { cur[p] = SI_NONE; nxt[p] = SI_NONE; }
-    if (t < SI_HISTO) { s_hist[t] = 0; s_keep[t] = 1; }
+    if (t < HISTO_LENGTH) { s_hist[t] = 0; s_keep[t] = 1; }
     __syncthreads();
     int sweeps = 0;
     for (;;) {
@@ -156,24 +129,18 @@ __global__ __launch_bounds__(SI_ORDERED_THREADS) void k_si_ordered(SiArgs A) {
             } else {                                                 // more candidates than the list holds: the window again, nothing left out
                 const float x = A.prev[(ob + p) * 2], y = A.prev[(ob + p) * 2 + 1], r = A.r;
                 const int level1 = kp1[p].octave;
-                SiRect R;
-                si_window(A.cam, x, y, r, R);
-                const int* cs = A.kf2.cell_start + (size_t)b * (SI_GRID_CELLS + 1);
+                GridRect R;
+                grid_window(A.cam, x, y, r, R);
+                const int* cs = A.kf2.cell_start + (size_t)b * (GRID_CELLS + 1);
                 const int* ci = A.kf2.cell_idx + ob;
                 const uint8_t* desc2 = A.kf2.desc + ob * 32;
                 const uint4* dl = reinterpret_cast<const uint4*>(A.desc1 + (ob + p) * 32);
                 const uint4 da = dl[0], db = dl[1];
-                for (int ix = R.x0; ix <= R.x1; ix++) {
-                    int beg, end;
-                    si_column(cs, ix, R.y0, R.y1, cap, beg, end);
-                    for (int q = beg; q < end; q++) {
-                        const int idx = ci[q];
-                        if ((unsigned)idx >= (unsigned)n2) continue;
-                        const viorb_keypoint k = kp2[idx];
-                        if (!(si_level_ok(level1, k.octave) && fabsf(k.x - x) < r && fabsf(k.y - y) < r)) continue;
-                        si_pick_visit(P, si_hamming(da, db, desc2 + (size_t)idx * 32), idx, si_seen(s_head, next, cur, idx, p));
-                    }
-                }
+                grid_scan(R, cs, ci, n2, cap, [&](int idx) {
+                    const viorb_keypoint k = kp2[idx];
+                    if (!(si_level_ok(level1, k.octave) && fabsf(k.x - x) < r && fabsf(k.y - y) < r)) return;
+                    si_pick_visit(P, desc_distance(da, db, desc2 + (size_t)idx * 32), idx, si_seen(s_head, next, cur, idx, p));
+                });
             }
             int w;
             const uint32_t s = si_decide(P, A.nnratio, w);
@@ -192,10 +159,10 @@ __global__ __launch_bounds__(SI_ORDERED_THREADS) void k_si_ordered(SiArgs A) {
     if (A.check_ori) {                                               // rotHist keeps a displaced point (:482 is never undone)
         for (int p = t; p < n1; p += blockDim.x) {
             const uint32_t s = cur[p];
-            if (s != SI_NONE) atomicAdd(&s_hist[si_rot_bin(kp1[p].angle, kp2[s & 0xffffu].angle)], 1);
+            if (s != SI_NONE) atomicAdd(&s_hist[rot_bin(kp1[p].angle, kp2[s & 0xffffu].angle)], 1);
         }
         __syncthreads();
-        if (t == 0) si_three_maxima(s_hist, s_keep);
+        if (t == 0) three_maxima(s_hist, s_keep);
         __syncthreads();
     }
     int found = 0;
@@ -210,7 +177,7 @@ __global__ __launch_bounds__(SI_ORDERED_THREADS) void k_si_ordered(SiArgs A) {
                 if (s != SI_NONE) {
                     const int f = (int)(s & 0xffffu);
                     if (s_head[f] != p) reason = SI_DISPLACED;
-                    else if (A.check_ori && !s_keep[si_rot_bin(kp1[p].angle, kp2[f].angle)]) reason = SI_ROTATION;
+                    else if (A.check_ori && !s_keep[rot_bin(kp1[p].angle, kp2[f].angle)]) reason = SI_ROTATION;
                     else { reason = SI_MATCHED; m = f; }
                 }
             }
@@ -218,7 +185,7 @@ __global__ __launch_bounds__(SI_ORDERED_THREADS) void k_si_ordered(SiArgs A) {
             if (A.out.reason) A.out.reason[ob + p] = reason;
             if (m >= 0) { A.prev[(ob + p) * 2] = kp2[m].x; A.prev[(ob + p) * 2 + 1] = kp2[m].y; }      // :515-517
         }
-        found += si_block_count(m >= 0, s_part);
+        found += block_count(m >= 0, s_part);
     }
     if (A.out.matches21 || A.out.matched_distance)
         for (int f = t; f < cap; f += blockDim.x) {
@@ -226,7 +193,7 @@ __global__ __launch_bounds__(SI_ORDERED_THREADS) void k_si_ordered(SiArgs A) {
             if (A.out.matches21) A.out.matches21[ob + f] = p;
             if (A.out.matched_distance) A.out.matched_distance[ob + f] = p >= 0 ? (int)(cur[p] >> 16) : INT_MAX;
         }
-    if (A.out.rot_hist && t < SI_HISTO) A.out.rot_hist[(size_t)b * SI_HISTO + t] = s_hist[t];
+    if (A.out.rot_hist && t < HISTO_LENGTH) A.out.rot_hist[(size_t)b * HISTO_LENGTH + t] = s_hist[t];
     if (t == 0) { A.nmatches[b] = found; if (A.out.sweeps) A.out.sweeps[b] = sweeps; }
 }
 
@@ -245,7 +212,7 @@ __global__ __launch_bounds__(SI_MEDIAN_THREADS) void k_si_median(const float* __
     const float* X = points + (size_t)b * cap * 3;
     const uint8_t* hp = has_point + (size_t)b * cap;
     int ng = 0;
-    for (int base = 0; base < n; base += SI_MEDIAN_THREADS) { const int i = base + t; ng += si_block_count(i < n && hp[i], s_part); }
+    for (int base = 0; base < n; base += SI_MEDIAN_THREADS) { const int i = base + t; ng += block_count(i < n && hp[i], s_part); }
     if (ng == 0) { if (t == 0) { median[b] = -1.0f; n_depths[b] = 0; } return; }
     if (t == 0) { s_prefix = 0; s_k = (ng - 1) / q; }
     for (int pass = 0; pass < 4; pass++) {
@@ -290,19 +257,6 @@ int si_check_common(int cap, int batch, const float* bounds4, int window_size, f
     return VIORB_OK;
 }
 
-SiCam si_cam(const float* bounds4) {
-    SiCam C;
-    C.minX = bounds4[0]; C.maxX = bounds4[1]; C.minY = bounds4[2]; C.maxY = bounds4[3];
-    C.wInv = static_cast<float>(SI_GRID_COLS) / static_cast<float>(C.maxX - C.minX);        // Frame.cc:184-185
-    C.hInv = static_cast<float>(SI_GRID_ROWS) / static_cast<float>(C.maxY - C.minY);
-    return C;
-}
-
-template <class T> int si_down(T* host, const T* dev, size_t n) {
-    if (host && n) VIORB_HIP_TRY(hipMemcpy(host, dev, sizeof(T) * n, hipMemcpyDeviceToHost));
-    return VIORB_OK;
-}
-
 } // namespace
 
 extern "C" {
@@ -337,7 +291,7 @@ int viorb_search_for_initialization_device(const viorb_keypoint* kps1, const uin
     A.cand = L.cand; A.cand_n = L.cand_n; A.why = L.why; A.st = L.st; A.st2 = L.st2; A.next = L.next;
     A.matches12 = matches12; A.nmatches = nmatches;
     if (out) A.out = *out; else memset(&A.out, 0, sizeof(A.out));
-    A.cam = si_cam(bounds4); A.r = (float)window_size; A.nnratio = nnratio; A.check_ori = check_orientation ? 1 : 0; A.cap = cap;
+    A.cam = grid_cam(bounds4); A.r = (float)window_size; A.nnratio = nnratio; A.check_ori = check_orientation ? 1 : 0; A.cap = cap;
     VIORB_LAUNCH(k_si_candidates, dim3((cap + SI_POINTS - 1) / SI_POINTS, batch), SI_BLOCK, 0, st, A);
     const size_t lds = (size_t)cap * sizeof(int);                    // cap <= VIORB_S3M_MAX_FEATURES: at most 64 KiB beside the static words
     if (lds > 48 * 1024) VIORB_HIP_TRY(raise_dynamic_lds(reinterpret_cast<const void*>(k_si_ordered), lds));
@@ -357,27 +311,24 @@ int viorb_search_for_initialization(const viorb_keypoint* kps1, const uint8_t* d
     DeviceBufs B;
     const size_t c = (size_t)cap, m1 = (size_t)n1, m2 = (size_t)n2;
     viorb_keypoint* dk1 = B.up(kps1, m1, c); uint8_t* dd1 = B.up(desc1, m1 * 32, c * 32); int32_t* dn1 = B.up(&n1, 1);
-    viorb_s3m_keyframes kf;
-    kf.cap = cap; kf.kps = B.up(kps2, m2, c); kf.desc = B.up(desc2, m2 * 32, c * 32); kf.count = B.up(&n2, 1);
-    int32_t* cs = B.zeros<int32_t>(SI_GRID_CELLS + 1); int32_t* ci = B.zeros<int32_t>(c);
-    kf.cell_start = cs; kf.cell_idx = ci;
     float* dprev = B.up(prev_matched, m1 * 2, c * 2);
     int32_t *d12 = B.zeros<int32_t>(c), *dnm = B.zeros<int32_t>(1);
     viorb_search_init_outputs D;
-    D.matches21 = B.zeros<int32_t>(c); D.matched_distance = B.zeros<int32_t>(c); D.rot_hist = B.zeros<int32_t>(SI_HISTO); D.reason = B.zeros<int32_t>(c);
+    D.matches21 = B.zeros<int32_t>(c); D.matched_distance = B.zeros<int32_t>(c); D.rot_hist = B.zeros<int32_t>(HISTO_LENGTH); D.reason = B.zeros<int32_t>(c);
     D.xy1 = B.zeros<float>(c * 2); D.xy2 = B.zeros<float>(c * 2); D.sweeps = B.zeros<int32_t>(1);
     const size_t wb = viorb_search_init_workspace_bytes(cap, 1);
     unsigned char* dw = B.zeros<unsigned char>(wb);
     if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
-    VIORB_TRY(viorb_keyframe_grid_device(kf.kps, kf.count, cap, 1, bounds4, cs, ci, nullptr));
+    viorb_s3m_keyframes kf;
+    VIORB_TRY(host_keyframe(B, kps2, desc2, n2, cap, bounds4, kf));
     VIORB_TRY(viorb_search_for_initialization_device(dk1, dd1, dn1, &kf, dprev, cap, 1, bounds4, window_size, nnratio, check_orientation, d12, dnm, &D,
                                                      dw, wb, nullptr));
     VIORB_HIP_TRY(hipDeviceSynchronize());
-    VIORB_TRY(si_down(matches12, d12, m1)); VIORB_TRY(si_down(nmatches, dnm, 1)); VIORB_TRY(si_down(prev_matched, dprev, m1 * 2));
+    VIORB_TRY(download(matches12, d12, m1)); VIORB_TRY(download(nmatches, dnm, 1)); VIORB_TRY(download(prev_matched, dprev, m1 * 2));
     if (out) {
-        VIORB_TRY(si_down(out->matches21, D.matches21, m2)); VIORB_TRY(si_down(out->matched_distance, D.matched_distance, m2));
-        VIORB_TRY(si_down(out->rot_hist, D.rot_hist, (size_t)SI_HISTO)); VIORB_TRY(si_down(out->reason, D.reason, m1));
-        VIORB_TRY(si_down(out->xy1, D.xy1, m1 * 2)); VIORB_TRY(si_down(out->xy2, D.xy2, m2 * 2)); VIORB_TRY(si_down(out->sweeps, D.sweeps, 1));
+        VIORB_TRY(download(out->matches21, D.matches21, m2)); VIORB_TRY(download(out->matched_distance, D.matched_distance, m2));
+        VIORB_TRY(download(out->rot_hist, D.rot_hist, (size_t)HISTO_LENGTH)); VIORB_TRY(download(out->reason, D.reason, m1));
+        VIORB_TRY(download(out->xy1, D.xy1, m1 * 2)); VIORB_TRY(download(out->xy2, D.xy2, m2 * 2)); VIORB_TRY(download(out->sweeps, D.sweeps, 1));
     }
     return VIORB_OK;
 }
@@ -404,8 +355,8 @@ int viorb_scene_median_depth(const float pose12[12], const float* points, const 
     if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
     VIORB_TRY(viorb_scene_median_depth_device(dp, dx, dh, dn, (int)c, 1, q, dm, dc, nullptr));
     VIORB_HIP_TRY(hipDeviceSynchronize());
-    VIORB_TRY(si_down(median, dm, 1));
-    return si_down(n_depths, dc, 1);
+    VIORB_TRY(download(median, dm, 1));
+    return download(n_depths, dc, 1);
 }
 
 // ---- host-only test hooks: search_init_core.h compiled for the host --------------------------------------------------------------------
@@ -425,21 +376,14 @@ int viorb_debug_search_init_window(const viorb_keypoint* kps2, int n2, const int
                                    float x, float y, float r, int level1, int32_t* rect4, int32_t* out_idx) {
     VIORB_REQUIRE(n2 >= 0 && cell_start && bounds4 && rect4 && (n2 == 0 || (kps2 && cell_idx && out_idx)), "null array or a negative count");
     VIORB_REQUIRE(bounds4[1] > bounds4[0] && bounds4[3] > bounds4[2], "empty image bounds");
-    SiRect R;
-    si_window(si_cam(bounds4), x, y, r, R);
+    GridRect R;
+    grid_window(grid_cam(bounds4), x, y, r, R);
     rect4[0] = R.x0; rect4[1] = R.x1; rect4[2] = R.y0; rect4[3] = R.y1;
     int n = 0;
-    if (R.empty) return 0;
-    for (int ix = R.x0; ix <= R.x1; ix++) {
-        const int beg = std::min(std::max(cell_start[ix * SI_GRID_ROWS + R.y0], 0), n2);
-        const int end = std::min(std::max(cell_start[ix * SI_GRID_ROWS + R.y1 + 1], beg), n2);
-        for (int q = beg; q < end; q++) {
-            const int idx = cell_idx[q];
-            if (idx < 0 || idx >= n2) continue;
-            const viorb_keypoint& k = kps2[idx];
-            if (si_level_ok(level1, k.octave) && fabsf(k.x - x) < r && fabsf(k.y - y) < r) out_idx[n++] = idx;
-        }
-    }
+    grid_scan(R, cell_start, cell_idx, n2, n2, [&](int idx) {
+        const viorb_keypoint& k = kps2[idx];
+        if (si_level_ok(level1, k.octave) && fabsf(k.x - x) < r && fabsf(k.y - y) < r) out_idx[n++] = idx;
+    });
     return n;
 }
 

@@ -4,47 +4,20 @@
 // the address and undefined-behaviour sanitizers).
 //
 // What is restated (reference file:line):
-//   ORBmatcher::SearchForInitialization        src/ORBmatcher.cc:405-520  (inner loop :436-457, accept :459-471, bin :475-480)
-//   Frame::GetFeaturesInArea (cell rectangle)  src/Frame.cc:507-526
-//   ORBmatcher::ComputeThreeMaxima             src/ORBmatcher.cc:1602-1643
+//   ORBmatcher::SearchForInitialization        src/ORBmatcher.cc:405-520  (inner loop :436-457, accept :459-471)
 //   KeyFrame::ComputeSceneMedianDepth          src/KeyFrame.cc:970-1000
-// Everything is integer arithmetic, float compares and individually rounded float products; nothing depends on contraction.
+// The cell rectangle of GetFeaturesInArea, the rotation bin (:475-480) and ComputeThreeMaxima are match_core.h. Everything is integer arithmetic, float compares and individually rounded float products; nothing depends on contraction.
 #pragma once
 #include <limits.h>
+#include "match_core.h"             // the grid window, the descriptor distance, the rotation bin and the three maxima
 #include "two_view_core.h"          // tv_float_key / tv_key_float: the order-preserving float map of the radix select
 
 namespace viorb {
 
 // reason[i]: the statement of the reference that ended point i (VIORB_SI_* of include/viorb_search_init.h)
 enum { SI_MATCHED = 0, SI_NOT_CANDIDATE = 1, SI_NO_FEATURE_IN_WINDOW = 2, SI_ABOVE_THRESHOLD = 3, SI_RATIO = 4, SI_DISPLACED = 5, SI_ROTATION = 6 };
-enum { SI_GRID_COLS = 64, SI_GRID_ROWS = 48, SI_GRID_CELLS = SI_GRID_COLS * SI_GRID_ROWS, SI_TH_LOW = 50, SI_HISTO = 30 };
 // the state of a point in the ordered phase: distance << 16 | feature when the point is accepted (:461), SI_NONE otherwise
 static const uint32_t SI_NONE = 0xffffffffu;
-
-struct SiCam { float minX, maxX, minY, maxY, wInv, hInv; };
-// nMinCellX nMaxCellX nMinCellY nMaxCellY; empty: one of the four early returns fired
-struct SiRect { int x0, x1, y0, y1; bool empty; };
-
-// (int) of a float as x86 converts it: a value no int holds gives INT_MIN (a prev_matched far outside the image)
-MAP_HD int si_to_int(float q) { return (q > -2147483648.0f && q < 2147483648.0f) ? (int)q : INT_MIN; }
-
-// Frame::GetFeaturesInArea :512-526: the float expressions, floor / ceil, the clamps and the early returns in the reference's order
-MAP_HD void si_window(const SiCam& C, float x, float y, float r, SiRect& R) {
-    R.x0 = R.y0 = 0; R.x1 = R.y1 = -1; R.empty = true;
-    const int a = si_to_int(floorf((x - C.minX - r) * C.wInv));
-    R.x0 = a < 0 ? 0 : a;
-    if (R.x0 >= SI_GRID_COLS) return;
-    const int b = si_to_int(ceilf((x - C.minX + r) * C.wInv));
-    R.x1 = b > SI_GRID_COLS - 1 ? SI_GRID_COLS - 1 : b;
-    if (R.x1 < 0) return;
-    const int c = si_to_int(floorf((y - C.minY - r) * C.hInv));
-    R.y0 = c < 0 ? 0 : c;
-    if (R.y0 >= SI_GRID_ROWS) return;
-    const int d = si_to_int(ceilf((y - C.minY + r) * C.hInv));
-    R.y1 = d > SI_GRID_ROWS - 1 ? SI_GRID_ROWS - 1 : d;
-    if (R.y1 < 0) return;
-    R.empty = false;
-}
 
 // The level filter of GetFeaturesInArea(x, y, r, level1, level1) for a point that passed :422 (level1 <= 0): bCheckLevels is
 // (level1 > 0) || (level1 >= 0), so level 0 admits level-0 features only and a negative level (no extractor produces one) admits all.
@@ -54,7 +27,7 @@ MAP_HD bool si_level_ok(int level1, int octave2) { return level1 < 0 || octave2 
 // as second best it passes the ratio test of every best <= TH_LOW ((float)d * ratio > TH_LOW >= best), exactly as the larger second best
 // or the INT_MAX that takes its place does ((float)d' * ratio >= (float)d * ratio for d' >= d and ratio > 0: float products are monotone).
 // When it would be the best, the point ends above the threshold with or without it.
-MAP_HD bool si_keep(int d, float nnratio) { return d <= SI_TH_LOW || !((float)d * nnratio > (float)SI_TH_LOW); }
+MAP_HD bool si_keep(int d, float nnratio) { return d <= TH_LOW || !((float)d * nnratio > (float)TH_LOW); }
 
 // The inner loop :436-457 over the candidates one at a time, in visiting order; seen = vMatchedDistance[i2] as this point sees it.
 struct SiPick { int best, dist, dist2; };
@@ -66,7 +39,7 @@ MAP_HD void si_pick_visit(SiPick& P, int d, int f, int seen) {
 }
 // :459-461. The state word of the point, and why it is not accepted.
 MAP_HD uint32_t si_decide(const SiPick& P, float nnratio, int& why) {
-    if (!(P.dist <= SI_TH_LOW)) { why = SI_ABOVE_THRESHOLD; return SI_NONE; }
+    if (!(P.dist <= TH_LOW)) { why = SI_ABOVE_THRESHOLD; return SI_NONE; }
     if (!((float)P.dist < (float)P.dist2 * nnratio)) { why = SI_RATIO; return SI_NONE; }
     why = SI_MATCHED;
     return ((uint32_t)P.dist << 16) | (uint32_t)P.best;
@@ -78,30 +51,6 @@ MAP_HD int si_seen(const int* head, const int* next, const uint32_t* st, int f, 
     int bq = -1;
     for (int q = head[f]; q >= 0; q = next[q]) if (q < p && q > bq) bq = q;
     return bq < 0 ? INT_MAX : (int)(st[bq] >> 16);
-}
-
-// :475-480: rot in float, + 360 when negative, round half away from zero of rot * (1.0f / 30), 30 wraps to 0
-MAP_HD int si_rot_bin(float angle1, float angle2) {
-    const float factor = 1.0f / SI_HISTO;
-    float rot = angle1 - angle2;
-    if (rot < 0.0f) rot += 360.0f;
-    const float b = roundf(rot * factor);
-    // 30 wraps to 0; the reference asserts the range (angles are in [0, 360)), a value outside it (a NaN angle) goes to bin 0 here
-    return (b >= 0.0f && b < (float)SI_HISTO) ? (int)b : 0;
-}
-
-// ComputeThreeMaxima (:1602-1643) over the bins' sizes: keep[i] = bin i is one of ind1 ind2 ind3
-MAP_HD void si_three_maxima(const int* hist, int* keep) {
-    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-    for (int i = 0; i < SI_HISTO; i++) {
-        const int sz = hist[i];
-        if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
-        else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
-        else if (sz > max3) { max3 = sz; ind3 = i; }
-    }
-    if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-    else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-    for (int i = 0; i < SI_HISTO; i++) keep[i] = (i == ind1 || i == ind2 || i == ind3);
 }
 
 // The ordered phase (:418-487) as a fixed-point iteration. st[p] is point p's state; a sweep evaluates every point against the states of

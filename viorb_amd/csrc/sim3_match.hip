@@ -20,40 +20,15 @@ enum { S3M_BLOCK = 256, S3M_WAVE = 64, S3M_LIST = 8, S3M_CLAIM_THREADS = 1024 };
 
 struct S3mKf { const viorb_keypoint* kps; const uint8_t* desc; const int* count; const int* cell_start; const int* cell_idx; int cap; };
 
-__device__ __forceinline__ int s3m_hamming(const uint4 da, const uint4 db, const uint8_t* row) {
-    const uint4* dc = reinterpret_cast<const uint4*>(row);
-    const uint4 ea = dc[0], eb = dc[1];
-    return __popc(da.x ^ ea.x) + __popc(da.y ^ ea.y) + __popc(da.z ^ ea.z) + __popc(da.w ^ ea.w) + __popc(db.x ^ eb.x) + __popc(db.y ^ eb.y) +
-           __popc(db.z ^ eb.z) + __popc(db.w ^ eb.w);
-}
-
-// KeyFrame::GetFeaturesInArea (src/KeyFrame.cc:927-942) over the CSR grid: visit(idx, octave) for every feature of the cell rectangle
-// with |dx| < r and |dy| < r, in the reference's order (ix outer, iy inner, insertion order inside a cell; the cells of one column are
-// adjacent in storage order ix*48 + iy).
+// KeyFrame::GetFeaturesInArea (src/KeyFrame.cc:927-942) over the CSR grid of a key frame with n features in arrays of cap: visit(idx, octave)
+// for every feature of the cell rectangle with |dx| < r and |dy| < r, in the reference's order (grid_scan).
 template <class Visit>
 __device__ __forceinline__ void s3m_scan(const S3mProj& P, const viorb_keypoint* __restrict__ kp, const int* __restrict__ cs, const int* __restrict__ ci,
-                                         Visit&& visit) {
-    for (int ix = P.x0; ix <= P.x1; ix++) {
-        const int pbeg = cs[ix * S3M_GRID_ROWS + P.y0], pend = cs[ix * S3M_GRID_ROWS + P.y1 + 1];
-        for (int q = pbeg; q < pend; q++) {
-            const int idx = ci[q];
-            const viorb_keypoint k = kp[idx];
-            if (!(fabsf(k.x - P.u) < P.radius && fabsf(k.y - P.v) < P.radius)) continue;
-            visit(idx, k.octave);
-        }
-    }
-}
-
-// The workgroup's count of `flag`, returned to every thread: the wavefronts' ballots, one LDS word per wavefront. Every thread calls it.
-__device__ __forceinline__ int s3m_block_count(bool flag, int* s_part) {
-    const int lane = threadIdx.x & (S3M_WAVE - 1), w = threadIdx.x / S3M_WAVE, nw = (blockDim.x + S3M_WAVE - 1) / S3M_WAVE;
-    const int c = __popcll(__ballot(flag));
-    if (lane == 0) s_part[w] = c;
-    __syncthreads();
-    int total = 0;
-    for (int k = 0; k < nw; k++) total += s_part[k];
-    __syncthreads();
-    return total;
+                                         int n, int cap, Visit&& visit) {
+    grid_scan(P.rect, cs, ci, n, cap, [&](int idx) {
+        const viorb_keypoint k = kp[idx];
+        if (fabsf(k.x - P.u) < P.radius && fabsf(k.y - P.v) < P.radius) visit(idx, k.octave);
+    });
 }
 
 // ---- SearchBySim3 ----------------------------------------------------------------------------------------------------------------------
@@ -91,14 +66,14 @@ __global__ __launch_bounds__(S3M_BLOCK) void k_s3m_oneway(S3mOnewayArgs A) {
             int best_dist = INT_MAX;
             bool any = false;
             const int lvl = P.level;
-            s3m_scan(P, oth.kf.kps + (size_t)b * oth.kf.cap, oth.kf.cell_start + (size_t)b * (S3M_GRID_CELLS + 1), oth.kf.cell_idx + (size_t)b * oth.kf.cap,
-                     [&](int idx, int octave) {
+            s3m_scan(P, oth.kf.kps + (size_t)b * oth.kf.cap, oth.kf.cell_start + (size_t)b * (GRID_CELLS + 1), oth.kf.cell_idx + (size_t)b * oth.kf.cap,
+                     n_oth, oth.kf.cap, [&](int idx, int octave) {
                          any = true;
                          if (octave < lvl - 1 || octave > lvl) return;
-                         const int dist = s3m_hamming(da, db, desc + (size_t)idx * 32);
+                         const int dist = desc_distance(da, db, desc + (size_t)idx * 32);
                          if (dist < best_dist) { best_dist = dist; best = idx; }
                      });
-            if (best_dist > S3M_TH_HIGH) best = -1;
+            if (best_dist > TH_HIGH) best = -1;
             reason = !any ? S3M_NO_FEATURE_IN_WINDOW : (best >= 0 ? S3M_MATCHED : S3M_ABOVE_THRESHOLD);
         }
     }
@@ -123,7 +98,7 @@ __global__ __launch_bounds__(S3M_CLAIM_THREADS) void k_s3m_mutual(S3mMutualArgs 
             A.match12[(size_t)b * A.cap1 + i1] = hit ? idx2 : -1;
             if (A.reason1 && idx2 >= 0 && !hit) A.reason1[(size_t)b * A.cap1 + i1] = S3M_NOT_MUTUAL;
         }
-        found += s3m_block_count(hit, s_part);
+        found += block_count(hit, s_part);
     }
     if (A.reason2)
         for (int i2 = threadIdx.x; i2 < A.cap2; i2 += blockDim.x) {
@@ -176,19 +151,19 @@ __global__ __launch_bounds__(S3M_BLOCK) void k_s3m_scw(S3mScwArgs A) {
             int best_dist = 256;
             bool any = false;
             const int lvl = P.level;
-            s3m_scan(P, A.kf.kps + (size_t)b * cap, A.kf.cell_start + (size_t)b * (S3M_GRID_CELLS + 1), A.kf.cell_idx + (size_t)b * cap,
-                     [&](int idx, int octave) {
+            s3m_scan(P, A.kf.kps + (size_t)b * cap, A.kf.cell_start + (size_t)b * (GRID_CELLS + 1), A.kf.cell_idx + (size_t)b * cap,
+                     n, cap, [&](int idx, int octave) {
                          any = true;
                          if (ORDERED && taken[idx]) return;
                          if (octave < lvl - 1 || octave > lvl) return;
-                         const int dist = s3m_hamming(da, db, desc + (size_t)idx * 32);
-                         if (ORDERED && dist <= S3M_TH_LOW) {
+                         const int dist = desc_distance(da, db, desc + (size_t)idx * 32);
+                         if (ORDERED && dist <= TH_LOW) {
                              if (ncand < S3M_LIST) list[(size_t)ncand * pcap] = ((uint32_t)dist << 16) | (uint32_t)idx;
                              ncand++;
                          }
                          if (dist < best_dist) { best_dist = dist; best = idx; }
                      });
-            if (best_dist > S3M_TH_LOW) best = -1;
+            if (best_dist > TH_LOW) best = -1;
             reason = !any ? S3M_NO_FEATURE_IN_WINDOW : (best >= 0 && !ORDERED ? S3M_MATCHED : S3M_ABOVE_THRESHOLD);
         }
     }
@@ -197,7 +172,7 @@ __global__ __launch_bounds__(S3M_BLOCK) void k_s3m_scw(S3mScwArgs A) {
         if (A.reason) A.reason[o] = reason;
     }
     if (!ORDERED) {
-        const int total = s3m_block_count(best >= 0, s_part);
+        const int total = block_count(best >= 0, s_part);
         if (threadIdx.x == 0) A.partial[(size_t)b * gridDim.x + blockIdx.x] = total;
     }
 }
@@ -253,14 +228,14 @@ __global__ __launch_bounds__(S3M_CLAIM_THREADS) void k_s3m_claim(S3mScwArgs A) {
                 int best_dist = 256;
                 c = -1;
                 const int lvl = P.level;
-                s3m_scan(P, A.kf.kps + (size_t)b * cap, A.kf.cell_start + (size_t)b * (S3M_GRID_CELLS + 1), A.kf.cell_idx + (size_t)b * cap,
-                         [&](int idx, int octave) {
+                s3m_scan(P, A.kf.kps + (size_t)b * cap, A.kf.cell_start + (size_t)b * (GRID_CELLS + 1), A.kf.cell_idx + (size_t)b * cap,
+                         n, cap, [&](int idx, int octave) {
                              if (taken[idx] || s_owner[idx] < p) return;
                              if (octave < lvl - 1 || octave > lvl) return;
-                             const int dist = s3m_hamming(da, db, desc + (size_t)idx * 32);
+                             const int dist = desc_distance(da, db, desc + (size_t)idx * 32);
                              if (dist < best_dist) { best_dist = dist; c = idx; }
                          });
-                if (best_dist > S3M_TH_LOW) c = -1;
+                if (best_dist > TH_LOW) c = -1;
             }
             if (c != choice[p]) { choice[p] = c; changed = 1; }
         }
@@ -271,7 +246,7 @@ __global__ __launch_bounds__(S3M_CLAIM_THREADS) void k_s3m_claim(S3mScwArgs A) {
         const int p = base + threadIdx.x;
         const bool hit = p < npts && choice[p] >= 0;
         if (hit && A.reason) A.reason[(size_t)b * pcap + p] = S3M_MATCHED;
-        found += s3m_block_count(hit, s_part);
+        found += block_count(hit, s_part);
     }
     if (threadIdx.x == 0) A.nmatches[b] = found;
 }
@@ -301,9 +276,7 @@ int s3m_check_cam(const viorb_mapping_camera* cam, const float* bounds4, float t
     VIORB_REQUIRE(cam->nlevels >= 1 && cam->nlevels <= 16, "nlevels must be 1..16");
     VIORB_REQUIRE(bounds4[1] > bounds4[0] && bounds4[3] > bounds4[2], "empty image bounds");
     C.fx = cam->fx; C.fy = cam->fy; C.cx = cam->cx; C.cy = cam->cy;
-    C.minX = bounds4[0]; C.maxX = bounds4[1]; C.minY = bounds4[2]; C.maxY = bounds4[3];
-    C.wInv = static_cast<float>(S3M_GRID_COLS) / static_cast<float>(C.maxX - C.minX);       // Frame.cc:184-185
-    C.hInv = static_cast<float>(S3M_GRID_ROWS) / static_cast<float>(C.maxY - C.minY);
+    C.g = grid_cam(bounds4);
     C.th = th; C.nlevels = cam->nlevels;
     C.log_sf = (float)log((double)cam->scale_factors[cam->nlevels > 1 ? 1 : 0]);
     for (int i = 0; i < 16; i++) C.scale[i] = cam->scale_factors[i < cam->nlevels ? i : cam->nlevels - 1];
@@ -335,22 +308,6 @@ S3mSideDev s3m_side(const viorb_s3m_side& s) {
     return d;
 }
 
-// the device side of a host-form key frame: arrays of max(n, 1) entries and its grid
-int s3m_host_kf(DeviceBufs& B, const viorb_keypoint* kps, const uint8_t* desc, int n, const float* bounds4, viorb_s3m_keyframes& kf) {
-    const size_t c = (size_t)std::max(n, 1);
-    kf.cap = (int)c;
-    kf.kps = B.up(kps, (size_t)n, c); kf.desc = B.up(desc, (size_t)n * 32, c * 32); kf.count = B.up(&n, 1);
-    int32_t* cs = B.zeros<int32_t>(S3M_GRID_CELLS + 1); int32_t* ci = B.zeros<int32_t>(c);
-    kf.cell_start = cs; kf.cell_idx = ci;
-    if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
-    return viorb_keyframe_grid_device(kf.kps, kf.count, kf.cap, 1, bounds4, cs, ci, nullptr);
-}
-
-template <class T> int s3m_down(T* host, const T* dev, size_t n) {
-    if (host && n) VIORB_HIP_TRY(hipMemcpy(host, dev, sizeof(T) * n, hipMemcpyDeviceToHost));
-    return VIORB_OK;
-}
-
 } // namespace
 
 extern "C" {
@@ -373,10 +330,10 @@ int viorb_keyframe_grid(const viorb_keypoint* kps, int n, const float bounds4[4]
     if (n > VIORB_S3M_MAX_FEATURES) { set_error("n %d above VIORB_S3M_MAX_FEATURES", n); return VIORB_ERR_CAPACITY; }
     VIORB_TRY(require_device());
     DeviceBufs B; viorb_s3m_keyframes kf;
-    VIORB_TRY(s3m_host_kf(B, kps, nullptr, n, bounds4, kf));         // the grid reads no descriptors
+    VIORB_TRY(host_keyframe(B, kps, nullptr, n, std::max(n, 1), bounds4, kf));         // the grid reads no descriptors
     VIORB_HIP_TRY(hipDeviceSynchronize());
-    VIORB_TRY(s3m_down(cell_start, kf.cell_start, (size_t)S3M_GRID_CELLS + 1));
-    return s3m_down(cell_idx, kf.cell_idx, (size_t)kf.cap);
+    VIORB_TRY(download(cell_start, kf.cell_start, (size_t)GRID_CELLS + 1));
+    return download(cell_idx, kf.cell_idx, (size_t)kf.cap);
 }
 
 int viorb_search_by_sim3_device(const viorb_s3m_side* side1, const viorb_s3m_side* side2, const float* R12, const float* t12, const float* s12,
@@ -420,7 +377,7 @@ int viorb_search_by_sim3(const viorb_keypoint* kps1, const uint8_t* desc1, int n
     const float* pose[2] = {pose12_1, pose12_2}; const uint8_t* hp[2] = {has_point1, has_point2}; const float* pf[2] = {pts_f1, pts_f2};
     const uint8_t* pd[2] = {pts_desc1, pts_desc2}; const uint8_t* al[2] = {already1, already2};
     for (int k = 0; k < 2; k++) {
-        VIORB_TRY(s3m_host_kf(B, kps[k], desc[k], n[k], bounds4, S[k].kf));
+        VIORB_TRY(host_keyframe(B, kps[k], desc[k], n[k], std::max(n[k], 1), bounds4, S[k].kf));
         const size_t c = (size_t)S[k].kf.cap, m = (size_t)n[k];
         S[k].pose12 = B.up(pose[k], 12); S[k].has_point = B.up(hp[k], m, c); S[k].pts_f = B.up(pf[k], m * 8, c * 8);
         S[k].pts_desc = B.up(pd[k], m * 32, c * 32); S[k].already = B.up(al[k], m, c);
@@ -434,9 +391,9 @@ int viorb_search_by_sim3(const viorb_keypoint* kps1, const uint8_t* desc1, int n
     if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
     VIORB_TRY(viorb_search_by_sim3_device(&S[0], &S[1], dR, dt, ds, cam, bounds4, th, 1, d12, dnf, dm1, dm2, dr1, dr2, dw, wb, nullptr));
     VIORB_HIP_TRY(hipDeviceSynchronize());
-    VIORB_TRY(s3m_down(match12, d12, (size_t)n1)); VIORB_TRY(s3m_down(nfound, dnf, 1)); VIORB_TRY(s3m_down(match1, dm1, (size_t)n1));
-    VIORB_TRY(s3m_down(match2, dm2, (size_t)n2)); VIORB_TRY(s3m_down(reason1, dr1, (size_t)n1));
-    return s3m_down(reason2, dr2, (size_t)n2);
+    VIORB_TRY(download(match12, d12, (size_t)n1)); VIORB_TRY(download(nfound, dnf, 1)); VIORB_TRY(download(match1, dm1, (size_t)n1));
+    VIORB_TRY(download(match2, dm2, (size_t)n2)); VIORB_TRY(download(reason1, dr1, (size_t)n1));
+    return download(reason2, dr2, (size_t)n2);
 }
 
 int viorb_search_by_projection_sim3_device(const viorb_s3m_keyframes* kf, const float* Scw, const float* pts_f, const uint8_t* pts_desc,
@@ -473,7 +430,7 @@ int viorb_search_by_projection_sim3(const viorb_keypoint* kps, const uint8_t* de
     if (n > VIORB_S3M_MAX_FEATURES) { set_error("n %d above VIORB_S3M_MAX_FEATURES", n); return VIORB_ERR_CAPACITY; }
     VIORB_TRY(require_device());
     DeviceBufs B; viorb_s3m_keyframes kf;
-    VIORB_TRY(s3m_host_kf(B, kps, desc, n, bounds4, kf));
+    VIORB_TRY(host_keyframe(B, kps, desc, n, std::max(n, 1), bounds4, kf));
     const size_t pc = (size_t)std::max(npts, 1), m = (size_t)npts;
     float *dS = B.up(Scw, 12), *dpf = B.up(pts_f, m * 8, pc * 8);
     uint8_t *dpd = B.up(pts_desc, m * 32, pc * 32), *dpv = B.up(pts_valid, m, pc), *dft = B.up(feat_taken, (size_t)n, (size_t)kf.cap);
@@ -483,8 +440,8 @@ int viorb_search_by_projection_sim3(const viorb_keypoint* kps, const uint8_t* de
     if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
     VIORB_TRY(viorb_search_by_projection_sim3_device(&kf, dS, dpf, dpd, dpv, dpc, (int)pc, dft, cam, bounds4, th, 1, dbi, dnm, dre, dw, wb, nullptr));
     VIORB_HIP_TRY(hipDeviceSynchronize());
-    VIORB_TRY(s3m_down(best_idx, dbi, m)); VIORB_TRY(s3m_down(nmatches, dnm, 1));
-    return s3m_down(reason, dre, m);
+    VIORB_TRY(download(best_idx, dbi, m)); VIORB_TRY(download(nmatches, dnm, 1));
+    return download(reason, dre, m);
 }
 
 int viorb_fuse_sim3_device(const viorb_s3m_keyframes* kf, const float* Scw, const float* pts_f, const uint8_t* pts_desc, const uint8_t* pts_valid,
@@ -518,7 +475,7 @@ int viorb_fuse_sim3(const viorb_keypoint* kps, const uint8_t* desc, int n, const
     if (n > VIORB_S3M_MAX_FEATURES) { set_error("n %d above VIORB_S3M_MAX_FEATURES", n); return VIORB_ERR_CAPACITY; }
     VIORB_TRY(require_device());
     DeviceBufs B; viorb_s3m_keyframes kf;
-    VIORB_TRY(s3m_host_kf(B, kps, desc, n, bounds4, kf));
+    VIORB_TRY(host_keyframe(B, kps, desc, n, std::max(n, 1), bounds4, kf));
     const size_t pc = (size_t)std::max(npts, 1), m = (size_t)npts;
     float *dS = B.up(Scw, 12), *dpf = B.up(pts_f, m * 8, pc * 8);
     uint8_t *dpd = B.up(pts_desc, m * 32, pc * 32), *dpv = B.up(pts_valid, m, pc);
@@ -528,8 +485,8 @@ int viorb_fuse_sim3(const viorb_keypoint* kps, const uint8_t* desc, int n, const
     if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
     VIORB_TRY(viorb_fuse_sim3_device(&kf, dS, dpf, dpd, dpv, npts, (int)pc, cam, bounds4, th, 1, dbi, dnf, dre, dw, wb, nullptr));
     VIORB_HIP_TRY(hipDeviceSynchronize());
-    VIORB_TRY(s3m_down(best_idx, dbi, m)); VIORB_TRY(s3m_down(nfused, dnf, 1));
-    return s3m_down(reason, dre, m);
+    VIORB_TRY(download(best_idx, dbi, m)); VIORB_TRY(download(nfused, dnf, 1));
+    return download(reason, dre, m);
 }
 
 // ---- host-only test hooks: sim3_match_core.h compiled for the host ---------------------------------------------------------------------
@@ -562,7 +519,7 @@ int viorb_debug_sim3_project(int which, const float* T12, const float* sR9, cons
     if (which == S3M_FN_SEARCH_BY_SIM3) s3m_project_pair(C, T12, sR9, t3, pt8, P);
     else { S3mScw D; s3m_decompose(T12, D); s3m_project_scw(C, D, pt8, P); }
     out4[0] = P.u; out4[1] = P.v; out4[2] = P.dist3D; out4[3] = P.radius;
-    out6[0] = P.level; out6[1] = P.x0; out6[2] = P.x1; out6[3] = P.y0; out6[4] = P.y1; out6[5] = P.reason;
+    out6[0] = P.level; out6[1] = P.rect.x0; out6[2] = P.rect.x1; out6[3] = P.rect.y0; out6[4] = P.rect.y1; out6[5] = P.reason;
     return VIORB_OK;
 }
 

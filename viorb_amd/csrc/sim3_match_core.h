@@ -6,26 +6,27 @@
 //   ORBmatcher::SearchByProjection(KeyFrame*, Scw, ...)   src/ORBmatcher.cc:290-403   (decomposition :298-303, gates :320-365, claim :370-398)
 //   ORBmatcher::Fuse(KeyFrame*, Scw, ...)                  src/ORBmatcher.cc:977-1100  (decomposition :985-990, gates :1008-1054)
 //   ORBmatcher::SearchBySim3                               src/ORBmatcher.cc:1102-1326 (transforms :1119-1121, gates :1158-1194 and :1238-1274)
-//   KeyFrame::GetFeaturesInArea (the cell rectangle)       src/KeyFrame.cc:906-925
 //   KeyFrame::IsInImage, MapPoint::PredictScale            src/KeyFrame.cc:947-950, src/MapPoint.cc (ceil(log(max / dist) / log(factor)), clamped)
-// Float / double placement is the audit table of DESIGN.md §2 ("Sim3 matchers"). PredictScale, the cell rectangle and the level window are
-// restated from k_fuse (frontend_kernels.hip), which stays as it is. Nothing here depends on contraction (-ffp-contract=off).
+// Float / double placement is the audit table of DESIGN.md §2 ("Sim3 matchers"). The cell rectangle of KeyFrame::GetFeaturesInArea, the
+// guarded float-to-int conversion and the thresholds are match_core.h; k_fuse (frontend_kernels.hip) predicts its level with
+// s3m_predict_level too. Nothing here depends on contraction (-ffp-contract=off).
 #pragma once
 #include <limits.h>
-#include "orb_math.h"
+#include "match_core.h"
 
 namespace viorb {
 
 // reason[i]: which statement of the reference ended the point (VIORB_S3M_* of include/viorb_sim3_match.h)
 enum { S3M_MATCHED = 0, S3M_NOT_CANDIDATE = 1, S3M_BEHIND = 2, S3M_OUT_OF_IMAGE = 3, S3M_OUT_OF_RANGE = 4, S3M_VIEW_ANGLE = 5,
        S3M_NO_FEATURE_IN_WINDOW = 6, S3M_ABOVE_THRESHOLD = 7, S3M_NOT_MUTUAL = 8 };
-enum { S3M_GRID_COLS = 64, S3M_GRID_ROWS = 48, S3M_GRID_CELLS = S3M_GRID_COLS * S3M_GRID_ROWS, S3M_TH_LOW = 50, S3M_TH_HIGH = 100 };
 // which function a projection belongs to (viorb_debug_sim3_project)
 enum { S3M_FN_SEARCH_BY_SIM3 = 0, S3M_FN_SEARCH_BY_PROJECTION = 1, S3M_FN_FUSE = 2 };
 
 // The camera, the image bounds and the search radius of one call. log_sf = (float)log((double)mfScaleFactor), taken on the host.
 struct S3mCam {
-    float fx, fy, cx, cy, minX, maxX, minY, maxY, wInv, hInv, th, log_sf;
+    float fx, fy, cx, cy;
+    GridCam g;
+    float th, log_sf;
     int nlevels;
     float scale[16];
 };
@@ -38,8 +39,8 @@ struct S3mScw { float scw, R[9], t[3], Ow[3]; };
 struct S3mPair { float sR12[9], sR21[9], t21[3]; };
 
 // One point after the gates: reason is the gate that ended it, or S3M_MATCHED when it reaches the window scan; the cell rectangle is
-// GetFeaturesInArea's (x0 <= x1 and y0 <= y1 whenever reason == S3M_MATCHED).
-struct S3mProj { float u, v, dist3D, radius; int level, x0, x1, y0, y1, reason; };
+// GetFeaturesInArea's (not empty whenever reason == S3M_MATCHED).
+struct S3mProj { float u, v, dist3D, radius; int level, reason; GridRect rect; };
 
 // M X of a row-major 3 x 3 in float: (m0 x0 + m1 x1) + m2 x2, the small-matrix gemm association
 VIORB_HD void s3m_mul3(const float* M, const float* X, float* out) {
@@ -79,41 +80,36 @@ VIORB_HD void s3m_pair(const float* R12, const float* t12, float s12, S3mPair& T
 VIORB_HD float s3m_norm3(float a, float b, float c) { return (float)sqrt(((double)a * a + (double)b * b) + (double)c * c); }
 
 // MapPoint::PredictScale: ratio = mfMaxDistance / dist in float, ceil(log(ratio) / mfLogScaleFactor) converted to int, clamped into
-// 0..nlevels-1. A quotient no int holds (non-finite: dist == 0, or a scale factor of 1 whose logarithm is 0) is converted as x86 converts
-// it, to INT_MIN, and so clamps to level 0 on the host and on the device alike.
-VIORB_HD int s3m_predict_level(float max_distance, float dist, const S3mCam& C) {
+// 0..nlevels-1. A quotient no int holds (non-finite: dist == 0, or a scale factor of 1 whose logarithm is 0) goes through float_to_int
+// and so clamps to level 0 on the host and on the device alike.
+VIORB_HD int s3m_predict_level(float max_distance, float dist, float log_sf, int nlevels) {
     const float ratio = max_distance / dist;
-    const float q = ceilf(viorb_logf(ratio) / C.log_sf);
-    int lvl = (q > -2147483648.0f && q < 2147483648.0f) ? (int)q : INT_MIN;
-    lvl = lvl < 0 ? 0 : (lvl >= C.nlevels ? C.nlevels - 1 : lvl);
-    return lvl;
+    const int lvl = float_to_int(ceilf(viorb_logf(ratio) / log_sf));
+    return lvl < 0 ? 0 : (lvl >= nlevels ? nlevels - 1 : lvl);
 }
 
 // From the point in the camera frame to the window: depth (rejected on z < 0, so z == 0 goes on with an infinite invz and fails the image
 // gate), projection, IsInImage, the 0.8 / 1.2 distance gate, with VIEW the viewing-angle gate PO . Pn < 0.5 dist (the dot in double, as
 // Mat::dot), PredictScale, radius = th * scale[level], the cell rectangle. X = pts_f[8]; PO is read with VIEW only.
 template <bool VIEW> VIORB_HD void s3m_gates(const S3mCam& C, const float* pc, float dist3D, const float* X, const float* PO, S3mProj& P) {
-    P.u = P.v = P.radius = 0.0f; P.dist3D = dist3D; P.level = 0; P.x0 = P.y0 = 0; P.x1 = P.y1 = -1;
+    P.u = P.v = P.radius = 0.0f; P.dist3D = dist3D; P.level = 0; P.rect.x0 = P.rect.y0 = 0; P.rect.x1 = P.rect.y1 = -1; P.rect.empty = true;
     if (pc[2] < 0.0f) { P.reason = S3M_BEHIND; return; }
     const float invz = 1.0f / pc[2];                         // 1.0 / z in double rounded to float is the float quotient
     const float x = pc[0] * invz, y = pc[1] * invz;
     const float u = C.fx * x + C.cx, v = C.fy * y + C.cy;
     P.u = u; P.v = v;
-    if (!(u >= C.minX && u < C.maxX && v >= C.minY && v < C.maxY)) { P.reason = S3M_OUT_OF_IMAGE; return; }
+    if (!(u >= C.g.minX && u < C.g.maxX && v >= C.g.minY && v < C.g.maxY)) { P.reason = S3M_OUT_OF_IMAGE; return; }
     const float maxD = 1.2f * X[7], minD = 0.8f * X[6];
     if (dist3D < minD || dist3D > maxD) { P.reason = S3M_OUT_OF_RANGE; return; }
     if (VIEW) {
         const double dotp = ((double)PO[0] * X[3] + (double)PO[1] * X[4]) + (double)PO[2] * X[5];
         if (dotp < 0.5 * (double)dist3D) { P.reason = S3M_VIEW_ANGLE; return; }
     }
-    const int lvl = s3m_predict_level(X[7], dist3D, C);
+    const int lvl = s3m_predict_level(X[7], dist3D, C.log_sf, C.nlevels);
     const float radius = C.th * C.scale[lvl];
     P.level = lvl; P.radius = radius;
-    P.x0 = (int)floorf((u - C.minX - radius) * C.wInv); P.x0 = P.x0 < 0 ? 0 : P.x0;
-    P.x1 = (int)ceilf((u - C.minX + radius) * C.wInv); P.x1 = P.x1 > S3M_GRID_COLS - 1 ? S3M_GRID_COLS - 1 : P.x1;
-    P.y0 = (int)floorf((v - C.minY - radius) * C.hInv); P.y0 = P.y0 < 0 ? 0 : P.y0;
-    P.y1 = (int)ceilf((v - C.minY + radius) * C.hInv); P.y1 = P.y1 > S3M_GRID_ROWS - 1 ? S3M_GRID_ROWS - 1 : P.y1;
-    P.reason = (P.x0 >= S3M_GRID_COLS || P.x1 < 0 || P.y0 >= S3M_GRID_ROWS || P.y1 < 0) ? S3M_NO_FEATURE_IN_WINDOW : S3M_MATCHED;
+    grid_window(C.g, u, v, radius, P.rect);
+    P.reason = P.rect.empty ? S3M_NO_FEATURE_IN_WINDOW : S3M_MATCHED;
 }
 
 // SearchByProjection(KF, Scw) and Fuse(KF, Scw): p3Dc = Rcw Pw + tcw, dist = |Pw - Ow|
@@ -146,7 +142,7 @@ template <class Free> VIORB_HD int s3m_pick(const uint32_t* list, int n, size_t 
         const int idx = (int)(e & 0xffffu), d = (int)(e >> 16);
         if (d < best_dist && is_free(idx)) { best_dist = d; best = idx; }
     }
-    return best_dist <= S3M_TH_LOW ? best : -1;
+    return best_dist <= TH_LOW ? best : -1;
 }
 
 // The point-order loop as a fixed-point iteration: choice[p] = s3m_pick over the features no earlier point chose in the previous sweep.

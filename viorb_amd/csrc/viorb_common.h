@@ -81,6 +81,9 @@ struct StreamCtxLease {
     bool ready();                       // a free context of the calling thread's current device, or a new one
 };
 
+// The device side of a host-form key frame: its arrays with `cap` >= max(n, 1) entries and its grid (viorb_keyframe_grid_device).
+int host_keyframe(DeviceBufs& B, const viorb_keypoint* kps, const uint8_t* desc, int n, int cap, const float* bounds4, viorb_s3m_keyframes& kf);
+
 } // namespace viorb
 
 #define VIORB_HIP_TRY(expr)                                                                   \
@@ -113,3 +116,13 @@ struct StreamCtxLease {
         }                                                                                     \
         VIORB_HIP_TRY(hipGetLastError());                                                     \
     } while (0)
+
+namespace viorb {
+
+// n elements of a device array to the host form's output; a NULL output or n == 0 copies nothing
+template <class T> int download(T* host, const T* dev, size_t n) {
+    if (host && n) VIORB_HIP_TRY(hipMemcpy(host, dev, sizeof(T) * n, hipMemcpyDeviceToHost));
+    return VIORB_OK;
+}
+
+} // namespace viorb

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 #include "viorb_common.h"
+#include "match_core.h"             // GRID_CELLS
 
 namespace viorb {
 
@@ -102,6 +103,16 @@ bool StreamCtxLease::ready() {
         }
     }
     return true;
+}
+
+int host_keyframe(DeviceBufs& B, const viorb_keypoint* kps, const uint8_t* desc, int n, int cap, const float* bounds4, viorb_s3m_keyframes& kf) {
+    const size_t c = (size_t)cap;
+    kf.cap = cap;
+    kf.kps = B.up(kps, (size_t)n, c); kf.desc = B.up(desc, (size_t)n * 32, c * 32); kf.count = B.up(&n, 1);
+    int32_t* cs = B.zeros<int32_t>(GRID_CELLS + 1); int32_t* ci = B.zeros<int32_t>(c);
+    kf.cell_start = cs; kf.cell_idx = ci;
+    if (!B.ok) { set_error("device allocation / upload failed"); return VIORB_ERR_HIP; }
+    return viorb_keyframe_grid_device(kf.kps, kf.count, kf.cap, 1, bounds4, cs, ci, nullptr);
 }
 
 } // namespace viorb
