@@ -193,6 +193,8 @@ typedef struct viorb_frontend_config {
 int viorb_frontend_create(const viorb_frontend_config* cfg, int max_batch, int cap, int device, viorb_frontend** out);
 int viorb_frontend_search_capacity(void);      /* largest cap whose search work arrays fit LDS (beyond it: global memory, slower) */
 int viorb_frontend_destroy(viorb_frontend* h);
+/* The max_batch and cap the handle was created with (either output may be NULL). */
+int viorb_frontend_capacity(const viorb_frontend* h, int32_t* max_batch, int32_t* cap);
 
 /* Frame::UndistortKeyPoints (reference src/Frame.cc:584-614) for a batch: kps_un[b][i] = kps[b][i] with pt replaced by
  * cv::undistortPoints(pt, mK, mDistCoef, R = Mat(), P = mK) — OpenCV 2.4: double inside, five fixed-point iterations of the
@@ -942,6 +944,11 @@ int viorb_debug_gba_last_trials(uint8_t* accepted, int cap, int* n);
 /* The two culling routines of the mapping thread (LocalMapping::KeyFrameCulling, ordered and exact, and LocalMapping::MapPointCulling),
  * in a header of their own. */
 #include "viorb_culling.h"
+
+/* Relocalisation after the PnP hypothesis (Tracking::Relocalization): the key-frame projection search
+ * ORBmatcher::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) and the solve / search / solve cascade, in a header of
+ * their own. */
+#include "viorb_relocalization.h"
 
 /* ---- Place recognition: BowVector, ORBVocabulary::score and KeyFrameDatabase (reference src/KeyFrameDatabase.cc:40-309) ------------
  * The question relocalisation (src/Tracking.cc:2134) and loop detection (src/LoopClosing.cc:148-165) begin with: which stored key frames

@@ -14,6 +14,7 @@ from .place import BowVector, BowVector_device, BowScore, BowScorePairs, KeyFram
 from .two_view import TwoViewInit, TwoViewBatch, draw_sets, two_view_config  # noqa: F401
 from .sim3 import Sim3Batch, sim3_ransac, sim3_config, optimize_sim3, optimize_sim3_batch, ransac_iterations  # noqa: F401
 from .sim3_match import Sim3MatchBatch, search_by_sim3, search_by_projection_sim3, fuse_sim3, keyframe_grid  # noqa: F401
+from .relocalization import RelocBatch, search_by_projection_reloc  # noqa: F401
 from .search_init import SearchInitBatch, search_for_initialization, scene_median_depth, scene_median_depth_batch  # noqa: F401
 from .culling import CullBatch, key_frame_culling, map_point_culling, map_point_culling_batch  # noqa: F401
 from .essential_graph import OptimizeEssentialGraph, OptimizeEssentialGraphDevice, essential_graph_workspace_bytes  # noqa: F401

@@ -1,7 +1,8 @@
 """ctypes declarations of include/viorb.h and of the headers it includes, viorb_global_ba_se3.h, viorb_two_view.h and viorb_sim3.h (kept 1:1; tests/test_host_hooks.py checks that every
 declared entry point of viorb.h is exported, has a signature here and that the argument counts agree; tests/test_global_ba_se3_ref.py
 does the same for SIGNATURES_GLOBAL_BA_SE3, tests/test_two_view_ref.py for SIGNATURES_TWO_VIEW, tests/test_sim3_ref.py for SIGNATURES_SIM3,
-tests/test_sim3_match_ref.py for SIGNATURES_SIM3_MATCH, tests/test_kf_culling_ref.py for SIGNATURES_CULLING)."""
+tests/test_sim3_match_ref.py for SIGNATURES_SIM3_MATCH, tests/test_kf_culling_ref.py for SIGNATURES_CULLING, tests/test_reloc_ref.py for
+SIGNATURES_RELOCALIZATION)."""
 import ctypes as C
 import os
 import numpy as np
@@ -127,6 +128,27 @@ class S3mSide(C.Structure):
     _fields_ = [("kf", S3mKeyframes)] + [(n, C.c_void_p) for n in ("pose12", "has_point", "pts_f", "pts_desc", "already")]
 
 
+class RelocConfig(C.Structure):
+    """viorb_reloc_config (include/viorb_relocalization.h)."""
+    _fields_ = [("min_good", C.c_int32), ("accept", C.c_int32), ("narrow_above", C.c_int32), ("th_coarse", C.c_float), ("orb_dist_coarse", C.c_int32),
+                ("th_narrow", C.c_float), ("orb_dist_narrow", C.c_int32), ("check_orientation", C.c_int32)]
+
+
+class RelocInputs(C.Structure):
+    """viorb_reloc_inputs (include/viorb_relocalization.h)."""
+    _fields_ = [("frames", C.POINTER(S3mKeyframes)), ("n_frames", C.c_int32), ("hyp_frame", C.c_void_p), ("uright", C.c_void_p)] \
+        + [(n, C.c_void_p) for n in ("pose12", "kf_angle", "kf_valid", "pts_f", "pts_desc", "kf_count")] + [("kcap", C.c_int32)] \
+        + [(n, C.c_void_p) for n in ("bow_match", "inlier")]
+
+
+RELOC_OUTPUT_FIELDS = ("accepted", "n_good", "stage", "counts", "out_pose12", "chi2", "frame_match", "outlier")
+
+
+class RelocOutputs(C.Structure):
+    """viorb_reloc_outputs (include/viorb_relocalization.h)."""
+    _fields_ = [(n, C.c_void_p) for n in RELOC_OUTPUT_FIELDS]
+
+
 SEARCH_INIT_OUTPUT_FIELDS = ("matches21", "matched_distance", "rot_hist", "reason", "xy1", "xy2", "sweeps")
 
 
@@ -199,6 +221,7 @@ SIGNATURES = {
     "viorb_frontend_create": (i32, [PP(FrontendConfig), i32, i32, i32, PP(vp)]),
     "viorb_frontend_search_capacity": (i32, []),
     "viorb_frontend_destroy": (i32, [vp]),
+    "viorb_frontend_capacity": (i32, [vp, vp, vp]),
     "viorb_frontend_grid_device": (i32, [vp, vp, vp, i32, vp, vp, vp]),
     "viorb_frontend_undistort_device": (i32, [vp, vp, vp, i32, vp, vp]),
     "viorb_undistort_points": (i32, [vp, i32, vp, vp, vp]),
@@ -428,6 +451,22 @@ SIGNATURES_CULLING = {
     "viorb_debug_map_point_code": (i32, [i32] * 7),
 }
 
+# mirrors include/viorb_relocalization.h (the relocalisation matcher and the refine cascade); tests/test_reloc_ref.py checks names and
+# argument counts against it
+SIGNATURES_RELOCALIZATION = {
+    "viorb_relocalization_workspace_bytes": (sz, [i32, i32, i32]),
+    "viorb_search_by_projection_reloc_device": (i32, [PP(S3mKeyframes), i32] + [vp] * 8 + [i32, vp] + _cam + [i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "viorb_search_by_projection_reloc": (i32, [vp, vp, i32] + [vp] * 6 + [i32, vp] + _cam + [i32, i32, vp, vp, vp]),
+    "viorb_reloc_config_default": (i32, [PP(RelocConfig)]),
+    "viorb_relocalization_refine_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "viorb_relocalization_refine_device": (i32, [vp, PP(RelocInputs), PP(RelocConfig), PP(MappingCamera), vp, C.c_double, i32, PP(RelocOutputs), vp, sz, vp]),
+    "viorb_relocalization_refine": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, PP(RelocConfig), PP(MappingCamera), vp, C.c_double] + [vp] * 8),
+    "viorb_relocalization_shape": (i32, [vp]),
+    "viorb_debug_reloc_project": (i32, [vp, vp] + _cam + [vp, vp]),
+    "viorb_debug_reloc_match": (i32, [vp, vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "viorb_debug_reloc_decide": (i32, [PP(RelocConfig), i32, i32, i32]),
+}
+
 _lib = None
 
 
@@ -449,7 +488,7 @@ def lib():
         L = C.CDLL(SO_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GLOBAL_BA_SE3.items()) + list(SIGNATURES_TWO_VIEW.items()) \
                 + list(SIGNATURES_SIM3.items()) + list(SIGNATURES_SIM3_MATCH.items()) + list(SIGNATURES_ESSENTIAL_GRAPH.items()) \
-                + list(SIGNATURES_SEARCH_INIT.items()) + list(SIGNATURES_CULLING.items()):
+                + list(SIGNATURES_SEARCH_INIT.items()) + list(SIGNATURES_CULLING.items()) + list(SIGNATURES_RELOCALIZATION.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -1612,6 +1612,13 @@ int viorb_frontend_create(const viorb_frontend_config* cfg, int max_batch, int c
     return VIORB_OK;
 }
 
+int viorb_frontend_capacity(const viorb_frontend* h, int32_t* max_batch, int32_t* cap) {
+    VIORB_REQUIRE(h, "null handle");
+    if (max_batch) *max_batch = h->max_batch;
+    if (cap) *cap = h->cap;
+    return VIORB_OK;
+}
+
 int viorb_frontend_search_capacity(void) {                                 // largest cap the projection search's LDS plan holds
     int lo = 1, hi = 65535;
     while (lo < hi) { const int mid = (lo + hi + 1) / 2; if (search_lds_bytes(mid, search_slot_n(mid)) <= 160 * 1024) lo = mid; else hi = mid - 1; }

@@ -200,47 +200,30 @@ __global__ __launch_bounds__(S3M_CLAIM_THREADS) void k_s3m_claim(S3mScwArgs A) {
     const uint32_t* cand = A.cand + (size_t)b * S3M_LIST * pcap;
     for (int p = threadIdx.x; p < pcap; p += blockDim.x) choice[p] = -1;
     __syncthreads();
-    for (;;) {
-        for (int f = threadIdx.x; f < n; f += blockDim.x) s_owner[f] = INT_MAX;
-        __syncthreads();
-        for (int p = threadIdx.x; p < npts; p += blockDim.x) { const int c = choice[p]; if (c >= 0) atomicMin(&s_owner[c], p); }
-        __syncthreads();
-        int changed = 0;
-        for (int p = threadIdx.x; p < npts; p += blockDim.x) {
-            const int nc = cand_n[p];
-            if (nc == 0) continue;
-            int c;
-            if (nc <= S3M_LIST) {
-                c = s3m_pick(cand + p, nc, (size_t)pcap, [&](int idx) { return s_owner[idx] >= p; });
-            } else {
-                S3mScw D;
-                s3m_decompose(A.Scw + (size_t)b * 12, D);
-                const float* X = A.pts_f + ((size_t)b * pcap + p) * 8;
-                float x8[8];
+    s3m_claim_sweeps(s_owner, n, npts, choice, cand_n, cand, (size_t)pcap, S3M_LIST, TH_LOW, [&](int p) {
+        S3mScw D;
+        s3m_decompose(A.Scw + (size_t)b * 12, D);
+        const float* X = A.pts_f + ((size_t)b * pcap + p) * 8;
+        float x8[8];
 #pragma unroll
-                for (int k = 0; k < 8; k++) x8[k] = X[k];
-                S3mProj P;
-                s3m_project_scw(A.cam, D, x8, P);
-                const uint4* dl = reinterpret_cast<const uint4*>(A.pts_desc + ((size_t)b * pcap + p) * 32);
-                const uint4 da = dl[0], db = dl[1];
-                const uint8_t* desc = A.kf.desc + (size_t)b * cap * 32;
-                const uint8_t* taken = A.feat_taken + (size_t)b * cap;
-                int best_dist = 256;
-                c = -1;
-                const int lvl = P.level;
-                s3m_scan(P, A.kf.kps + (size_t)b * cap, A.kf.cell_start + (size_t)b * (GRID_CELLS + 1), A.kf.cell_idx + (size_t)b * cap,
-                         n, cap, [&](int idx, int octave) {
-                             if (taken[idx] || s_owner[idx] < p) return;
-                             if (octave < lvl - 1 || octave > lvl) return;
-                             const int dist = desc_distance(da, db, desc + (size_t)idx * 32);
-                             if (dist < best_dist) { best_dist = dist; c = idx; }
-                         });
-                if (best_dist > TH_LOW) c = -1;
-            }
-            if (c != choice[p]) { choice[p] = c; changed = 1; }
-        }
-        if (!__syncthreads_or(changed)) break;
-    }
+        for (int k = 0; k < 8; k++) x8[k] = X[k];
+        S3mProj P;
+        s3m_project_scw(A.cam, D, x8, P);
+        const uint4* dl = reinterpret_cast<const uint4*>(A.pts_desc + ((size_t)b * pcap + p) * 32);
+        const uint4 da = dl[0], db = dl[1];
+        const uint8_t* desc = A.kf.desc + (size_t)b * cap * 32;
+        const uint8_t* taken = A.feat_taken + (size_t)b * cap;
+        int best_dist = 256, c = -1;
+        const int lvl = P.level;
+        s3m_scan(P, A.kf.kps + (size_t)b * cap, A.kf.cell_start + (size_t)b * (GRID_CELLS + 1), A.kf.cell_idx + (size_t)b * cap,
+                 n, cap, [&](int idx, int octave) {
+                     if (taken[idx] || s_owner[idx] < p) return;
+                     if (octave < lvl - 1 || octave > lvl) return;
+                     const int dist = desc_distance(da, db, desc + (size_t)idx * 32);
+                     if (dist < best_dist) { best_dist = dist; c = idx; }
+                 });
+        return best_dist <= TH_LOW ? c : -1;
+    });
     int found = 0;
     for (int base = 0; base < npts; base += blockDim.x) {
         const int p = base + threadIdx.x;

@@ -134,15 +134,15 @@ VIORB_HD void s3m_project_pair(const S3mCam& C, const float* pose12_own, const f
 
 // The ordered phase of SearchByProjection(KF, Scw) (:370-398). A candidate is dist << 16 | feature; a point's list holds its candidates
 // that are free on entry, in GetFeaturesInArea visiting order. s3m_pick is the reference's inner loop over the candidates `is_free`
-// admits: the first minimum; -1 when there is none at a distance <= TH_LOW.
-template <class Free> VIORB_HD int s3m_pick(const uint32_t* list, int n, size_t stride, Free&& is_free) {
+// admits: the first minimum; -1 when there is none at a distance <= gate (TH_LOW for the Scw matcher, ORBdist for the relocalisation one).
+template <class Free> VIORB_HD int s3m_pick(const uint32_t* list, int n, size_t stride, Free&& is_free, int gate = TH_LOW) {
     int best = -1, best_dist = 256;
     for (int k = 0; k < n; k++) {
         const uint32_t e = list[(size_t)k * stride];
         const int idx = (int)(e & 0xffffu), d = (int)(e >> 16);
         if (d < best_dist && is_free(idx)) { best_dist = d; best = idx; }
     }
-    return best_dist <= TH_LOW ? best : -1;
+    return best_dist <= gate ? best : -1;
 }
 
 // The point-order loop as a fixed-point iteration: choice[p] = s3m_pick over the features no earlier point chose in the previous sweep.
@@ -150,7 +150,7 @@ template <class Free> VIORB_HD int s3m_pick(const uint32_t* list, int n, size_t 
 // changes nothing is the loop's result, so the iteration ends after at most npts + 1 sweeps. The device kernel runs the same sweeps with a
 // workgroup; this is the serial form. owner [nfeat] is scratch. Returns the number of sweeps.
 inline int s3m_claim_in_order(const uint32_t* cand, const int32_t* cand_n, int npts, int lcap, const uint8_t* taken_in, int nfeat, int32_t* choice,
-                              int32_t* owner) {
+                              int32_t* owner, int gate = TH_LOW) {
     for (int p = 0; p < npts; p++) choice[p] = -1;
     int sweeps = 0;
     for (;;) {
@@ -160,11 +160,37 @@ inline int s3m_claim_in_order(const uint32_t* cand, const int32_t* cand_n, int n
         bool changed = false;
         for (int p = 0; p < npts; p++) {
             const int n = cand_n[p] < lcap ? cand_n[p] : lcap;
-            const int c = s3m_pick(cand + (size_t)p * lcap, n, 1, [&](int idx) { return idx < nfeat && !taken_in[idx] && owner[idx] >= p; });
+            const int c = s3m_pick(cand + (size_t)p * lcap, n, 1, [&](int idx) { return idx < nfeat && !taken_in[idx] && owner[idx] >= p; }, gate);
             if (c != choice[p]) { choice[p] = c; changed = true; }
         }
         if (!changed) return sweeps;
     }
 }
+
+#if defined(__HIPCC__)
+// The same sweeps with a workgroup, the points of a sweep in parallel; every thread of the workgroup calls it. s_owner [n] (LDS): the
+// lowest point that chose feature f in the previous sweep (LDS atomics on scratch). choice [npts] is -1 on entry and holds the loop's
+// result on return. cand: entry k of point p at cand[k * stride + p], cand_n [npts] counts on past list_cap; a point whose candidates
+// exceeded its list is served by rescan(p) = the first minimum of its window among the features that are free on entry and whose
+// s_owner is >= p, or -1 above the gate. Shared by k_s3m_claim (sim3_match.hip) and k_reloc_claim (relocalization.hip).
+template <class Rescan>
+__device__ __forceinline__ void s3m_claim_sweeps(int* s_owner, int n, int npts, int* choice, const int* __restrict__ cand_n,
+                                                 const uint32_t* __restrict__ cand, size_t stride, int list_cap, int gate, Rescan&& rescan) {
+    for (;;) {
+        for (int f = threadIdx.x; f < n; f += blockDim.x) s_owner[f] = INT_MAX;
+        __syncthreads();
+        for (int p = threadIdx.x; p < npts; p += blockDim.x) { const int c = choice[p]; if (c >= 0) atomicMin(&s_owner[c], p); }
+        __syncthreads();
+        int changed = 0;
+        for (int p = threadIdx.x; p < npts; p += blockDim.x) {
+            const int nc = cand_n[p];
+            if (nc == 0) continue;
+            const int c = nc <= list_cap ? s3m_pick(cand + p, nc, stride, [&](int idx) { return s_owner[idx] >= p; }, gate) : rescan(p);
+            if (c != choice[p]) { choice[p] = c; changed = 1; }
+        }
+        if (!__syncthreads_or(changed)) break;
+    }
+}
+#endif
 
 } // namespace viorb

@@ -15,6 +15,7 @@
 //   search_by_projection_sim3        ORBmatcher::SearchByProjection(KeyFrame*, Scw, vpPoints, vpMatched, th)    :290-403
 //   fuse_sim3                        ORBmatcher::Fuse(KeyFrame*, Scw, vpPoints, th, vpReplacePoint)             :977-1100
 //   search_for_initialization        ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize)   :405-520
+//   search_by_projection_reloc       ORBmatcher::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist)          :1473-1600
 //
 // Two accessors the reference does not have are needed on MapPoint (its mfMinDistance / mfMaxDistance are protected and the existing
 // getters return them scaled by 0.8 / 1.2): `float GetMinDistance()` and `float GetMaxDistance()`, returning the raw members under
@@ -346,6 +347,27 @@ inline int search_for_initialization(FrameT& F1, FrameT& F2, PointVec& vbPrevMat
                                           check_ori ? 1 : 0, &m12[0], &nmatches, 0), "SearchForInitialization");
     vnMatches12.assign(m12.begin(), m12.begin() + n1);
     for (int i = 0; i < n1; i++) if (m12[i] >= 0) { vbPrevMatched[i].x = prev[2 * i]; vbPrevMatched[i].y = prev[2 * i + 1]; }
+    return nmatches;
+}
+
+// ORBmatcher::SearchByProjection(Frame &CurrentFrame, KeyFrame *pKF, const set<MapPoint*> &sAlreadyFound, const float th, const int ORBdist),
+// the call sites of src/Tracking.cc:2238 and :2252 (relocalization_refine of viorb_tracking_shim.h runs the whole cascade, these two
+// searches included, in one call): the ordered search and the rotation histogram run on the device, CurrentFrame.mvpMapPoints[bestIdx2] = pMP
+// (:1558) is written for the matches the histogram keeps. Returns nmatches.
+template <class FrameT, class KeyFrameT, class MapPointT>
+inline int search_by_projection_reloc(FrameT& F, KeyFrameT* pKF, const std::set<MapPointT*>& sAlreadyFound, float th, int ORBdist, bool check_ori) {
+    RelocKeyFrame<KeyFrameT, MapPointT> K(pKF);
+    const int n = F.N, np = (int)K.vpMPs.size();
+    std::vector<viorb_keypoint> kk; flatten_keys(F.mvKeysUn, n, kk);
+    std::vector<unsigned char> found(np + 1, 0), taken(n + 1, 0);
+    for (int i = 0; i < np; i++) found[i] = K.vpMPs[i] && sAlreadyFound.count(K.vpMPs[i]) ? 1 : 0;
+    for (int j = 0; j < n; j++) taken[j] = F.mvpMapPoints[j] ? 1 : 0;
+    float pose[12], bounds[4]; flatten_pose(F.mTcw, pose);
+    const viorb_mapping_camera cam = reloc_camera(F, bounds);
+    std::vector<int32_t> best(np + 1, -1); int nmatches = 0;
+    check(viorb_search_by_projection_reloc(&kk[0], F.mDescriptors.data, n, pose, &K.angle[0], &K.valid[0], &found[0], &K.pts_f[0], &K.desc[0], np, &taken[0], &cam,
+                                           bounds, th, ORBdist, check_ori ? 1 : 0, &best[0], &nmatches, 0), "SearchByProjection(Frame, KeyFrame)");
+    for (int i = 0; i < np; i++) if (best[i] >= 0) F.mvpMapPoints[best[i]] = K.vpMPs[i];
     return nmatches;
 }
 

@@ -2,6 +2,7 @@
 // include/viorb.h for the two per-frame calls Tracking makes after extraction:
 //   ORBmatcher::SearchByProjection(Frame&, const Frame&, th, bMono)            reference src/ORBmatcher.cc:1328-1471
 //   Optimizer::PoseOptimization(Frame*, KeyFrame*|Frame*, preint, gw, marg)    reference src/Optimizer.cc:323-1112
+// and for the refine cascade of Tracking::Relocalization (relocalization_refine, reference src/Tracking.cc:2209-2269).
 // Function templates over the reference's Frame / KeyFrame / MapPoint / NavState / IMUPreintegrator: this
 // header includes none of the reference's headers — it is compiled inside the reference tree, after them
 // (INTEGRATION.md shows the three-line replacements of the reference functions that call into it). It only
@@ -11,6 +12,8 @@
 #define VIORB_TRACKING_SHIM_H
 
 #include <vector>
+#include <map>
+#include <utility>
 #include <cstring>
 #include <string>
 #include <stdexcept>
@@ -121,6 +124,83 @@ inline int pose_optimization_keyframe(FrameT* pFrame, KeyFrameT* pLastKF, const 
         pFrame->mNavStatePrior = ns;
     }
     return (int)info[0];
+}
+
+// ---- relocalisation (include/viorb_relocalization.h) ---------------------------------------------------------------------------------
+// The camera and the image bounds of a frame or key frame as the relocalisation entries take them.
+template <class FrameT> inline viorb_mapping_camera reloc_camera(const FrameT& F, float bounds4[4]) {
+    viorb_mapping_camera cam; std::memset(&cam, 0, sizeof(cam));
+    cam.fx = F.fx; cam.fy = F.fy; cam.cx = F.cx; cam.cy = F.cy; cam.mbf = F.mbf; cam.nlevels = F.mnScaleLevels;
+    for (int i = 0; i < 16; i++) {
+        const int l = i < F.mnScaleLevels ? i : F.mnScaleLevels - 1;
+        cam.scale_factors[i] = F.mvScaleFactors[l]; cam.level_sigma2[i] = F.mvLevelSigma2[l];
+    }
+    cam.scale_factor = cam.scale_factors[F.mnScaleLevels > 1 ? 1 : 0];
+    bounds4[0] = F.mnMinX; bounds4[1] = F.mnMaxX; bounds4[2] = F.mnMinY; bounds4[3] = F.mnMaxY;
+    return cam;
+}
+
+// The candidate key frame flattened by feature index: angle, validity (a point exists and is not bad), the point's position, distances and
+// descriptor; index_of maps a map point to its feature. Throws where a pointer repeats in GetMapPointMatches(): the cascade identifies a
+// map point by the key-frame feature that holds it.
+template <class KeyFrameT, class MapPointT> struct RelocKeyFrame {
+    std::vector<MapPointT*> vpMPs; std::vector<float> angle, pts_f; std::vector<unsigned char> valid, desc; std::map<MapPointT*, int> index_of;
+    explicit RelocKeyFrame(KeyFrameT* pKF) : vpMPs(pKF->GetMapPointMatches()) {
+        const int n = (int)vpMPs.size();
+        angle.assign(n + 1, 0.f); pts_f.assign((size_t)(n + 1) * 8, 0.f); valid.assign(n + 1, 0); desc.assign((size_t)(n + 1) * 32, 0);
+        for (int i = 0; i < n; i++) {
+            angle[i] = pKF->mvKeysUn[i].angle;
+            MapPointT* pMP = vpMPs[i];
+            if (!pMP) continue;
+            if (!index_of.insert(std::make_pair(pMP, i)).second) throw std::runtime_error("Relocalization: a map point repeats in GetMapPointMatches()");
+            if (pMP->isBad()) continue;
+            valid[i] = 1;
+            const cv::Mat Pw = pMP->GetWorldPos(), d = pMP->GetDescriptor();
+            float* f8 = &pts_f[(size_t)i * 8];
+            for (int c = 0; c < 3; c++) f8[c] = Pw.at<float>(c);
+            f8[6] = pMP->GetMinDistance(); f8[7] = pMP->GetMaxDistance();
+            std::memcpy(&desc[(size_t)i * 32], d.data, 32);
+        }
+    }
+};
+
+// Tracking::Relocalization from `Tcw.copyTo(mCurrentFrame.mTcw)` to `if(nGood>=50)` (src/Tracking.cc:2209-2269) for one hypothesis: Tcw and
+// vbInliers are what PnPsolver::iterate returned, vpMapPointMatches is SearchByBoW's result for this candidate. Leaves F.mTcw (SetPose),
+// F.mvpMapPoints and F.mvbOutlier as the reference does at the exit it takes and returns nGood; *stage (may be NULL) receives the
+// VIORB_RELOC_* exit. The caller keeps its loop: `if(nGood>=50) { bMatch = true; break; }`.
+template <class FrameT, class KeyFrameT, class MapPointT>
+inline int relocalization_refine(FrameT& F, KeyFrameT* pKF, const cv::Mat& Tcw, const std::vector<bool>& vbInliers,
+                                 const std::vector<MapPointT*>& vpMapPointMatches, bool check_ori = true, int* stage = 0) {
+    const int n = F.N;
+    RelocKeyFrame<KeyFrameT, MapPointT> K(pKF);
+    const int npts = (int)K.vpMPs.size();
+    std::vector<viorb_keypoint> kk(n + 1);
+    std::vector<float> ur(n + 1, -1.f);
+    std::vector<int32_t> bow(n + 1, -1), fm(n + 1, -1); std::vector<unsigned char> inl(n + 1, 0), ol(n + 1, 0);
+    for (int j = 0; j < n; j++) {
+        const cv::KeyPoint& k = F.mvKeysUn[j];
+        kk[j].x = k.pt.x; kk[j].y = k.pt.y; kk[j].size = k.size; kk[j].angle = k.angle; kk[j].response = k.response; kk[j].octave = k.octave; kk[j].class_id = k.class_id;
+        ur[j] = F.mvuRight[j];
+        if (j < (int)vbInliers.size() && vbInliers[j] && j < (int)vpMapPointMatches.size() && vpMapPointMatches[j]) {
+            typename std::map<MapPointT*, int>::const_iterator it = K.index_of.find(vpMapPointMatches[j]);
+            if (it == K.index_of.end()) throw std::runtime_error("Relocalization: an inlier's map point is not held by the candidate key frame");
+            bow[j] = it->second; inl[j] = 1;
+        }
+    }
+    float pose[12], out_pose[12], bounds[4];
+    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) pose[3 * r + c] = Tcw.at<float>(r, c); pose[9 + r] = Tcw.at<float>(r, 3); }
+    const viorb_mapping_camera cam = reloc_camera(F, bounds);
+    viorb_reloc_config cfg; check(viorb_reloc_config_default(&cfg), "Relocalization");
+    cfg.check_orientation = check_ori ? 1 : 0;
+    int32_t accepted = 0, n_good = 0, st = 0, counts[8]; double chi2 = 0;
+    check(viorb_relocalization_refine(&kk[0], F.mDescriptors.data, &ur[0], n, pose, &K.angle[0], &K.valid[0], &K.pts_f[0], &K.desc[0], npts, &bow[0], &inl[0],
+                                      &cfg, &cam, bounds, (double)F.mbf, &accepted, &n_good, &st, counts, out_pose, &chi2, &fm[0], &ol[0]), "Relocalization");
+    cv::Mat T(4, 4, CV_32F);
+    for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) T.at<float>(r, c) = r < 3 ? (c < 3 ? out_pose[3 * r + c] : out_pose[9 + r]) : (c == 3 ? 1.f : 0.f);
+    F.SetPose(T);
+    for (int j = 0; j < n; j++) { F.mvpMapPoints[j] = fm[j] >= 0 ? K.vpMPs[fm[j]] : static_cast<MapPointT*>(0); F.mvbOutlier[j] = ol[j] != 0; }
+    if (stage) *stage = st;
+    return n_good;
 }
 
 } // namespace viorb_shim

@@ -1506,3 +1506,52 @@ def make_culling_problem(seed, n_kf=None, n_cand=None, max_kps=300, min_kps=0, n
     s["cand_kf"], s["kp_start"] = cand.astype(np.int32), np.array(kp_start, np.int32)
     s["kp_point"], s["kp_octave"], s["kp_depth"] = np.array(point, np.int32), np.array(octave, np.uint8), depth.astype(np.float32)
     return s
+
+
+def make_reloc_problem(seed, n_feat=1000, n_pts=1000, n_cand=1, shared=0.7, n_bow=80, n_inliers=40, nlevels=8, w=752, h=480):
+    """A lost frame of n_feat features and n_cand candidate key frames of n_pts map points each, as Tracking::Relocalization meets them
+    after PnPsolver::iterate: a share `shared` of each candidate's points is seen in the frame (a feature near the projection, a
+    descriptor some bits away), n_bow of them are SearchByBoW matches and n_inliers of those RANSAC inliers, so that the cascade's first
+    solve leaves between 10 and 50 good points, the coarse search runs and the second solve decides. dict(kps, desc, intr4, sf, bounds4, hyps): a hypothesis is
+    dict(pose12, kf_angle, kf_valid, kf_found, feat_taken, pts_f, pts_desc, bow_match, inlier), indexed by key-frame feature."""
+    from .capi import KP_DTYPE
+    rng = np.random.default_rng(seed)
+    f32 = np.float32
+    intr4 = np.array([458.654, 457.296, 367.215, 248.375], f32)
+    sf = (f32(1.2) ** np.arange(nlevels)).astype(f32)
+    R = _rotvec_to_R(rng.normal(0, 0.3, 3)); t = rng.normal(0, 1.0, 3)
+    kps = np.zeros(n_feat, KP_DTYPE)
+    kps["x"], kps["y"] = rng.uniform(8, w - 12, n_feat), rng.uniform(8, h - 12, n_feat)
+    kps["octave"] = np.minimum(rng.geometric(0.35, n_feat) - 1, nlevels - 1)
+    kps["angle"], kps["size"], kps["response"] = rng.uniform(0, 359.9, n_feat), 31 * sf[kps["octave"]], 50
+    desc = rng.integers(0, 256, (n_feat, 32), dtype=np.uint8)
+    hyps = []
+    for c in range(n_cand):
+        seen = rng.permutation(n_feat)[:min(int(shared * n_pts), n_feat)]
+        pts_f, pts_desc, ang = np.zeros((n_pts, 8), f32), rng.integers(0, 256, (n_pts, 32), dtype=np.uint8), rng.uniform(0, 359.9, n_pts).astype(f32)
+        z = rng.uniform(2, 10, n_pts)
+        u, v = rng.uniform(0, w, n_pts), rng.uniform(0, h, n_pts)
+        lvl = rng.integers(0, nlevels, n_pts)
+        u[:len(seen)], v[:len(seen)] = kps["x"][seen] + rng.normal(0, 0.7, len(seen)), kps["y"][seen] + rng.normal(0, 0.7, len(seen))
+        lvl[:len(seen)] = kps["octave"][seen]
+        Xc = np.stack([(u - intr4[2]) / intr4[0] * z, (v - intr4[3]) / intr4[1] * z, z], 1)
+        Xw = (Xc - t) @ R                                          # R^T (Xc - t), row-wise
+        dist = np.linalg.norm(Xc, axis=1)
+        pts_f[:, :3] = Xw
+        pts_f[:, 7] = dist * 1.2 ** (lvl - 0.5); pts_f[:, 6] = pts_f[:, 7] / 1.2 ** (nlevels - 1)
+        for k, f in enumerate(seen):
+            pts_desc[k] = _flip_bits(rng, desc[f], int(rng.integers(0, 45)))
+            ang[k] = (kps["angle"][f] + 30.0 + rng.normal(0, 4)) % 360.0
+        order = rng.permutation(n_pts)                               # the key frame's own feature order
+        inv = np.argsort(order)
+        pts_f, pts_desc, ang = pts_f[order], pts_desc[order], ang[order]
+        bow, inl = np.full(n_feat, -1, np.int32), np.zeros(n_feat, np.uint8)
+        for k in range(min(n_bow, len(seen))):
+            bow[seen[k]] = inv[k]
+            inl[seen[k]] = k < n_inliers
+        dR = _rotvec_to_R(rng.normal(0, 0.002, 3))
+        pose = np.concatenate([(dR @ R).ravel(), dR @ t + rng.normal(0, 0.01, 3)]).astype(f32)
+        found = np.zeros(n_pts, np.uint8); found[bow[inl != 0]] = 1
+        hyps.append(dict(pose12=pose, kf_angle=ang, kf_valid=(rng.uniform(size=n_pts) > 0.03).astype(np.uint8), kf_found=found, feat_taken=inl.copy(),
+                         pts_f=pts_f, pts_desc=pts_desc, bow_match=bow, inlier=inl, frame=0))
+    return dict(kps=kps, desc=desc, intr4=intr4, sf=sf, bounds4=np.array([0, w, 0, h], f32), hyps=hyps)
