@@ -945,6 +945,10 @@ int viorb_debug_gba_last_trials(uint8_t* accepted, int cap, int* n);
  * in a header of their own. */
 #include "viorb_culling.h"
 
+/* The local map of the tracking thread (Tracking::UpdateLocalMap: UpdateLocalKeyFrames, ordered and exact, and UpdateLocalPoints) and
+ * the packing of its points for viorb_frontend_search_local_points_device, in a header of their own. */
+#include "viorb_local_map.h"
+
 /* Relocalisation after the PnP hypothesis (Tracking::Relocalization): the key-frame projection search
  * ORBmatcher::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) and the solve / search / solve cascade, in a header of
  * their own. */

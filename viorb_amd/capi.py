@@ -2,7 +2,7 @@
 declared entry point of viorb.h is exported, has a signature here and that the argument counts agree; tests/test_global_ba_se3_ref.py
 does the same for SIGNATURES_GLOBAL_BA_SE3, tests/test_two_view_ref.py for SIGNATURES_TWO_VIEW, tests/test_sim3_ref.py for SIGNATURES_SIM3,
 tests/test_sim3_match_ref.py for SIGNATURES_SIM3_MATCH, tests/test_kf_culling_ref.py for SIGNATURES_CULLING, tests/test_reloc_ref.py for
-SIGNATURES_RELOCALIZATION)."""
+SIGNATURES_RELOCALIZATION, tests/test_local_map_ref.py for SIGNATURES_LOCAL_MAP)."""
 import ctypes as C
 import os
 import numpy as np
@@ -172,6 +172,22 @@ class CullMap(C.Structure):
 class CullResult(C.Structure):
     """viorb_cull_result (include/viorb_culling.h)."""
     _fields_ = [(n, C.c_void_p) for n in CULL_RESULT_FIELDS]
+
+
+LOCAL_MAP_INTS = ("batch", "n_kf", "n_child", "n_kp", "n_pt", "n_obs")
+LOCAL_MAP_ARRAYS = ("kf_start", "kf_bad", "kf_parent", "kf_prev", "kf_next", "covis10", "child_start", "child_kf", "kf_by_key", "kp_start", "kp_point",
+                    "pt_start", "pt_bad", "obs_start", "obs", "frame_point", "frame_count", "prev_lkf", "prev_n_lkf", "prev_ref_kf")
+LOCAL_MAP_RESULT_FIELDS = ("lkf", "n_lkf", "n_voted", "ref_kf", "lpt", "n_lpt", "status", "frame_point_out", "kf_votes")
+
+
+class LocalMapSnapshot(C.Structure):
+    """viorb_local_map_snapshot (include/viorb_local_map.h)."""
+    _fields_ = [(n, C.c_int32) for n in LOCAL_MAP_INTS] + [(n, C.c_void_p) for n in LOCAL_MAP_ARRAYS]
+
+
+class LocalMapResult(C.Structure):
+    """viorb_local_map_result (include/viorb_local_map.h)."""
+    _fields_ = [(n, C.c_void_p) for n in LOCAL_MAP_RESULT_FIELDS]
 
 
 class TrackerConfig(C.Structure):
@@ -467,6 +483,18 @@ SIGNATURES_RELOCALIZATION = {
     "viorb_debug_reloc_decide": (i32, [PP(RelocConfig), i32, i32, i32]),
 }
 
+# mirrors include/viorb_local_map.h (Tracking::UpdateLocalMap and the packing of its points); tests/test_local_map_ref.py checks names and
+# argument counts against it
+SIGNATURES_LOCAL_MAP = {
+    "viorb_update_local_map_workspace_bytes": (sz, [i32, i32, i32]),
+    "viorb_update_local_map_device": (i32, [PP(LocalMapSnapshot), PP(LocalMapResult), i32, i32, i32, vp, sz, vp]),
+    "viorb_update_local_map": (i32, [PP(LocalMapSnapshot), PP(LocalMapResult), i32, i32, i32]),
+    "viorb_update_local_map_shape": (i32, [vp]),
+    "viorb_local_points_gather_workspace_bytes": (sz, [i32]),
+    "viorb_local_points_gather_device": (i32, [PP(LocalMapSnapshot), PP(LocalMapResult), i32, i32] + [vp] * 8 + [sz, vp]),
+    "viorb_debug_update_local_map_host": (i32, [PP(LocalMapSnapshot), PP(LocalMapResult), i32, i32, i32]),
+}
+
 _lib = None
 
 
@@ -488,7 +516,8 @@ def lib():
         L = C.CDLL(SO_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GLOBAL_BA_SE3.items()) + list(SIGNATURES_TWO_VIEW.items()) \
                 + list(SIGNATURES_SIM3.items()) + list(SIGNATURES_SIM3_MATCH.items()) + list(SIGNATURES_ESSENTIAL_GRAPH.items()) \
-                + list(SIGNATURES_SEARCH_INIT.items()) + list(SIGNATURES_CULLING.items()) + list(SIGNATURES_RELOCALIZATION.items()):
+                + list(SIGNATURES_SEARCH_INIT.items()) + list(SIGNATURES_CULLING.items()) + list(SIGNATURES_RELOCALIZATION.items()) \
+                + list(SIGNATURES_LOCAL_MAP.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -11,8 +11,11 @@
 #ifndef VIORB_TRACKING_SHIM_H
 #define VIORB_TRACKING_SHIM_H
 
+#include <algorithm>
+#include <functional>
 #include <vector>
 #include <map>
+#include <set>
 #include <utility>
 #include <cstring>
 #include <string>
@@ -201,6 +204,118 @@ inline int relocalization_refine(FrameT& F, KeyFrameT* pKF, const cv::Mat& Tcw, 
     for (int j = 0; j < n; j++) { F.mvpMapPoints[j] = fm[j] >= 0 ? K.vpMPs[fm[j]] : static_cast<MapPointT*>(0); F.mvbOutlier[j] = ol[j] != 0; }
     if (stage) *stage = st;
     return n_good;
+}
+
+// ---- Tracking::UpdateLocalMap (include/viorb_local_map.h) ------------------------------------------------------------------------------
+// The two calls of Tracking::UpdateLocalMap (src/Tracking.cc:1966-1967) become
+//   viorb_shim::update_local_map<KeyFrame, MapPoint>(mCurrentFrame, mvpLocalKeyFrames, mpReferenceKF, mvpLocalMapPoints);
+// The snapshot holds the key frames that observe a point of the frame (they are voted, and only they are visited by the neighbour loop),
+// their GetBestCovisibilityKeyFrames(10), GetChilds, GetParent, GetPrevKeyFrame and GetNextKeyFrame (what an iteration can add), and
+// the previous mvpLocalKeyFrames and mpReferenceKF (kept when nothing votes); a link of a key frame that is never visited is passed as
+// -1. Every key frame of the snapshot brings its GetMapPointMatches; observations are passed for the frame's points only. Pointer order
+// enters through kf_by_key, sorted with std::less<KeyFrame*>, and through the iteration order of GetChilds. Written back as the
+// reference leaves them: the bad points of F.mvpMapPoints cleared, mvpLocalKeyFrames, mpReferenceKF and F.mpReferenceKF (only when a key
+// frame won the vote), mvpLocalMapPoints. Returns VIORB_OK or VIORB_ULM_NO_VOTES; a failure throws.
+template <class KeyFrameT, class MapPointT, class FrameT>
+inline int update_local_map(FrameT& F, std::vector<KeyFrameT*>& mvpLocalKeyFrames, KeyFrameT*& mpReferenceKF, std::vector<MapPointT*>& mvpLocalMapPoints) {
+    std::map<KeyFrameT*, int> kf_slot; std::vector<KeyFrameT*> kfs;
+    std::map<MapPointT*, int> pt_slot; std::vector<MapPointT*> pts;
+    struct Add {
+        static int kf(std::map<KeyFrameT*, int>& m, std::vector<KeyFrameT*>& v, KeyFrameT* k) {
+            typename std::map<KeyFrameT*, int>::iterator it = m.find(k);
+            if (it != m.end()) return it->second;
+            m[k] = (int)v.size(); v.push_back(k); return (int)v.size() - 1;
+        }
+        static int pt(std::map<MapPointT*, int>& m, std::vector<MapPointT*>& v, MapPointT* p) {
+            typename std::map<MapPointT*, int>::iterator it = m.find(p);
+            if (it != m.end()) return it->second;
+            m[p] = (int)v.size(); v.push_back(p); return (int)v.size() - 1;
+        }
+    };
+    const int N = F.N;
+    std::vector<int32_t> frame_point(std::max(N, 1), -1);
+    std::vector<std::vector<int32_t> > pt_obs;                       // by point index; empty for a point the frame does not hold
+    for (int i = 0; i < N; i++) {
+        MapPointT* pMP = F.mvpMapPoints[i];
+        if (!pMP) continue;
+        const size_t before = pts.size();
+        const int p = Add::pt(pt_slot, pts, pMP);
+        frame_point[i] = p;
+        if (pts.size() == before) continue;
+        pt_obs.resize(pts.size());
+        const std::map<KeyFrameT*, size_t> observations = pMP->GetObservations();
+        for (typename std::map<KeyFrameT*, size_t>::const_iterator it = observations.begin(); it != observations.end(); ++it) pt_obs[p].push_back(Add::kf(kf_slot, kfs, it->first));
+    }
+    const size_t n_visited = kfs.size();                             // slots below: the key frames a vote can reach
+    std::vector<int32_t> covis10(n_visited * 10, -1), child_start(1, 0), child_kf;
+    std::vector<int32_t> parent(n_visited, -1), prev(n_visited, -1), next(n_visited, -1);
+    for (size_t k = 0; k < n_visited; k++) {
+        KeyFrameT* pKF = kfs[k];
+        const std::vector<KeyFrameT*> vNeighs = pKF->GetBestCovisibilityKeyFrames(10);
+        for (size_t j = 0; j < vNeighs.size() && j < 10; j++) covis10[k * 10 + j] = Add::kf(kf_slot, kfs, vNeighs[j]);
+        const std::set<KeyFrameT*> spChilds = pKF->GetChilds();
+        for (typename std::set<KeyFrameT*>::const_iterator sit = spChilds.begin(); sit != spChilds.end(); ++sit) child_kf.push_back(Add::kf(kf_slot, kfs, *sit));
+        child_start.push_back((int32_t)child_kf.size());
+        if (pKF->GetParent()) parent[k] = Add::kf(kf_slot, kfs, pKF->GetParent());
+        if (pKF->GetPrevKeyFrame()) prev[k] = Add::kf(kf_slot, kfs, pKF->GetPrevKeyFrame());
+        if (pKF->GetNextKeyFrame()) next[k] = Add::kf(kf_slot, kfs, pKF->GetNextKeyFrame());
+    }
+    std::vector<int32_t> prev_lkf;
+    for (size_t j = 0; j < mvpLocalKeyFrames.size(); j++) prev_lkf.push_back(Add::kf(kf_slot, kfs, mvpLocalKeyFrames[j]));
+    const int32_t prev_ref = mpReferenceKF ? Add::kf(kf_slot, kfs, mpReferenceKF) : -1;
+    const size_t nk = kfs.size();
+    if (nk > 65535) throw std::runtime_error("UpdateLocalMap: more than 65535 key frames in the snapshot");
+    covis10.resize(std::max<size_t>(nk, 1) * 10, -1); child_start.resize(nk + 1, (int32_t)child_kf.size());
+    parent.resize(std::max<size_t>(nk, 1), -1); prev.resize(parent.size(), -1); next.resize(parent.size(), -1);
+    std::vector<uint8_t> kf_bad(std::max<size_t>(nk, 1), 0);
+    std::vector<int32_t> kp_start(1, 0), kp_point;
+    for (size_t k = 0; k < nk; k++) {
+        kf_bad[k] = kfs[k]->isBad() ? 1 : 0;
+        const std::vector<MapPointT*> vpMPs = kfs[k]->GetMapPointMatches();
+        for (size_t i = 0; i < vpMPs.size(); i++) kp_point.push_back(vpMPs[i] ? Add::pt(pt_slot, pts, vpMPs[i]) : -1);
+        kp_start.push_back((int32_t)kp_point.size());
+    }
+    const size_t np = pts.size();
+    pt_obs.resize(np);
+    std::vector<uint8_t> pt_bad(std::max<size_t>(np, 1), 0);
+    std::vector<int32_t> obs_start(1, 0); std::vector<uint32_t> obs;
+    for (size_t p = 0; p < np; p++) {
+        pt_bad[p] = pts[p]->isBad() ? 1 : 0;
+        for (size_t o = 0; o < pt_obs[p].size(); o++) obs.push_back((uint32_t)pt_obs[p][o]);
+        obs_start.push_back((int32_t)obs.size());
+    }
+    std::vector<std::pair<KeyFrameT*, int32_t> > by_ptr;             // the order of std::map<KeyFrame*, int> keyframeCounter
+    for (size_t k = 0; k < nk; k++) by_ptr.push_back(std::make_pair(kfs[k], (int32_t)k));
+    struct Less { bool operator()(const std::pair<KeyFrameT*, int32_t>& a, const std::pair<KeyFrameT*, int32_t>& b) const { return std::less<KeyFrameT*>()(a.first, b.first); } };
+    std::sort(by_ptr.begin(), by_ptr.end(), Less());
+    std::vector<int32_t> kf_by_key(std::max<size_t>(nk, 1), 0);
+    for (size_t j = 0; j < nk; j++) kf_by_key[j] = by_ptr[j].second;
+    // every array at least one element long: the library refuses a null pointer whatever the count
+    const int n_child = (int)child_kf.size(), n_kp = (int)kp_point.size(), n_obs = (int)obs.size();
+    child_kf.resize(std::max<size_t>(child_kf.size(), 1)); kp_point.resize(std::max<size_t>(kp_point.size(), 1), -1); obs.resize(std::max<size_t>(obs.size(), 1));
+    const int cap = std::max(N, 1), lcap = (int)std::max<size_t>(nk, 1), pcap = (int)std::max<size_t>(np, 1);     // the lists hold distinct entries: nothing overflows
+    prev_lkf.resize(lcap, -1);
+    const int32_t kf_start[2] = {0, (int32_t)nk}, pt_start[2] = {0, (int32_t)np}, frame_count = N, prev_n = (int32_t)mvpLocalKeyFrames.size();
+    viorb_local_map_snapshot m;
+    m.batch = 1; m.n_kf = (int32_t)nk; m.n_child = n_child; m.n_kp = n_kp; m.n_pt = (int32_t)np; m.n_obs = n_obs;
+    m.kf_start = kf_start; m.kf_bad = &kf_bad[0]; m.kf_parent = &parent[0]; m.kf_prev = &prev[0]; m.kf_next = &next[0];
+    m.covis10 = &covis10[0]; m.child_start = &child_start[0]; m.child_kf = &child_kf[0]; m.kf_by_key = &kf_by_key[0];
+    m.kp_start = &kp_start[0]; m.kp_point = &kp_point[0]; m.pt_start = pt_start; m.pt_bad = &pt_bad[0]; m.obs_start = &obs_start[0]; m.obs = &obs[0];
+    m.frame_point = &frame_point[0]; m.frame_count = &frame_count; m.prev_lkf = &prev_lkf[0]; m.prev_n_lkf = &prev_n; m.prev_ref_kf = &prev_ref;
+    std::vector<int32_t> lkf(lcap, -1), lpt(pcap, -1), fpo(cap, -1);
+    int32_t n_lkf = 0, n_voted = 0, ref = -1, n_lpt = 0, status = 0;
+    viorb_local_map_result r;
+    std::memset(&r, 0, sizeof(r));
+    r.lkf = &lkf[0]; r.n_lkf = &n_lkf; r.n_voted = &n_voted; r.ref_kf = &ref; r.lpt = &lpt[0]; r.n_lpt = &n_lpt; r.status = &status; r.frame_point_out = &fpo[0];
+    check(viorb_update_local_map(&m, &r, cap, lcap, pcap), "UpdateLocalMap");
+    if (status != VIORB_OK && status != VIORB_ULM_NO_VOTES) throw std::runtime_error("UpdateLocalMap: the library refused the snapshot");
+    for (int i = 0; i < N; i++) if (fpo[i] < 0) F.mvpMapPoints[i] = static_cast<MapPointT*>(0);
+    mvpLocalKeyFrames.clear();
+    for (int32_t j = 0; j < n_lkf; j++) mvpLocalKeyFrames.push_back(kfs[lkf[j]]);
+    if (n_voted > 0) { mpReferenceKF = kfs[ref]; F.mpReferenceKF = mpReferenceKF; }               // pKFmax exists (:2120-2124)
+    mvpLocalMapPoints.clear();
+    for (int32_t j = 0; j < n_lpt; j++) mvpLocalMapPoints.push_back(pts[lpt[j]]);
+    return status;
 }
 
 } // namespace viorb_shim
