@@ -174,7 +174,7 @@ static void add_stream(Packed& P) {
             const bool stereo = rnd() % 3 == 0;
             int oc = base + (rnd() % 3 == 0 ? rint_(-2, 2) : 0);
             oc = oc < 0 ? 0 : oc > 7 ? 7 : oc;
-            P.obs.push_back(cull_obs_pack(slots[k], oc, stereo));
+            P.obs.push_back(snap_obs_pack(slots[k], oc, stereo));
             seen[slots[k]].push_back(p);
             n += stereo ? 2 : 1;
         }

@@ -139,6 +139,59 @@ def expected(name):
     return T.key_frame_culling(scene, mono)
 
 
+# ---- broken snapshots ---------------------------------------------------------------------------------------------------------------------
+def breakable_scene():
+    """4 key frames, 2 candidates of 2 keypoints each, 3 points of which point 1 is seen by both candidates."""
+    pts = pts_seen_by(1, [0, 2, 3]) + pts_seen_by(1, [0, 1, 2, 3]) + pts_seen_by(1, [1, 2, 3])
+    return M.scene_from_lists(chain([0.0, 0.1, 0.2, 2.5]), 3, [(0, table(0, 2)), (1, table(1, 2))], pts, vins_inited=True)
+
+
+def broken(scene):
+    """(what, scene) for every kind of broken snapshot the validator refuses (the list of tests/cpp/culling_core_host_test.cpp), made from
+    a scene with at least 2 candidates, 2 points, a keypoint and an observation."""
+    nk, n_pt, big = len(scene["kf_flags"]), len(scene["pt_nobs"]), 1 << 28
+    c = int(scene["cand_kf"][0])
+    out = []
+
+    def brk(what, field, index, value):
+        s = {k: (np.array(v, copy=True) if isinstance(v, np.ndarray) else v) for k, v in scene.items()}
+        if index is None:
+            s[field] = value
+        else:
+            s[field][index] = value
+        out.append((what, s))
+    brk("a point index at the end of the stream", "kp_point", 0, n_pt)
+    brk("a point index far past the end", "kp_point", 0, big)
+    brk("a point index below -1", "kp_point", 0, -2)
+    brk("an observation slot at the end", "obs", 0, (int(scene["obs"][0]) & ~0xffff) | nk)
+    brk("an observation slot past the end", "obs", 0, int(scene["obs"][0]) | 0xffff)
+    brk("descending keypoint offsets", "kp_start", 1, int(scene["kp_start"][2]) + 1)
+    brk("a keypoint offset past the total", "kp_start", 1, big)
+    brk("descending observation offsets", "obs_start", 1, int(scene["obs_start"][2]) + 1)
+    brk("a negative observation offset", "obs_start", 1, -big)
+    brk("a candidate whose prev lies outside the snapshot", "kf_prev", c, nk)
+    brk("a candidate whose next is below -1", "kf_next", c, -2)
+    brk("cur_kf out of range", "cur", None, nk)
+    brk("a negative cur_kf", "cur", None, -1)
+    brk("a candidate slot past the end", "cand_kf", 0, big)
+    brk("an observation count of 2^30", "pt_nobs", 0, 1 << 30)
+    brk("a candidate listed twice", "cand_kf", 1, c)
+    return out
+
+
+def untouched(scenes, b, o, fill=77):
+    """Whether stream b's ranges of the flat result arrays o (every field but status and n_culled, which a refused stream gets) still
+    hold the fill value. The ranges are cut by the sizes of the scenes, not through the offsets of the snapshot."""
+    size = dict(n_kf="kf_flags", n_cand="cand_kf", n_pt="pt_nobs", n_obs="obs")
+    ok = True
+    for f, total in M._OUT_LEN.items():
+        if total == "batch":
+            continue
+        lo = sum(len(s[size[total]]) for s in scenes[:b])
+        ok = ok and bool((np.asarray(o[f])[lo:lo + len(scenes[b][size[total]])] == fill).all())
+    return ok
+
+
 # ---- random batches -----------------------------------------------------------------------------------------------------------------------
 CHECKED = ("cand_reason", "cand_redundant", "cand_mps", "n_culled", "culled_order", "kf_bad", "kf_to_be_erased", "kf_prev_out", "kf_next_out",
            "kf_repreint", "pt_nobs_out", "pt_bad_out", "obs_alive")

@@ -2,9 +2,11 @@
 literal checker tests/kf_culling_ref.py in every output, on the hand-built scenes of tests/kf_culling_cases.py, on the sizes at which
 the kernels take another path (read from viorb_key_frame_culling_shape), on batches of unequal streams and on 300 random streams whose
 conditions are asserted on the checker's output first. cand_recounted has no counterpart in the reference: it is 1 exactly for the
-candidates that no skip test removed, which the ordered phase counts itself. Every snapshot here is valid."""
+candidates that no skip test removed, which the ordered phase counts itself. One test puts every kind of broken snapshot between two
+valid streams; every other snapshot here is valid."""
 import numpy as np
 import pytest
+from viorb_amd import capi
 from viorb_amd import culling as M
 import kf_culling_ref as T
 import kf_culling_cases as K
@@ -76,6 +78,25 @@ def test_batches_of_unequal_streams(n):
     assert len(scenes) == n
     for mono in (True, False):
         _check(scenes, mono, host_form=n == 3)
+
+
+def test_a_broken_snapshot_is_refused_alone_between_two_good_streams():
+    """Every kind of broken snapshot of kf_culling_cases.broken in the middle of three streams: the device form refuses it alone and
+    leaves its ranges of every output array as they were; the host-buffer form copies its zeroed device outputs over a refused stream's
+    rows (DESIGN.md "Map culling"), so only its statuses and the neighbours are asserted."""
+    good, (name, other) = K.breakable_scene(), next((c[0], c[1]) for c in K.CASES if c[0] == "shrinking_mps_ab")
+    e_good, e_other = T.key_frame_culling(good, True), K.expected(name)
+    for what, bad in K.broken(good):
+        scenes = [other, bad, good]
+        bt = M.CullBatch(scenes, True)
+        bt.run()
+        got = bt.results()
+        assert got[1] == dict(status=capi.ERR_INVALID_ARG, n_culled=0), what
+        assert K.untouched(scenes, 1, {f: v.cpu().numpy() for f, v in bt.o.items()}), what
+        assert K.differences(got[0], e_other) == [] and K.differences(got[2], e_good) == [], what
+        host = M.key_frame_culling(scenes, True)
+        assert [h["status"] for h in host] == [0, capi.ERR_INVALID_ARG, 0], what
+        assert K.differences(host[0], e_other) == [] and K.differences(host[2], e_good) == [], what
 
 
 def test_three_hundred_random_streams():

@@ -77,6 +77,23 @@ def test_host_core_equals_the_checker_on_random_streams_in_one_batch():
         assert rec.any() and not rec.all() and (rec == (np.concatenate([e["cand_reason"] for e in exp]) >= T.KEPT)).all()
 
 
+def test_host_core_refuses_a_broken_snapshot_alone_between_two_good_streams():
+    good, (name, other) = K.breakable_scene(), next((c[0], c[1]) for c in K.CASES if c[0] == "shrinking_mps_ab")
+    e_good, e_other = T.key_frame_culling(good, True), K.expected(name)
+    kinds = K.broken(good)
+    assert len(kinds) == 16
+    for what, bad in kinds:
+        scenes = [other, bad, good]
+        P = M.pack(scenes)
+        flat = M._run_host(viorb_amd.lib().viorb_debug_key_frame_culling_host, P, True)
+        got = M.split(P, flat)
+        assert got[1] == dict(status=capi.ERR_INVALID_ARG, n_culled=0), what
+        assert K.untouched(scenes, 1, flat), what
+        assert K.differences(got[0], e_other) == [] and K.differences(got[2], e_good) == [], what
+    # the helper tells a written range from an untouched one
+    assert not K.untouched(scenes, 0, flat) and not K.untouched(scenes, 2, flat)
+
+
 def test_map_point_codes_and_the_found_ratio_identity():
     rng = np.random.default_rng(2)
     f = np.concatenate([[0, 0, 1, 1, 1, 5, 4194303, 4194303, 4194304, 4194303, 16777215 // 4], rng.integers(0, 2 ** 22, 3000), rng.integers(0, 40, 3000)])

@@ -17,7 +17,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import viorb_amd
-from viorb_amd import capi
+from viorb_amd import capi, snapshot as S
 from viorb_amd import culling as M
 from viorb_amd.synth import make_culling_problem
 
@@ -56,16 +56,6 @@ def literal_exe(given):
     return exe
 
 
-def write_snapshot(P, mono, path):
-    with open(path, "wb") as f:
-        f.write(np.array([P[k] for k in capi.CULL_MAP_INTS] + [int(mono), 0], np.int32).tobytes())
-        for k in capi.CULL_MAP_ARRAYS:
-            n = {"kf_start": P["batch"] + 1, "cand_start": P["batch"] + 1, "pt_start": P["batch"] + 1, "cur_kf": P["batch"], "vins_inited": P["batch"],
-                 "th_depth": P["batch"], "cand_kf": P["n_cand"], "kp_start": P["n_cand"] + 1, "kp_point": P["n_kp"], "kp_octave": P["n_kp"], "kp_depth": P["n_kp"],
-                 "pt_nobs": P["n_pt"], "pt_bad": P["n_pt"], "obs_start": P["n_pt"] + 1, "obs": P["n_obs"]}.get(k, P["n_kf"])
-            f.write(P[k][:n].tobytes())
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -99,7 +89,7 @@ def main():
         Pc = P if nb == B else M.pack(scenes[:nb])
         with tempfile.TemporaryDirectory() as d:
             path = os.path.join(d, "snapshot.bin")
-            write_snapshot(Pc, True, path)
+            S.write_snapshot(path, [Pc[k] for k in capi.CULL_MAP_INTS] + [1, 0], Pc, capi.CULL_MAP_ARRAYS)          # monocular
             out = subprocess.run([exe, "time", path, "3"], capture_output=True, text=True, check=True).stdout
         emit(dict(what="one CPU thread, -O2", map=name, **json.loads(out)))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)

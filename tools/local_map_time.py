@@ -18,7 +18,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import viorb_amd
-from viorb_amd import capi
+from viorb_amd import capi, snapshot as S
 from viorb_amd import local_map as M
 
 
@@ -86,16 +86,6 @@ def literal_exe(given):
     return exe
 
 
-def write_snapshot(P, path):
-    B = P["batch"]
-    n = dict(kf_start=B + 1, pt_start=B + 1, covis10=P["n_kf"] * 10, child_start=P["n_kf"] + 1, child_kf=P["n_child"], kp_start=P["n_kf"] + 1, kp_point=P["n_kp"],
-             pt_bad=P["n_pt"], obs_start=P["n_pt"] + 1, obs=P["n_obs"], frame_point=B * P["cap"], frame_count=B, prev_lkf=B * P["lcap"], prev_n_lkf=B, prev_ref_kf=B)
-    with open(path, "wb") as f:
-        f.write(np.array([P[k] for k in capi.LOCAL_MAP_INTS] + [P["cap"], P["lcap"], P["pcap"]], np.int32).tobytes())
-        for k in capi.LOCAL_MAP_ARRAYS:
-            f.write(P[k][:n.get(k, P["n_kf"])].tobytes())
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -134,7 +124,7 @@ def main():
         Pc = P if nb == B else M.pack(scenes[:nb])
         with tempfile.TemporaryDirectory() as d:
             path = os.path.join(d, "snapshot.bin")
-            write_snapshot(Pc, path)
+            S.write_snapshot(path, [Pc[k] for k in capi.LOCAL_MAP_INTS] + [Pc["cap"], Pc["lcap"], Pc["pcap"]], Pc, capi.LOCAL_MAP_ARRAYS)
             out = subprocess.run([exe, "time", path, "3"], capture_output=True, text=True, check=True).stdout
         emit(dict(what="one CPU thread, -O2", for_streams=B, **json.loads(out)))           # "streams": how many of them were timed
     os.makedirs(os.path.dirname(a.out), exist_ok=True)

@@ -20,15 +20,15 @@ enum { CULL_WAVE = 64, CULL_PREP_THREADS = 256, CULL_ORDERED_THREADS = 1024, CUL
 __global__ __launch_bounds__(CULL_PREP_THREADS) void k_cull_prepare(CullMap M, CullWork W) {
     const int b = blockIdx.x, t = threadIdx.x, nt = CULL_PREP_THREADS;
     int ok = __syncthreads_and(cull_validate_ranges(M, b, t, nt));
-    CullStream S = {0, 0, 0, 0, 0, 0};
+    CullStream S = CullStream();
     if (ok) { S = cull_stream(M, b); ok = __syncthreads_and(cull_validate_offsets(M, S, b, t, nt)); }
     if (ok) ok = __syncthreads_and(cull_validate_entries(M, S, t, nt));
     if (ok) {
         cull_prepare(M, S, W, t, nt);
         __syncthreads();                                             // every slot of cand_of_kf holds -1 (plain stores of this workgroup, one CU)
-        cull_prepare_candidates(M, S, W, t, nt);
+        snap_distinct_fill(M.cand_kf + S.c0, S.nc, W.cand_of_kf + S.k0, t, nt);
         __syncthreads();
-        ok = __syncthreads_and(cull_validate_distinct(M, S, W, t, nt));
+        ok = __syncthreads_and(snap_distinct_check(M.cand_kf + S.c0, S.nc, W.cand_of_kf + S.k0, t, nt));
     }
     if (t == 0) W.ok[b] = ok;
 }
@@ -46,10 +46,9 @@ __device__ __forceinline__ void cull_block_sum2(int& a, int& b, int (*s_part)[2]
 }
 
 // blockIdx.x = stream; the candidates in order. Thread 0 holds the links and evaluates the skip tests; a count or an erase spreads the
-// candidate's keypoints over the workgroup. What one phase writes to global memory the next one reads after a __syncthreads(): the
-// workgroup runs on one CU, whose L1 its wavefronts share, and __syncthreads() carries the workgroup-scope release and acquire and waits
-// for the outstanding stores, so plain stores need nothing more. The words the erase step changes with atomics (point and observation
-// words) are read with cull_ld, which is served by L2 where the atomics execute.
+// candidate's keypoints over the workgroup. What one phase writes to global memory with plain stores the next one reads after a
+// __syncthreads(); the words the erase step changes with atomics (point and observation words) are read with snap_ld_agent
+// (map_snapshot_core.h has the reasoning for both).
 __global__ __launch_bounds__(CULL_ORDERED_THREADS) void k_cull_ordered(CullMap M, CullWork W, CullOut R, int monocular) {
     __shared__ int s_part[CULL_ORDERED_THREADS / CULL_WAVE][2];
     __shared__ int s_reason;
@@ -118,9 +117,6 @@ CullLayout cull_layout(void* base, int batch, int n_kf, int n_cand, int n_pt, in
     L.total = Y.end();
     return L;
 }
-bool cull_sizes_ok(int batch, int n_kf, int n_cand, int n_kp, int n_pt, int n_obs) {
-    return batch >= 1 && batch <= 65535 && n_kf >= 0 && n_cand >= 0 && n_kp >= 0 && n_pt >= 0 && n_obs >= 0;
-}
 
 int cull_check_map(const viorb_cull_map* m, int monocular) {
     VIORB_REQUIRE(m, "null snapshot");
@@ -162,7 +158,7 @@ int mpc_check(const void* bad, const void* found, const void* visible, const voi
 extern "C" {
 
 size_t viorb_key_frame_culling_workspace_bytes(int batch, int n_kf, int n_cand, int n_pt, int n_obs) {
-    if (!cull_sizes_ok(batch, n_kf, n_cand, 0, n_pt, n_obs)) return 0;
+    if (batch < 1 || batch > 65535 || n_kf < 0 || n_cand < 0 || n_pt < 0 || n_obs < 0) return 0;
     return cull_layout(nullptr, batch, n_kf, n_cand, n_pt, n_obs).total;
 }
 
@@ -175,9 +171,8 @@ int viorb_key_frame_culling_shape(int32_t* out4) {
 int viorb_key_frame_culling_device(const viorb_cull_map* map, int monocular, const viorb_cull_result* result, void* workspace, size_t workspace_bytes,
                                    void* stream) {
     VIORB_TRY(cull_check_map(map, monocular));
-    VIORB_REQUIRE(workspace && ((uintptr_t)workspace & 255) == 0 &&
-                      workspace_bytes >= cull_layout(nullptr, map->batch, map->n_kf, map->n_cand, map->n_pt, map->n_obs).total,
-                  "workspace smaller than viorb_key_frame_culling_workspace_bytes or not 256-byte aligned");
+    VIORB_REQUIRE_WORKSPACE(workspace, workspace_bytes, cull_layout(nullptr, map->batch, map->n_kf, map->n_cand, map->n_pt, map->n_obs).total,
+                            "viorb_key_frame_culling_workspace_bytes");
     VIORB_TRY(require_device());
     hipStream_t st = (hipStream_t)stream;
     const CullMap M = cull_map(*map);

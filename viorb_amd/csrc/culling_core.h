@@ -11,7 +11,7 @@
 #pragma once
 #include <stdint.h>
 #include <math.h>
-#include "mapping_core.h"           // MAP_HD
+#include "map_snapshot_core.h"      // the snapshot's layout, its observation word, the validator's checks, the memory shim
 
 namespace viorb {
 
@@ -20,19 +20,12 @@ enum { KFC_FIRST_KF = 0, KFC_TIME_GAP = 1, KFC_BEFORE_CURRENT = 2, KFC_RECENT = 
 enum { MPC_KEEP = 0, MPC_DROP_BAD = 1, MPC_CULL_FOUND_RATIO = 2, MPC_CULL_FEW_OBS = 3, MPC_RETIRE = 4 };
 enum { CULL_KF_FIRST = 1, CULL_KF_NOT_ERASE = 2 };                              // kf_flags
 enum { CULL_ST_BAD = 1, CULL_ST_TO_BE_ERASED = 2, CULL_ST_REPREINT = 4 };       // the working state of a key frame
-enum { CULL_MAX_KF = 65535, CULL_NOBS_LIMIT = 1 << 30 };
+enum { CULL_NOBS_LIMIT = 1 << 30 };
 
-// An observation word: bits 0-15 the key-frame slot, 16-23 the octave of that key frame's keypoint, bit 24 mvuRight >= 0. The working
-// copy adds bit 31: the observation is still in mObservations.
-static const uint32_t CULL_OBS_STEREO = 1u << 24, CULL_OBS_ALIVE = 1u << 31;
-MAP_HD uint32_t cull_obs_pack(int slot, int octave, int stereo) { return (uint32_t)slot | ((uint32_t)octave << 16) | (stereo ? CULL_OBS_STEREO : 0u); }
-MAP_HD int cull_obs_slot(uint32_t w) { return (int)(w & 0xffffu); }
-MAP_HD int cull_obs_octave(uint32_t w) { return (int)((w >> 16) & 0xffu); }
-MAP_HD int cull_obs_weight(uint32_t w) { return (w & CULL_OBS_STEREO) ? 2 : 1; }      // AddObservation / EraseObservation: nObs += 2 when stereo
 // A point word: nObs in bits 1-31 (two's complement), isBad() in bit 0; |nObs| < 2^30 (the validator), so nothing overflows.
-MAP_HD int32_t cull_pt_pack(int32_t nobs, int bad) { return (int32_t)(((uint32_t)nobs << 1) | (bad ? 1u : 0u)); }
-MAP_HD int32_t cull_pt_nobs(int32_t w) { return w >> 1; }
-MAP_HD int cull_pt_bad(int32_t w) { return w & 1; }
+VIORB_HD int32_t cull_pt_pack(int32_t nobs, int bad) { return (int32_t)(((uint32_t)nobs << 1) | (bad ? 1u : 0u)); }
+VIORB_HD int32_t cull_pt_nobs(int32_t w) { return w >> 1; }
+VIORB_HD int cull_pt_bad(int32_t w) { return w & 1; }
 
 // The snapshot (viorb_cull_map) and the working state (the workspace; host: plain arrays)
 struct CullMap {
@@ -44,112 +37,62 @@ struct CullMap {
 };
 struct CullWork {
     int32_t* pt; uint32_t* obs;                          // [n_pt] point words, [n_obs] observation words with the alive bit
-    int32_t* cand_of_kf; int32_t* prev; int32_t* next;   // [n_kf]: the candidate ordinal of a slot or -1 (the validator: none twice); the current links
+    int32_t* cand_of_kf; int32_t* prev; int32_t* next;   // [n_kf]: the candidate ordinal of a slot or -1 (the validator's mark: none twice); the current links
     uint8_t* kf_state;                                   // [n_kf] CULL_ST_*
     int32_t* ok;                                         // [batch]
 };
-struct CullStream { int k0, nk, c0, nc, p0, np; };       // the stream's ranges of key frames, candidates and points
+struct CullStream : SnapStream { int c0, nc; };          // the stream's ranges of key frames and points, and of candidates
 
-// ---- loads and read-modify-writes of the working state ---------------------------------------------------------------------------------
-// On the device the erase step updates point and observation words with integer atomics, which execute in L2. The ordered kernel reads
-// those words with relaxed agent-scope loads (L2-served), so that no wave reads an L1 line from before another wave's atomic.
-template <class T> MAP_HD T cull_ld(const T* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-    return *p;
-#endif
-}
-MAP_HD uint32_t cull_fetch_and(uint32_t* p, uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return atomicAnd(p, v);
-#else
-    const uint32_t o = *p; *p = o & v; return o;
-#endif
-}
-MAP_HD int32_t cull_fetch_add(int32_t* p, int32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return atomicAdd(p, v);
-#else
-    const int32_t o = *p; *p = o + v; return o;
-#endif
-}
-MAP_HD void cull_or(int32_t* p, int32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    atomicOr(p, v);
-#else
-    *p |= v;
-#endif
-}
-
-// ---- the stream validator --------------------------------------------------------------------------------------------------------------
-// Three steps; thread `tid` of `nt` checks its share and the caller ANDs the shares before the next step (the host calls with 0 of 1).
-// No step reads through an index that an earlier step has not accepted.
-// Step 1: the batch-level offsets of streams 0..b are non-negative, ascending and inside the totals, and so are the nested offsets at
-// the streams' boundaries (kp_start at cand_start[i], obs_start at pt_start[i]). With step 2 this keeps the key frames, candidates,
-// points, keypoints and observations of two accepted streams apart whatever a refused stream between them holds.
-MAP_HD bool cull_validate_ranges(const CullMap& M, int b, int tid, int nt) {
+// ---- the stream validator: the steps of map_snapshot_core.h on this snapshot's arrays ----------------------------------------------------
+// The erase step updates point and observation words with integer atomics, so the ordered kernel reads them with snap_ld_agent.
+// Step 1: kp_start is nested under cand_start, obs_start under pt_start.
+VIORB_HD bool cull_validate_ranges(const CullMap& M, int b, int tid, int nt) {
     bool ok = true;
     for (int i = tid; i <= b; i += nt) {
-        ok = ok && M.kf_start[i] >= 0 && M.kf_start[i] <= M.kf_start[i + 1] && M.kf_start[i + 1] <= M.n_kf;
-        const int c0 = M.cand_start[i], c1 = M.cand_start[i + 1], p0 = M.pt_start[i], p1 = M.pt_start[i + 1];
-        if (!(c0 >= 0 && c0 <= c1 && c1 <= M.n_cand && p0 >= 0 && p0 <= p1 && p1 <= M.n_pt)) { ok = false; continue; }
-        ok = ok && M.kp_start[c0] >= 0 && M.kp_start[c0] <= M.kp_start[c1] && M.kp_start[c1] <= M.n_kp;
-        ok = ok && M.obs_start[p0] >= 0 && M.obs_start[p0] <= M.obs_start[p1] && M.obs_start[p1] <= M.n_obs;
+        ok = ok && snap_span(M.kf_start, i, i + 1, M.n_kf);
+        if (!(snap_span(M.cand_start, i, i + 1, M.n_cand) && snap_span(M.pt_start, i, i + 1, M.n_pt))) { ok = false; continue; }
+        ok = ok && snap_span(M.kp_start, M.cand_start[i], M.cand_start[i + 1], M.n_kp);
+        ok = ok && snap_span(M.obs_start, M.pt_start[i], M.pt_start[i + 1], M.n_obs);
     }
     return ok;
 }
-MAP_HD CullStream cull_stream(const CullMap& M, int b) {
+VIORB_HD CullStream cull_stream(const CullMap& M, int b) {
     CullStream S;
-    S.k0 = M.kf_start[b]; S.nk = M.kf_start[b + 1] - S.k0; S.c0 = M.cand_start[b]; S.nc = M.cand_start[b + 1] - S.c0;
-    S.p0 = M.pt_start[b]; S.np = M.pt_start[b + 1] - S.p0;
+    static_cast<SnapStream&>(S) = snap_stream(M.kf_start, M.pt_start, b);
+    S.c0 = M.cand_start[b]; S.nc = M.cand_start[b + 1] - S.c0;
     return S;
 }
-// Step 2: the nested offsets, the candidates' slots and links, the current key frame, the observation counts.
-MAP_HD bool cull_validate_offsets(const CullMap& M, const CullStream& S, int b, int tid, int nt) {
-    bool ok = S.nk >= 1 && S.nk <= CULL_MAX_KF && M.cur_kf[b] >= 0 && M.cur_kf[b] < S.nk;
-    for (int j = tid; j <= S.nc; j += nt) {
-        const int a = M.kp_start[S.c0 + j];
-        ok = ok && a >= 0 && a <= M.n_kp && (j == S.nc || a <= M.kp_start[S.c0 + j + 1]);
-        if (j < S.nc) {
-            const int c = M.cand_kf[S.c0 + j];
-            if (c < 0 || c >= S.nk) { ok = false; continue; }
-            const int p = M.kf_prev[S.k0 + c], n = M.kf_next[S.k0 + c];
-            ok = ok && p >= -1 && p < S.nk && n >= -1 && n < S.nk;
-        }
+// Step 2: at least one key frame and the current one among them, the nested offsets, the candidates' slots and their links (only
+// candidates' links are followed), the observation counts.
+VIORB_HD bool cull_validate_offsets(const CullMap& M, const CullStream& S, int b, int tid, int nt) {
+    bool ok = S.nk >= 1 && S.nk <= SNAP_MAX_KF && M.cur_kf[b] >= 0 && M.cur_kf[b] < S.nk;
+    ok &= snap_offsets_run(M.kp_start, S.c0, S.nc, M.n_kp, tid, nt);
+    ok &= snap_offsets_run(M.obs_start, S.p0, S.np, M.n_obs, tid, nt);
+    for (int j = tid; j < S.nc; j += nt) {
+        const int c = M.cand_kf[S.c0 + j];
+        if (c < 0 || c >= S.nk) { ok = false; continue; }
+        const int p = M.kf_prev[S.k0 + c], n = M.kf_next[S.k0 + c];
+        ok &= snap_slot_or_none(p, S.nk) && snap_slot_or_none(n, S.nk);
     }
-    for (int p = tid; p <= S.np; p += nt) {
-        const int a = M.obs_start[S.p0 + p];
-        ok = ok && a >= 0 && a <= M.n_obs && (p == S.np || a <= M.obs_start[S.p0 + p + 1]);
-        if (p < S.np) { const int32_t n = M.pt_nobs[S.p0 + p]; ok = ok && n > -CULL_NOBS_LIMIT && n < CULL_NOBS_LIMIT; }
-    }
+    for (int p = tid; p < S.np; p += nt) { const int32_t n = M.pt_nobs[S.p0 + p]; ok &= n > -CULL_NOBS_LIMIT && n < CULL_NOBS_LIMIT; }
     return ok;
 }
 // Step 3: every point index of the keypoint tables and every slot of the observation words.
-MAP_HD bool cull_validate_entries(const CullMap& M, const CullStream& S, int tid, int nt) {
-    bool ok = true;
-    for (int i = M.kp_start[S.c0] + tid, e = M.kp_start[S.c0 + S.nc]; i < e; i += nt) ok = ok && M.kp_point[i] >= -1 && M.kp_point[i] < S.np;
-    for (int o = M.obs_start[S.p0] + tid, e = M.obs_start[S.p0 + S.np]; o < e; o += nt) ok = ok && cull_obs_slot(M.obs[o]) < S.nk;
+VIORB_HD bool cull_validate_entries(const CullMap& M, const CullStream& S, int tid, int nt) {
+    bool ok = snap_entries_within(M.kp_point, M.kp_start[S.c0], M.kp_start[S.c0 + S.nc], -1, S.np, tid, nt);
+    ok &= snap_obs_slots_below(M.obs, M.obs_start[S.p0], M.obs_start[S.p0 + S.np], S.nk, tid, nt);
     return ok;
 }
-// The working state of the share of `tid`. cand_of_kf is filled by a second pass (cull_prepare_candidates) after every slot holds -1.
-MAP_HD void cull_prepare(const CullMap& M, const CullStream& S, const CullWork& W, int tid, int nt) {
+// The working state of the share of `tid`. cand_of_kf holds -1 in every slot before step 4 (snap_distinct_fill of cand_kf, after a
+// barrier) gives the candidates' slots their ordinals; a key frame listed twice is refused by snap_distinct_check.
+VIORB_HD void cull_prepare(const CullMap& M, const CullStream& S, const CullWork& W, int tid, int nt) {
     for (int p = tid; p < S.np; p += nt) W.pt[S.p0 + p] = cull_pt_pack(M.pt_nobs[S.p0 + p], M.pt_bad[S.p0 + p] != 0);
-    for (int o = M.obs_start[S.p0] + tid, e = M.obs_start[S.p0 + S.np]; o < e; o += nt) W.obs[o] = (M.obs[o] & 0x01ffffffu) | CULL_OBS_ALIVE;
+    for (int o = M.obs_start[S.p0] + tid, e = M.obs_start[S.p0 + S.np]; o < e; o += nt) W.obs[o] = (M.obs[o] & 0x01ffffffu) | SNAP_OBS_ALIVE;
     for (int k = tid; k < S.nk; k += nt) { W.cand_of_kf[S.k0 + k] = -1; W.prev[S.k0 + k] = M.kf_prev[S.k0 + k]; W.next[S.k0 + k] = M.kf_next[S.k0 + k]; W.kf_state[S.k0 + k] = 0; }
-}
-MAP_HD void cull_prepare_candidates(const CullMap& M, const CullStream& S, const CullWork& W, int tid, int nt) {
-    for (int j = tid; j < S.nc; j += nt) W.cand_of_kf[S.k0 + M.cand_kf[S.c0 + j]] = j;
-}
-// A key frame listed twice is refused: one of the two ordinals lost the slot.
-MAP_HD bool cull_validate_distinct(const CullMap& M, const CullStream& S, const CullWork& W, int tid, int nt) {
-    bool ok = true;
-    for (int j = tid; j < S.nc; j += nt) ok = ok && W.cand_of_kf[S.k0 + M.cand_kf[S.c0 + j]] == j;
-    return ok;
 }
 
 // ---- the skip tests (:1697-1750) on the current links: a reason, or -1 when the candidate is counted -----------------------------------
-MAP_HD int cull_skip(const CullMap& M, const CullStream& S, const CullWork& W, int c, int cur, bool vins_inited) {
+VIORB_HD int cull_skip(const CullMap& M, const CullStream& S, const CullWork& W, int c, int cur, bool vins_inited) {
     if (M.kf_flags[S.k0 + c] & CULL_KF_FIRST) return KFC_FIRST_KF;
     const int prev = W.prev[S.k0 + c], next = W.next[S.k0 + c];
     if (prev >= 0 && next >= 0 && !vins_inited && fabs(M.kf_time[S.k0 + next] - M.kf_time[S.k0 + prev]) > 0.5) return KFC_TIME_GAP;
@@ -159,48 +102,48 @@ MAP_HD int cull_skip(const CullMap& M, const CullStream& S, const CullWork& W, i
 }
 
 // ---- the count of one keypoint (:1774-1814): bit 0 nMPs++, bit 1 nRedundantObservations++ ----------------------------------------------
-MAP_HD int cull_count_keypoint(const CullMap& M, const CullStream& S, const CullWork& W, int c, int i, bool monocular, float th_depth) {
+VIORB_HD int cull_count_keypoint(const CullMap& M, const CullStream& S, const CullWork& W, int c, int i, bool monocular, float th_depth) {
     const int p = M.kp_point[i];
     if (p < 0) return 0;
-    const int32_t w = cull_ld(&W.pt[S.p0 + p]);
+    const int32_t w = snap_ld_agent(&W.pt[S.p0 + p]);
     if (cull_pt_bad(w)) return 0;
     if (!monocular) { const float d = M.kp_depth[i]; if (d > th_depth || d < 0) return 0; }
     const int level = M.kp_octave[i];
     int n = 0;
     for (int o = M.obs_start[S.p0 + p], e = M.obs_start[S.p0 + p + 1]; o < e; o++) {
-        const uint32_t ow = cull_ld(&W.obs[o]);
-        if (!(ow & CULL_OBS_ALIVE)) continue;
-        if (cull_obs_slot(ow) == c) continue;
-        if (cull_obs_octave(ow) <= level + 1) n++;           // the break at thObs does not change nObs >= thObs
+        const uint32_t ow = snap_ld_agent(&W.obs[o]);
+        if (!(ow & SNAP_OBS_ALIVE)) continue;
+        if (snap_obs_slot(ow) == c) continue;
+        if (snap_obs_octave(ow) <= level + 1) n++;           // the break at thObs does not change nObs >= thObs
     }
     return 1 | ((cull_pt_nobs(w) > 3 && n >= 3) ? 2 : 0);
 }
 
 // :1819, in double as the reference compares an int with 0.9 * int
-MAP_HD bool cull_decide(int redundant, int mps) { return (double)redundant > 0.9 * (double)mps; }
+VIORB_HD bool cull_decide(int redundant, int mps) { return (double)redundant > 0.9 * (double)mps; }
 
 // ---- the erase step of one keypoint (KeyFrame.cc:775-777, MapPoint.cc:118-175) ---------------------------------------------------------
 // The lane that flips the alive bit of the point's observation of c does the erase; an entry that names the same point again finds the
 // bit already clear. When the point goes bad its remaining observations are cleared.
-MAP_HD void cull_erase_keypoint(const CullMap& M, const CullStream& S, const CullWork& W, int c, int i) {
+VIORB_HD void cull_erase_keypoint(const CullMap& M, const CullStream& S, const CullWork& W, int c, int i) {
     const int p = M.kp_point[i];
     if (p < 0) return;
     const int o0 = M.obs_start[S.p0 + p], o1 = M.obs_start[S.p0 + p + 1];
     int delta = 0;
     for (int o = o0; o < o1; o++) {
-        const uint32_t ow = cull_ld(&W.obs[o]);
-        if ((ow & CULL_OBS_ALIVE) && cull_obs_slot(ow) == c && (cull_fetch_and(&W.obs[o], ~CULL_OBS_ALIVE) & CULL_OBS_ALIVE)) delta += cull_obs_weight(ow);
+        const uint32_t ow = snap_ld_agent(&W.obs[o]);
+        if ((ow & SNAP_OBS_ALIVE) && snap_obs_slot(ow) == c && (snap_fetch_and(&W.obs[o], ~SNAP_OBS_ALIVE) & SNAP_OBS_ALIVE)) delta += snap_obs_weight(ow);
     }
     if (delta == 0) return;
-    const int32_t w = cull_fetch_add(&W.pt[S.p0 + p], -2 * delta) - 2 * delta;
+    const int32_t w = snap_fetch_add(&W.pt[S.p0 + p], -2 * delta) - 2 * delta;
     const bool goes_bad = cull_pt_nobs(w) <= 2;                                  // MapPoint.cc:137
     if (!goes_bad) return;
-    cull_or(&W.pt[S.p0 + p], 1);
-    for (int o = o0; o < o1; o++) cull_fetch_and(&W.obs[o], ~CULL_OBS_ALIVE);    // mObservations.clear()
+    snap_or(&W.pt[S.p0 + p], 1);
+    for (int o = o0; o < o1; o++) snap_fetch_and(&W.obs[o], ~SNAP_OBS_ALIVE);    // mObservations.clear()
 }
 
 // ---- the links (KeyFrame.cc:849-875), one thread ---------------------------------------------------------------------------------------
-MAP_HD void cull_unlink(const CullStream& S, const CullWork& W, int c) {
+VIORB_HD void cull_unlink(const CullStream& S, const CullWork& W, int c) {
     const int prev = W.prev[S.k0 + c], next = W.next[S.k0 + c];
     if (prev >= 0) W.next[S.k0 + prev] = next;
     if (next >= 0) W.prev[S.k0 + next] = prev;
@@ -214,7 +157,7 @@ MAP_HD void cull_unlink(const CullStream& S, const CullWork& W, int c) {
 // correctly rounded quotient is below 0.25f exactly when 4 * found < visible: found / visible <= 0.25 - 1 / (4 visible), and 1 / (4 visible)
 // > 2^-26 is more than half an ulp (2^-27) below 0.25, while a quotient >= 0.25 rounds to >= 0.25. visible == 0 gives inf or NaN, neither
 // below 0.25f, as 4 * found < 0 is false.
-MAP_HD int cull_map_point(int bad, int32_t found, int32_t visible, int32_t first_kf_id, int32_t nobs, int32_t cur_kf_id, bool monocular) {
+VIORB_HD int cull_map_point(int bad, int32_t found, int32_t visible, int32_t first_kf_id, int32_t nobs, int32_t cur_kf_id, bool monocular) {
     if (bad) return MPC_DROP_BAD;
     if (4 * (int64_t)found < (int64_t)visible) return MPC_CULL_FOUND_RATIO;
     const int64_t age = (int64_t)cur_kf_id - (int64_t)first_kf_id;
@@ -230,30 +173,30 @@ struct CullOut {
     uint8_t* kf_bad; uint8_t* kf_to_be_erased; int32_t* kf_prev_out; int32_t* kf_next_out; uint8_t* kf_repreint;
     int32_t* pt_nobs_out; uint8_t* pt_bad_out; uint8_t* obs_alive;
 };
-MAP_HD void cull_write_candidate(const CullOut& R, int g, int reason, int redundant, int mps, int recounted) {
+VIORB_HD void cull_write_candidate(const CullOut& R, int g, int reason, int redundant, int mps, int recounted) {
     if (R.cand_reason) R.cand_reason[g] = reason;
     if (R.cand_redundant) R.cand_redundant[g] = redundant;
     if (R.cand_mps) R.cand_mps[g] = mps;
     if (R.cand_recounted) R.cand_recounted[g] = recounted;
 }
 // The state the loop leaves, the share of `tid`
-MAP_HD void cull_write_state(const CullMap& M, const CullStream& S, const CullWork& W, const CullOut& R, int n_culled, int tid, int nt) {
+VIORB_HD void cull_write_state(const CullMap& M, const CullStream& S, const CullWork& W, const CullOut& R, int n_culled, int tid, int nt) {
     for (int k = tid; k < S.nk; k += nt) {
-        const int st = cull_ld(&W.kf_state[S.k0 + k]);
+        const int st = snap_ld_agent(&W.kf_state[S.k0 + k]);
         if (R.kf_bad) R.kf_bad[S.k0 + k] = (st & CULL_ST_BAD) ? 1 : 0;
         if (R.kf_to_be_erased) R.kf_to_be_erased[S.k0 + k] = (st & CULL_ST_TO_BE_ERASED) ? 1 : 0;
         if (R.kf_repreint) R.kf_repreint[S.k0 + k] = (st & CULL_ST_REPREINT) ? 1 : 0;
-        if (R.kf_prev_out) R.kf_prev_out[S.k0 + k] = cull_ld(&W.prev[S.k0 + k]);
-        if (R.kf_next_out) R.kf_next_out[S.k0 + k] = cull_ld(&W.next[S.k0 + k]);
+        if (R.kf_prev_out) R.kf_prev_out[S.k0 + k] = snap_ld_agent(&W.prev[S.k0 + k]);
+        if (R.kf_next_out) R.kf_next_out[S.k0 + k] = snap_ld_agent(&W.next[S.k0 + k]);
     }
     if (R.culled_order) for (int j = n_culled + tid; j < S.nc; j += nt) R.culled_order[S.c0 + j] = -1;
     if (R.pt_nobs_out || R.pt_bad_out)
         for (int p = tid; p < S.np; p += nt) {
-            const int32_t w = cull_ld(&W.pt[S.p0 + p]);
+            const int32_t w = snap_ld_agent(&W.pt[S.p0 + p]);
             if (R.pt_nobs_out) R.pt_nobs_out[S.p0 + p] = cull_pt_nobs(w);
             if (R.pt_bad_out) R.pt_bad_out[S.p0 + p] = (uint8_t)cull_pt_bad(w);
         }
-    if (R.obs_alive) for (int o = M.obs_start[S.p0] + tid, e = M.obs_start[S.p0 + S.np]; o < e; o += nt) R.obs_alive[o] = (cull_ld(&W.obs[o]) & CULL_OBS_ALIVE) ? 1 : 0;
+    if (R.obs_alive) for (int o = M.obs_start[S.p0] + tid, e = M.obs_start[S.p0 + S.np]; o < e; o += nt) R.obs_alive[o] = (snap_ld_agent(&W.obs[o]) & SNAP_OBS_ALIVE) ? 1 : 0;
 }
 
 // The phases of the device form on one host thread, stream by stream: validate and prepare, then the ordered loop. W holds arrays of
@@ -261,10 +204,14 @@ MAP_HD void cull_write_state(const CullMap& M, const CullStream& S, const CullWo
 inline void cull_run_host(const CullMap& M, const CullWork& W, const CullOut& R, bool monocular) {
     for (int b = 0; b < M.batch; b++) {
         bool ok = cull_validate_ranges(M, b, 0, 1);
-        CullStream S = {0, 0, 0, 0, 0, 0};
+        CullStream S = CullStream();
         if (ok) { S = cull_stream(M, b); ok = cull_validate_offsets(M, S, b, 0, 1); }
         ok = ok && cull_validate_entries(M, S, 0, 1);
-        if (ok) { cull_prepare(M, S, W, 0, 1); cull_prepare_candidates(M, S, W, 0, 1); ok = cull_validate_distinct(M, S, W, 0, 1); }
+        if (ok) {
+            cull_prepare(M, S, W, 0, 1);
+            snap_distinct_fill(M.cand_kf + S.c0, S.nc, W.cand_of_kf + S.k0, 0, 1);
+            ok = snap_distinct_check(M.cand_kf + S.c0, S.nc, W.cand_of_kf + S.k0, 0, 1);
+        }
         W.ok[b] = ok;
         if (R.status) R.status[b] = ok ? 0 : -1;
         if (R.n_culled) R.n_culled[b] = 0;

@@ -45,19 +45,19 @@ struct UlmWaveFirst {
 __global__ __launch_bounds__(ULM_PREP_THREADS) void k_ulm_prepare(UlmMap M, UlmWork W) {
     const int b = blockIdx.x, t = threadIdx.x, nt = ULM_PREP_THREADS;
     int ok = __syncthreads_and(ulm_validate_ranges(M, b, t, nt));
-    UlmStream S = {0, 0, 0, 0};
-    if (ok) { S = ulm_stream(M, b); ok = __syncthreads_and(ulm_validate_offsets(M, S, b, t, nt)); }
+    SnapStream S = {0, 0, 0, 0};
+    if (ok) { S = snap_stream(M.kf_start, M.pt_start, b); ok = __syncthreads_and(ulm_validate_offsets(M, S, b, t, nt)); }
     if (ok) ok = __syncthreads_and(ulm_validate_entries(M, S, b, t, nt));
     if (ok) {                                                        // plain stores of this workgroup, one CU: a barrier between fill and check
-        ulm_distinct_fill(M.kf_by_key + S.k0, S.nk, W.mark + S.k0, t, nt);
+        snap_distinct_fill(M.kf_by_key + S.k0, S.nk, W.mark + S.k0, t, nt);
         __syncthreads();
-        ok = __syncthreads_and(ulm_distinct_check(M.kf_by_key + S.k0, S.nk, W.mark + S.k0, t, nt));
+        ok = __syncthreads_and(snap_distinct_check(M.kf_by_key + S.k0, S.nk, W.mark + S.k0, t, nt));
     }
     if (ok) {
         const int32_t* prev = M.prev_lkf + (size_t)b * M.lcap;
-        ulm_distinct_fill(prev, M.prev_n_lkf[b], W.mark + S.k0, t, nt);
+        snap_distinct_fill(prev, M.prev_n_lkf[b], W.mark + S.k0, t, nt);
         __syncthreads();
-        ok = __syncthreads_and(ulm_distinct_check(prev, M.prev_n_lkf[b], W.mark + S.k0, t, nt));
+        ok = __syncthreads_and(snap_distinct_check(prev, M.prev_n_lkf[b], W.mark + S.k0, t, nt));
     }
     if (ok) ulm_prepare(S, W, t, nt);
     if (t == 0) W.info[b * ULM_INFO + ULM_INFO_OK] = ok;
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(ULM_KF_THREADS) void k_ulm_key_frames(UlmMap M, Ulm
     __shared__ int s_size;
     const int b = blockIdx.x, t = threadIdx.x, nt = ULM_KF_THREADS;
     if (!W.info[b * ULM_INFO + ULM_INFO_OK]) { if (t == 0) ulm_write_refused(R, b); return; }      // the whole workgroup
-    const UlmStream S = ulm_stream(M, b);
+    const SnapStream S = snap_stream(M.kf_start, M.pt_start, b);
     const bool lds = S.nk <= ULM_LDS_KF;
     int32_t* votes = lds ? s_votes : W.votes + S.k0;
     int32_t* mark = lds ? s_mark : W.mark + S.k0;
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(ULM_KF_THREADS) void k_ulm_key_frames(UlmMap M, Ulm
     for (int i = t; i < fc; i += nt) cast += ulm_vote_keypoint(M, S, votes, R, b, i);
     if (R.frame_point_out) for (int i = fc + t; i < M.cap; i += nt) R.frame_point_out[(size_t)b * M.cap + i] = -1;
     const int any = __syncthreads_or(cast != 0);                     // also: every atomic add has been performed (s_waitcnt before the barrier)
-    if (R.kf_votes) for (int k = t; k < S.nk; k += nt) R.kf_votes[S.k0 + k] = ulm_ld_votes(&votes[k]);
+    if (R.kf_votes) for (int k = t; k < S.nk; k += nt) R.kf_votes[S.k0 + k] = snap_ld_agent(&votes[k]);
     int n = 0, n_voted = 0, ref = M.prev_ref_kf[b], status = ULM_OK;
     if (!any) {                                                      // :2018
         status = ULM_NO_VOTES; n = M.prev_n_lkf[b];
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(ULM_KF_THREADS) void k_ulm_key_frames(UlmMap M, Ulm
     for (int j0 = 0; j0 < n; j0 += nt) {
         const int j = j0 + t;
         int c = 0;
-        if (j < n) { const int g = S.k0 + ulm_ld(&list[j]); c = M.kp_start[g + 1] - M.kp_start[g]; }
+        if (j < n) { const int g = S.k0 + snap_ld_wg(&list[j]); c = M.kp_start[g + 1] - M.kp_start[g]; }
         int total;
         const int at = entries + ulm_block_scan<ULM_KF_THREADS>(c, total, s_part);
         if (j < n) estart[j] = at;
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(ULM_KF_THREADS) void k_ulm_key_frames(UlmMap M, Ulm
 __global__ __launch_bounds__(ULM_CLAIM_THREADS) void k_ulm_claim_points(UlmMap M, UlmWork W) {
     const int b = blockIdx.y;
     if (!W.info[b * ULM_INFO + ULM_INFO_OK]) return;
-    const UlmStream S = ulm_stream(M, b);
+    const SnapStream S = snap_stream(M.kf_start, M.pt_start, b);
     const int n = W.info[b * ULM_INFO + ULM_INFO_LIST], entries = W.info[b * ULM_INFO + ULM_INFO_ENTRIES];
     const int32_t* list = W.list + S.k0 + b; const int32_t* estart = W.estart + S.k0 + b;
     for (long long pos = (long long)blockIdx.x * ULM_CLAIM_THREADS + threadIdx.x; pos < entries; pos += (long long)gridDim.x * ULM_CLAIM_THREADS)
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(ULM_PT_THREADS) void k_ulm_local_points(UlmMap M, U
     __shared__ int s_part[ULM_PT_THREADS / ULM_WAVE];
     const int b = blockIdx.x, t = threadIdx.x, nt = ULM_PT_THREADS;
     if (!W.info[b * ULM_INFO + ULM_INFO_OK]) return;                 // the whole workgroup; its status is written
-    const UlmStream S = ulm_stream(M, b);
+    const SnapStream S = snap_stream(M.kf_start, M.pt_start, b);
     const int n = W.info[b * ULM_INFO + ULM_INFO_LIST], entries = W.info[b * ULM_INFO + ULM_INFO_ENTRIES];
     const int32_t* list = W.list + S.k0 + b; const int32_t* estart = W.estart + S.k0 + b;
     int n_lpt = 0;
@@ -280,8 +280,7 @@ int viorb_update_local_map_shape(int32_t* out4) {
 int viorb_update_local_map_device(const viorb_local_map_snapshot* map, const viorb_local_map_result* result, int cap, int lcap, int pcap,
                                   void* workspace, size_t workspace_bytes, void* stream) {
     VIORB_TRY(ulm_check(map, cap, lcap, pcap));
-    VIORB_REQUIRE(workspace && ((uintptr_t)workspace & 255) == 0 && workspace_bytes >= ulm_layout(nullptr, map->batch, map->n_kf, map->n_pt).total,
-                  "workspace smaller than viorb_update_local_map_workspace_bytes or not 256-byte aligned");
+    VIORB_REQUIRE_WORKSPACE(workspace, workspace_bytes, ulm_layout(nullptr, map->batch, map->n_kf, map->n_pt).total, "viorb_update_local_map_workspace_bytes");
     VIORB_TRY(require_device());
     hipStream_t st = (hipStream_t)stream;
     const UlmMap M = ulm_map(*map, cap, lcap, pcap);
@@ -361,8 +360,7 @@ int viorb_local_points_gather_device(const viorb_local_map_snapshot* map, const 
     VIORB_REQUIRE(map->pt_start && map->frame_count && result->lpt && result->n_lpt && result->status && result->frame_point_out, "null array");
     VIORB_REQUIRE(map_pts_f && map_pts_desc && pt_nobs && pts_f && pts_desc && pts_count && pts_flags, "null array");
     VIORB_REQUIRE((((uintptr_t)map_pts_f | (uintptr_t)map_pts_desc | (uintptr_t)pts_f | (uintptr_t)pts_desc) & 15) == 0, "point arrays not 16-byte aligned");
-    VIORB_REQUIRE(workspace && ((uintptr_t)workspace & 255) == 0 && workspace_bytes >= viorb_local_points_gather_workspace_bytes(map->n_pt),
-                  "workspace smaller than viorb_local_points_gather_workspace_bytes or not 256-byte aligned");
+    VIORB_REQUIRE_WORKSPACE(workspace, workspace_bytes, viorb_local_points_gather_workspace_bytes(map->n_pt), "viorb_local_points_gather_workspace_bytes");
     VIORB_TRY(require_device());
     UlmGather G;
     G.pt_start = map->pt_start; G.frame_count = map->frame_count; G.lpt = result->lpt; G.n_lpt = result->n_lpt; G.status = result->status;

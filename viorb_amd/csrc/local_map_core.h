@@ -10,12 +10,12 @@
 // so a fresh mark per call stands for them: `mark` for key frames, the first position of a point for map points.
 #pragma once
 #include <stdint.h>
-#include "mapping_core.h"           // MAP_HD
+#include "map_snapshot_core.h"      // the snapshot's layout, its observation word, the validator's checks, the memory shim
 
 namespace viorb {
 
 enum { ULM_OK = 0, ULM_NO_VOTES = 1, ULM_OVERFLOW = 2, ULM_INVALID = -1 };     // status (VIORB_ULM_* of include/viorb_local_map.h)
-enum { ULM_MAX_KF = 65535, ULM_LIMIT = 80, ULM_COVIS = 10, ULM_NO_POS = 0x7fffffff };
+enum { ULM_LIMIT = 80, ULM_COVIS = 10, ULM_NO_POS = 0x7fffffff };
 enum { ULM_INFO_OK = 0, ULM_INFO_LIST = 1, ULM_INFO_STATUS = 2, ULM_INFO_ENTRIES = 3, ULM_INFO = 4 };       // info[b][4]
 
 // The snapshot (viorb_local_map_snapshot with the three row lengths) and the working state (the workspace; host: plain arrays)
@@ -39,169 +39,100 @@ struct UlmOut {
     int32_t* lkf; int32_t* n_lkf; int32_t* n_voted; int32_t* ref_kf; int32_t* lpt; int32_t* n_lpt; int32_t* status;
     int32_t* frame_point_out; int32_t* kf_votes;
 };
-struct UlmStream { int k0, nk, p0, np; };                // the stream's ranges of key frames and points
 
-// ---- loads and stores of what one phase's lanes write and read among themselves ----------------------------------------------------------
-// On the device the neighbour loop is run by one wavefront whose lanes read marks and list entries that another lane has just written;
-// these go through relaxed workgroup-scope atomics with a workgroup fence after a push, so the compiler keeps them in memory and in order
-// (a workgroup runs on one CU: its wavefronts share the L1 and the LDS).
-MAP_HD int32_t ulm_ld(const int32_t* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-    return *p;
-#endif
-}
-// A vote count after the atomic adds, which execute in L2: an agent-scope load is served there, past an L1 line from before them.
-MAP_HD int32_t ulm_ld_votes(const int32_t* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-    return *p;
-#endif
-}
-MAP_HD void ulm_st(int32_t* p, int32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-    *p = v;
-#endif
-}
-MAP_HD void ulm_fence() {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-#endif
-}
-MAP_HD void ulm_add(int32_t* p, int32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    atomicAdd(p, v);
-#else
-    *p += v;
-#endif
-}
-MAP_HD void ulm_min(int32_t* p, int32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    atomicMin(p, v);
-#else
-    if (v < *p) *p = v;
-#endif
-}
-
-// ---- the stream validator --------------------------------------------------------------------------------------------------------------
-// Thread `tid` of `nt` checks its share and the caller ANDs the shares before the next step (the host calls with 0 of 1). No step reads
-// through an index that an earlier step has not accepted.
-// Step 1: the batch-level offsets of streams 0..b are non-negative, ascending and inside the totals, and so are the nested offsets at
-// the streams' boundaries. With step 2 this keeps the arrays of two accepted streams apart whatever a refused stream between them holds.
-MAP_HD bool ulm_validate_ranges(const UlmMap& M, int b, int tid, int nt) {
+// ---- the stream validator: the steps of map_snapshot_core.h on this snapshot's arrays ----------------------------------------------------
+// In the neighbour loop one wavefront's lanes read marks and list entries that another lane has just written (snap_ld_wg, snap_st_wg,
+// snap_fence_wg after a push); the votes are integer atomic adds and are read with snap_ld_agent.
+// Step 1: kp_start and child_start are nested under kf_start, obs_start under pt_start.
+VIORB_HD bool ulm_validate_ranges(const UlmMap& M, int b, int tid, int nt) {
     bool ok = true;
     for (int i = tid; i <= b; i += nt) {
-        const int k0 = M.kf_start[i], k1 = M.kf_start[i + 1], p0 = M.pt_start[i], p1 = M.pt_start[i + 1];
-        if (!(k0 >= 0 && k0 <= k1 && k1 <= M.n_kf && p0 >= 0 && p0 <= p1 && p1 <= M.n_pt)) { ok = false; continue; }
-        ok = ok && M.kp_start[k0] >= 0 && M.kp_start[k0] <= M.kp_start[k1] && M.kp_start[k1] <= M.n_kp;
-        ok = ok && M.child_start[k0] >= 0 && M.child_start[k0] <= M.child_start[k1] && M.child_start[k1] <= M.n_child;
-        ok = ok && M.obs_start[p0] >= 0 && M.obs_start[p0] <= M.obs_start[p1] && M.obs_start[p1] <= M.n_obs;
+        if (!(snap_span(M.kf_start, i, i + 1, M.n_kf) && snap_span(M.pt_start, i, i + 1, M.n_pt))) { ok = false; continue; }
+        const int k0 = M.kf_start[i], k1 = M.kf_start[i + 1];
+        ok = ok && snap_span(M.kp_start, k0, k1, M.n_kp) && snap_span(M.child_start, k0, k1, M.n_child);
+        ok = ok && snap_span(M.obs_start, M.pt_start[i], M.pt_start[i + 1], M.n_obs);
     }
     return ok;
 }
-MAP_HD UlmStream ulm_stream(const UlmMap& M, int b) {
-    UlmStream S;
-    S.k0 = M.kf_start[b]; S.nk = M.kf_start[b + 1] - S.k0; S.p0 = M.pt_start[b]; S.np = M.pt_start[b + 1] - S.p0;
-    return S;
-}
-MAP_HD bool ulm_slot_or_none(int v, int nk) { return v >= -1 && v < nk; }
-// Step 2: the per-stream scalars, the nested offsets, the links, the neighbour table and the range of kf_by_key.
-MAP_HD bool ulm_validate_offsets(const UlmMap& M, const UlmStream& S, int b, int tid, int nt) {
+// Step 2: the per-stream scalars, the nested offsets, every key frame's links, the neighbour table and the range of kf_by_key.
+VIORB_HD bool ulm_validate_offsets(const UlmMap& M, const SnapStream& S, int b, int tid, int nt) {
     const int fc = M.frame_count[b], pn = M.prev_n_lkf[b];
-    bool ok = S.nk <= ULM_MAX_KF && fc >= 0 && fc <= M.cap && pn >= 0 && pn <= M.lcap && pn <= S.nk && ulm_slot_or_none(M.prev_ref_kf[b], S.nk);
-    for (int k = tid; k <= S.nk; k += nt) {
-        const int a = M.kp_start[S.k0 + k], c = M.child_start[S.k0 + k];
-        ok = ok && a >= 0 && a <= M.n_kp && (k == S.nk || a <= M.kp_start[S.k0 + k + 1]);
-        ok = ok && c >= 0 && c <= M.n_child && (k == S.nk || c <= M.child_start[S.k0 + k + 1]);
-        if (k < S.nk) {
-            ok = ok && ulm_slot_or_none(M.kf_parent[S.k0 + k], S.nk) && ulm_slot_or_none(M.kf_prev[S.k0 + k], S.nk) && ulm_slot_or_none(M.kf_next[S.k0 + k], S.nk);
-            ok = ok && M.kf_by_key[S.k0 + k] >= 0 && M.kf_by_key[S.k0 + k] < S.nk;
-            for (int i = 0; i < ULM_COVIS; i++) ok = ok && ulm_slot_or_none(M.covis10[(size_t)(S.k0 + k) * ULM_COVIS + i], S.nk);
-        }
-    }
-    for (int p = tid; p <= S.np; p += nt) {
-        const int a = M.obs_start[S.p0 + p];
-        ok = ok && a >= 0 && a <= M.n_obs && (p == S.np || a <= M.obs_start[S.p0 + p + 1]);
+    bool ok = S.nk <= SNAP_MAX_KF && fc >= 0 && fc <= M.cap && pn >= 0 && pn <= M.lcap && pn <= S.nk && snap_slot_or_none(M.prev_ref_kf[b], S.nk);
+    ok &= snap_offsets_run(M.kp_start, S.k0, S.nk, M.n_kp, tid, nt);
+    ok &= snap_offsets_run(M.child_start, S.k0, S.nk, M.n_child, tid, nt);
+    ok &= snap_offsets_run(M.obs_start, S.p0, S.np, M.n_obs, tid, nt);
+    for (int k = tid; k < S.nk; k += nt) {
+        const int g = S.k0 + k, parent = M.kf_parent[g], prev = M.kf_prev[g], next = M.kf_next[g], key = M.kf_by_key[g];
+        ok &= snap_slot_or_none(parent, S.nk) && snap_slot_or_none(prev, S.nk) && snap_slot_or_none(next, S.nk) && key >= 0 && key < S.nk;
+        for (int i = 0; i < ULM_COVIS; i++) ok &= snap_slot_or_none(M.covis10[(size_t)g * ULM_COVIS + i], S.nk);
     }
     return ok;
 }
 // Step 3: every point index of the keypoint tables and of the frame, every slot of the children, the observations and the previous list.
-MAP_HD bool ulm_validate_entries(const UlmMap& M, const UlmStream& S, int b, int tid, int nt) {
-    bool ok = true;
-    for (int i = M.kp_start[S.k0] + tid, e = M.kp_start[S.k0 + S.nk]; i < e; i += nt) ok = ok && M.kp_point[i] >= -1 && M.kp_point[i] < S.np;
-    for (int i = M.child_start[S.k0] + tid, e = M.child_start[S.k0 + S.nk]; i < e; i += nt) ok = ok && M.child_kf[i] >= 0 && M.child_kf[i] < S.nk;
-    for (int o = M.obs_start[S.p0] + tid, e = M.obs_start[S.p0 + S.np]; o < e; o += nt) ok = ok && (int)(M.obs[o] & 0xffffu) < S.nk;
-    for (int i = tid, e = M.frame_count[b]; i < e; i += nt) { const int p = M.frame_point[(size_t)b * M.cap + i]; ok = ok && p >= -1 && p < S.np; }
-    for (int i = tid, e = M.prev_n_lkf[b]; i < e; i += nt) { const int k = M.prev_lkf[(size_t)b * M.lcap + i]; ok = ok && k >= 0 && k < S.nk; }
+VIORB_HD bool ulm_validate_entries(const UlmMap& M, const SnapStream& S, int b, int tid, int nt) {
+    bool ok = snap_entries_within(M.kp_point, M.kp_start[S.k0], M.kp_start[S.k0 + S.nk], -1, S.np, tid, nt);
+    ok &= snap_entries_within(M.child_kf, M.child_start[S.k0], M.child_start[S.k0 + S.nk], 0, S.nk, tid, nt);
+    ok &= snap_obs_slots_below(M.obs, M.obs_start[S.p0], M.obs_start[S.p0 + S.np], S.nk, tid, nt);
+    ok &= snap_entries_within(M.frame_point + (size_t)b * M.cap, 0, M.frame_count[b], -1, S.np, tid, nt);
+    ok &= snap_entries_within(M.prev_lkf + (size_t)b * M.lcap, 0, M.prev_n_lkf[b], 0, S.nk, tid, nt);
     return ok;
 }
-// Step 4, twice: n in-range slots are distinct when every one finds its own ordinal in mark[] after all have written theirs (fill, a
-// barrier, check). For kf_by_key (n = nk) that makes it a permutation.
-MAP_HD void ulm_distinct_fill(const int32_t* slots, int n, int32_t* mark, int tid, int nt) { for (int j = tid; j < n; j += nt) mark[slots[j]] = j; }
-MAP_HD bool ulm_distinct_check(const int32_t* slots, int n, const int32_t* mark, int tid, int nt) {
-    bool ok = true;
-    for (int j = tid; j < n; j += nt) ok = ok && mark[slots[j]] == j;
-    return ok;
-}
-// The working state the later phases expect
-MAP_HD void ulm_prepare(const UlmStream& S, const UlmWork& W, int tid, int nt) { for (int p = tid; p < S.np; p += nt) W.first[S.p0 + p] = ULM_NO_POS; }
+// Step 4, twice (snap_distinct_fill / snap_distinct_check on mark[]): kf_by_key, which n = nk distinct slots make a permutation, and the
+// previous list. Then the working state the later phases expect:
+VIORB_HD void ulm_prepare(const SnapStream& S, const UlmWork& W, int tid, int nt) { for (int p = tid; p < S.np; p += nt) W.first[S.p0 + p] = ULM_NO_POS; }
 
 // ---- votes (:2000-2016): keypoint i of the frame; the number of votes it cast ------------------------------------------------------------
 // votes is the stream's own [nk].
-MAP_HD int ulm_vote_keypoint(const UlmMap& M, const UlmStream& S, int32_t* votes, const UlmOut& R, int b, int i) {
+VIORB_HD int ulm_vote_keypoint(const UlmMap& M, const SnapStream& S, int32_t* votes, const UlmOut& R, int b, int i) {
     const size_t g = (size_t)b * M.cap + i;
     int p = M.frame_point[g], n = 0;
     if (p >= 0) {
         if (M.pt_bad[S.p0 + p]) p = -1;                                                         // :2013
-        else for (int o = M.obs_start[S.p0 + p], e = M.obs_start[S.p0 + p + 1]; o < e; o++, n++) ulm_add(&votes[M.obs[o] & 0xffffu], 1);
+        else for (int o = M.obs_start[S.p0 + p], e = M.obs_start[S.p0 + p + 1]; o < e; o++, n++) snap_fetch_add(&votes[snap_obs_slot(M.obs[o])], 1);
     }
     if (R.frame_point_out) R.frame_point_out[g] = p;
     return n;
 }
 // The walk of keyframeCounter (:2028-2043) at key position j: the slot when it enters the list, else -1. key = (votes, first key position
 // wins) for the search of pKFmax, larger is better.
-MAP_HD int ulm_voted_slot(const UlmMap& M, const UlmStream& S, const int32_t* votes, int j, long long* key) {
-    const int k = M.kf_by_key[S.k0 + j], v = ulm_ld_votes(&votes[k]);
+VIORB_HD int ulm_voted_slot(const UlmMap& M, const SnapStream& S, const int32_t* votes, int j, long long* key) {
+    const int k = M.kf_by_key[S.k0 + j], v = snap_ld_agent(&votes[k]);
     if (v <= 0 || M.kf_bad[S.k0 + k]) return -1;
-    *key = (long long)v * 65536 + (ULM_MAX_KF - j);
+    *key = (long long)v * 65536 + (SNAP_MAX_KF - j);
     return k;
 }
-MAP_HD int ulm_key_slot(const UlmMap& M, const UlmStream& S, long long key) { return M.kf_by_key[S.k0 + (ULM_MAX_KF - (int)(key & 0xffff))]; }
+VIORB_HD int ulm_key_slot(const UlmMap& M, const SnapStream& S, long long key) { return M.kf_by_key[S.k0 + (SNAP_MAX_KF - (int)(key & 0xffff))]; }
 
 // ---- the neighbour loop (:2047-2118) ----------------------------------------------------------------------------------------------------
 // Run by `nl` lanes in step (the device: one wavefront; the host: lane 0 of 1). first_of(c) returns the c of the lowest lane whose c >= 0,
 // or -1, the same value to every lane. mark and list are the stream's own; list holds the n voted key frames.
-MAP_HD int ulm_push(int32_t* mark, int32_t* list, int size, int c, int lane) {
-    if (lane == 0) { ulm_st(&list[size], c); ulm_st(&mark[c], 1); }
-    ulm_fence();
+VIORB_HD int ulm_push(int32_t* mark, int32_t* list, int size, int c, int lane) {
+    if (lane == 0) { snap_st_wg(&list[size], c); snap_st_wg(&mark[c], 1); }
+    snap_fence_wg();
     return size + 1;
 }
 template <class First>
-MAP_HD int ulm_first_eligible(const UlmMap& M, const UlmStream& S, const int32_t* mark, const int32_t* cand, int n, int lane, int nl, First first_of) {
+VIORB_HD int ulm_first_eligible(const UlmMap& M, const SnapStream& S, const int32_t* mark, const int32_t* cand, int n, int lane, int nl, First first_of) {
     for (int i0 = 0; i0 < n; i0 += nl) {
         int c = -1;
-        if (i0 + lane < n) { c = cand[i0 + lane]; if (c >= 0 && (M.kf_bad[S.k0 + c] || ulm_ld(&mark[c]))) c = -1; }
+        if (i0 + lane < n) { c = cand[i0 + lane]; if (c >= 0 && (M.kf_bad[S.k0 + c] || snap_ld_wg(&mark[c]))) c = -1; }
         c = first_of(c);
         if (c >= 0) return c;
     }
     return -1;
 }
 template <class First>
-MAP_HD int ulm_neighbour_loop(const UlmMap& M, const UlmStream& S, int32_t* mark, int32_t* list, int n, int lane, int nl, First first_of) {
+VIORB_HD int ulm_neighbour_loop(const UlmMap& M, const SnapStream& S, int32_t* mark, int32_t* list, int n, int lane, int nl, First first_of) {
     int size = n;
     for (int j = 0; j < n; j++) {                                                              // itEndKF is taken before the loop
         if (size > ULM_LIMIT) break;                                                            // :2050
-        const int kf = ulm_ld(&list[j]), g = S.k0 + kf;
+        const int kf = snap_ld_wg(&list[j]), g = S.k0 + kf;
         int c = ulm_first_eligible(M, S, mark, M.covis10 + (size_t)g * ULM_COVIS, ULM_COVIS, lane, nl, first_of);      // :2055-2069
         if (c >= 0) size = ulm_push(mark, list, size, c, lane);
         c = ulm_first_eligible(M, S, mark, M.child_kf + M.child_start[g], M.child_start[g + 1] - M.child_start[g], lane, nl, first_of);   // :2071-2084
         if (c >= 0) size = ulm_push(mark, list, size, c, lane);
         const int link[3] = {M.kf_parent[g], M.kf_prev[g], M.kf_next[g]};                       // :2086-2117: no isBad() test
-        for (int q = 0; q < 3; q++) if (link[q] >= 0 && !ulm_ld(&mark[link[q]])) size = ulm_push(mark, list, size, link[q], lane);
+        for (int q = 0; q < 3; q++) if (link[q] >= 0 && !snap_ld_wg(&mark[link[q]])) size = ulm_push(mark, list, size, link[q], lane);
     }
     return size;
 }
@@ -209,41 +140,41 @@ MAP_HD int ulm_neighbour_loop(const UlmMap& M, const UlmStream& S, int32_t* mark
 // ---- local points (:1970-1993) -------------------------------------------------------------------------------------------------------------
 // The point at flat position pos of the stream's (list ordinal, keypoint) entries, or -1. estart[j] <= pos < estart[j + 1] picks j; a key
 // frame without keypoints owns no position.
-MAP_HD int ulm_entry_point(const UlmMap& M, const UlmStream& S, const int32_t* list, const int32_t* estart, int n_list, int pos) {
+VIORB_HD int ulm_entry_point(const UlmMap& M, const SnapStream& S, const int32_t* list, const int32_t* estart, int n_list, int pos) {
     int lo = 0, hi = n_list;
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (estart[mid] <= pos) lo = mid; else hi = mid; }
     return M.kp_point[M.kp_start[S.k0 + list[lo]] + (pos - estart[lo])];
 }
-MAP_HD void ulm_claim(const UlmMap& M, const UlmStream& S, const UlmWork& W, const int32_t* list, const int32_t* estart, int n_list, int pos) {
+VIORB_HD void ulm_claim(const UlmMap& M, const SnapStream& S, const UlmWork& W, const int32_t* list, const int32_t* estart, int n_list, int pos) {
     const int p = ulm_entry_point(M, S, list, estart, n_list, pos);
-    if (p >= 0 && !M.pt_bad[S.p0 + p]) ulm_min(&W.first[S.p0 + p], pos);
+    if (p >= 0 && !M.pt_bad[S.p0 + p]) snap_min(&W.first[S.p0 + p], pos);
 }
 // The point that position pos appends to mvpLocalMapPoints, or -1: not null, not bad, and not taken by a lower position.
-MAP_HD int ulm_kept_point(const UlmMap& M, const UlmStream& S, const UlmWork& W, const int32_t* list, const int32_t* estart, int n_list, int pos) {
+VIORB_HD int ulm_kept_point(const UlmMap& M, const SnapStream& S, const UlmWork& W, const int32_t* list, const int32_t* estart, int n_list, int pos) {
     const int p = ulm_entry_point(M, S, list, estart, n_list, pos);
     return (p >= 0 && !M.pt_bad[S.p0 + p] && W.first[S.p0 + p] == pos) ? p : -1;
 }
 
 // ---- outputs --------------------------------------------------------------------------------------------------------------------------------
-MAP_HD void ulm_write_refused(const UlmOut& R, int b) { if (R.status) R.status[b] = ULM_INVALID; }
+VIORB_HD void ulm_write_refused(const UlmOut& R, int b) { if (R.status) R.status[b] = ULM_INVALID; }
 // lkf[b], the share of `tid`: the first min(n, lcap) entries of the list, then -1
-MAP_HD void ulm_write_list(const UlmMap& M, const UlmOut& R, const int32_t* list, int n, int b, int tid, int nt) {
+VIORB_HD void ulm_write_list(const UlmMap& M, const UlmOut& R, const int32_t* list, int n, int b, int tid, int nt) {
     if (!R.lkf) return;
     for (int j = tid; j < M.lcap; j += nt) R.lkf[(size_t)b * M.lcap + j] = j < n ? list[j] : -1;
 }
 
 // The phases of the device form on one host thread, stream by stream. W holds arrays of the sizes UlmWork names.
 inline void ulm_run_host(const UlmMap& M, const UlmWork& W, const UlmOut& R) {
-    struct Self { MAP_HD int operator()(int c) const { return c; } };
+    struct Self { VIORB_HD int operator()(int c) const { return c; } };
     for (int b = 0; b < M.batch; b++) {
         bool ok = ulm_validate_ranges(M, b, 0, 1);
-        UlmStream S = {0, 0, 0, 0};
-        if (ok) { S = ulm_stream(M, b); ok = ulm_validate_offsets(M, S, b, 0, 1); }
+        SnapStream S = {0, 0, 0, 0};
+        if (ok) { S = snap_stream(M.kf_start, M.pt_start, b); ok = ulm_validate_offsets(M, S, b, 0, 1); }
         ok = ok && ulm_validate_entries(M, S, b, 0, 1);
-        if (ok) { ulm_distinct_fill(M.kf_by_key + S.k0, S.nk, W.mark + S.k0, 0, 1); ok = ulm_distinct_check(M.kf_by_key + S.k0, S.nk, W.mark + S.k0, 0, 1); }
+        if (ok) { snap_distinct_fill(M.kf_by_key + S.k0, S.nk, W.mark + S.k0, 0, 1); ok = snap_distinct_check(M.kf_by_key + S.k0, S.nk, W.mark + S.k0, 0, 1); }
         if (ok) {
             const int32_t* prev = M.prev_lkf + (size_t)b * M.lcap;
-            ulm_distinct_fill(prev, M.prev_n_lkf[b], W.mark + S.k0, 0, 1); ok = ulm_distinct_check(prev, M.prev_n_lkf[b], W.mark + S.k0, 0, 1);
+            snap_distinct_fill(prev, M.prev_n_lkf[b], W.mark + S.k0, 0, 1); ok = snap_distinct_check(prev, M.prev_n_lkf[b], W.mark + S.k0, 0, 1);
         }
         W.info[b * ULM_INFO + ULM_INFO_OK] = ok;
         if (!ok) { ulm_write_refused(R, b); continue; }

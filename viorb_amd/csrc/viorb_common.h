@@ -104,6 +104,10 @@ int host_keyframe(DeviceBufs& B, const viorb_keypoint* kps, const uint8_t* desc,
         }                                             \
     } while (0)
 
+// A caller's workspace: non-null, 256-byte aligned, at least `need` bytes, where `sizer` names the entry point that returns `need`
+#define VIORB_REQUIRE_WORKSPACE(ws, bytes, need, sizer) \
+    VIORB_REQUIRE((ws) && ((uintptr_t)(ws) & 255) == 0 && (bytes) >= (need), "workspace smaller than " sizer " or not 256-byte aligned")
+
 // returns the status of x unless it is VIORB_OK
 #define VIORB_TRY(x) do { int _rc = (x); if (_rc != VIORB_OK) return _rc; } while (0)
 

@@ -7,7 +7,7 @@ which scene_from_lists builds from Python lists; pack() lays a list of scenes ou
 as one dict per stream, cut to the stream's ranges. The host hook (no device) is key_frame_culling_host_core."""
 import ctypes as C
 import numpy as np
-from . import capi
+from . import capi, snapshot as S
 from .capi import lib, check, ptr, _torch_up as _up
 
 FIRST_KF, TIME_GAP, BEFORE_CURRENT, RECENT, KEPT, CULLED, DEFERRED = range(7)
@@ -49,48 +49,33 @@ def scene_from_lists(kfs, cur, cands, pts, vins_inited=False, th_depth=40.0):
     s["kf_prev"] = np.array([k.get("prev", -1) for k in kfs], np.int32)
     s["kf_next"] = np.array([k.get("next", -1) for k in kfs], np.int32)
     s["cand_kf"] = np.array([c[0] for c in cands], np.int32)
-    s["kp_start"] = np.concatenate([[0], np.cumsum([len(c[1]) for c in cands])]).astype(np.int32)
+    s["kp_start"], s["kp_point"] = S.csr([c[1] for c in cands], np.int32, lambda k: k[0])
     kps = [k for c in cands for k in c[1]]
-    s["kp_point"] = np.array([k[0] for k in kps], np.int32)
     s["kp_octave"] = np.array([k[1] for k in kps], np.uint8)
     s["kp_depth"] = np.array([k[2] for k in kps], np.float32)
     s["pt_nobs"] = np.array([p["nobs"] if p.get("nobs") is not None else sum(2 if o[2] else 1 for o in p["obs"]) for p in pts], np.int32)
     s["pt_bad"] = np.array([1 if p.get("bad") else 0 for p in pts], np.uint8)
-    s["obs_start"] = np.concatenate([[0], np.cumsum([len(p["obs"]) for p in pts])]).astype(np.int32)
-    s["obs"] = np.array([obs_word(*o) for p in pts for o in p["obs"]], np.uint32)
+    s["obs_start"], s["obs"] = S.csr([p["obs"] for p in pts], np.uint32, lambda o: obs_word(*o))
     return s
 
 
 def pack(scenes):
     """The flat arrays of viorb_cull_map for a list of scenes (every array at least one element long), with the totals."""
-    B = len(scenes)
-    cnt = lambda f: np.array([len(s[f]) for s in scenes], np.int64)
-    start = lambda n: np.concatenate([[0], np.cumsum(n)]).astype(np.int32)
-    cat = lambda f: np.concatenate([np.asarray(s[f], _DT[f]) for s in scenes]) if B else np.zeros(0, _DT[f])
-    P = dict(batch=B, n_kf=int(cnt("kf_flags").sum()), n_cand=int(cnt("cand_kf").sum()), n_kp=int(cnt("kp_point").sum()), n_pt=int(cnt("pt_nobs").sum()),
-             n_obs=int(cnt("obs").sum()))
-    P["kf_start"], P["cand_start"], P["pt_start"] = start(cnt("kf_flags")), start(cnt("cand_kf")), start(cnt("pt_nobs"))
+    cnt = lambda f: sum(len(s[f]) for s in scenes)
+    P = dict(batch=len(scenes), n_kf=cnt("kf_flags"), n_cand=cnt("cand_kf"), n_kp=cnt("kp_point"), n_pt=cnt("pt_nobs"), n_obs=cnt("obs"))
+    for f, src in (("kf_start", "kf_flags"), ("cand_start", "cand_kf"), ("pt_start", "pt_nobs")):
+        P[f] = S.starts([s[src] for s in scenes])
     for f in ("kf_flags", "kf_time", "kf_prev", "kf_next", "cand_kf", "kp_point", "kp_octave", "kp_depth", "pt_nobs", "pt_bad", "obs"):
-        P[f] = cat(f)
-    kp0, ob0 = start(cnt("kp_point")), start(cnt("obs"))
-    P["kp_start"] = np.concatenate([np.asarray(s["kp_start"][:-1], np.int32) + kp0[b] for b, s in enumerate(scenes)] + [[P["n_kp"]]]).astype(np.int32)
-    P["obs_start"] = np.concatenate([np.asarray(s["obs_start"][:-1], np.int32) + ob0[b] for b, s in enumerate(scenes)] + [[P["n_obs"]]]).astype(np.int32)
+        P[f] = S.cat(scenes, f, _DT[f])
+    P["kp_start"], P["obs_start"] = S.rebase(scenes, "kp_start", "kp_point"), S.rebase(scenes, "obs_start", "obs")
     P["cur_kf"] = np.array([s["cur"] for s in scenes], np.int32)
     P["vins_inited"] = np.array([1 if s["vins_inited"] else 0 for s in scenes], np.uint8)
     P["th_depth"] = np.array([s["th_depth"] for s in scenes], np.float32)
-    for f in capi.CULL_MAP_ARRAYS:
-        a = np.ascontiguousarray(P[f], _DT[f])
-        P[f] = a if len(a) else np.zeros(1, _DT[f])
-    return P
+    return S.finish(P, capi.CULL_MAP_ARRAYS, _DT)
 
 
 def _map_struct(P, arrays=None):
-    arrays = arrays or P
-    return capi.CullMap(*([P[f] for f in capi.CULL_MAP_INTS] + [ptr(arrays[f]) for f in capi.CULL_MAP_ARRAYS]))
-
-
-def _host_outputs(P):
-    return {f: np.full(max(P[_OUT_LEN[f]], 1), 77, _OUT_DT[f]) for f in capi.CULL_RESULT_FIELDS}
+    return S.struct(capi.CullMap, capi.CULL_MAP_INTS, capi.CULL_MAP_ARRAYS, P, arrays)
 
 
 def split(P, o):
@@ -112,22 +97,24 @@ def split(P, o):
     return res
 
 
-def _run_host(fn, scenes, monocular, packed):
-    P = packed or pack(scenes)
-    o = _host_outputs(P)
-    m, r = _map_struct(P), capi.CullResult(*[ptr(o[f]) for f in capi.CULL_RESULT_FIELDS])
+def _run_host(fn, P, monocular):
+    """The flat result arrays one call of a host entry leaves."""
+    o = S.outputs(capi.CULL_RESULT_FIELDS, lambda f: max(P[_OUT_LEN[f]], 1), _OUT_DT.get)
+    m, r = _map_struct(P), S.struct(capi.CullResult, (), capi.CULL_RESULT_FIELDS, o)
     check(fn(C.byref(m), int(bool(monocular)), C.byref(r)))
-    return split(P, o)
+    return o
 
 
 def key_frame_culling(scenes, monocular, packed=None):
     """viorb_key_frame_culling (host buffers): one result dict per scene."""
-    return _run_host(lib().viorb_key_frame_culling, scenes, monocular, packed)
+    P = packed or pack(scenes)
+    return split(P, _run_host(lib().viorb_key_frame_culling, P, monocular))
 
 
 def key_frame_culling_host_core(scenes, monocular, packed=None):
     """viorb_debug_key_frame_culling_host: culling_core.h on the host (no device), the phases of the device form on one thread."""
-    return _run_host(lib().viorb_debug_key_frame_culling_host, scenes, monocular, packed)
+    P = packed or pack(scenes)
+    return split(P, _run_host(lib().viorb_debug_key_frame_culling_host, P, monocular))
 
 
 class CullBatch:
@@ -136,20 +123,17 @@ class CullBatch:
     def __init__(self, scenes, monocular, device=0, packed=None):
         import torch
         self.torch, self.dev, self.monocular = torch, torch.device("cuda", device), bool(monocular)
-        self.P = packed or pack(scenes)
-        self.d = {f: _up(self.P[f].view(np.int32) if self.P[f].dtype == np.uint32 else self.P[f], device) for f in capi.CULL_MAP_ARRAYS}
-        self.map = _map_struct(self.P, self.d)
-        tdt = {np.int32: torch.int32, np.uint8: torch.uint8}
-        self.o = {f: torch.full((max(self.P[_OUT_LEN[f]], 1),), 77, dtype=tdt[_OUT_DT[f]], device=self.dev) for f in capi.CULL_RESULT_FIELDS}
-        self.res = capi.CullResult(*[ptr(self.o[f]) for f in capi.CULL_RESULT_FIELDS])
-        P = self.P
+        self.P = P = packed or pack(scenes)
+        self.d = S.upload(P, capi.CULL_MAP_ARRAYS, device)
+        self.map = _map_struct(P, self.d)
+        self.o = S.outputs(capi.CULL_RESULT_FIELDS, lambda f: max(P[_OUT_LEN[f]], 1), _OUT_DT.get, torch, self.dev)
+        self.res = S.struct(capi.CullResult, (), capi.CULL_RESULT_FIELDS, self.o)
         self._wb = lib().viorb_key_frame_culling_workspace_bytes(P["batch"], P["n_kf"], P["n_cand"], P["n_pt"], P["n_obs"])
-        self._ws = torch.zeros(self._wb + 256, dtype=torch.uint8, device=self.dev)
+        self._ws, self._wp = S.workspace(torch, self.dev, self._wb)
 
     def run(self, outputs=True):
-        ws = C.c_void_p(self._ws.data_ptr() + (-self._ws.data_ptr()) % 256)
-        check(lib().viorb_key_frame_culling_device(C.byref(self.map), int(self.monocular), C.byref(self.res) if outputs else None, ws, self._wb,
-                                                   C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)))
+        check(lib().viorb_key_frame_culling_device(C.byref(self.map), int(self.monocular), C.byref(self.res) if outputs else None, self._wp, self._wb,
+                                                   S.stream_ptr(self.torch, self.dev)))
 
     def inputs(self):
         """The snapshot as it lies on the device now."""

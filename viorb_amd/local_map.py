@@ -6,8 +6,8 @@ which scene_from_lists builds from Python lists; pack() lays a list of scenes ou
 the row lengths cap / lcap / pcap. Results come back as one dict per stream. The host hook (no device) is update_local_map_host_core."""
 import ctypes as C
 import numpy as np
-from . import capi
-from .capi import lib, check, ptr, _torch_up as _up
+from . import capi, snapshot as S
+from .capi import lib, check, ptr
 
 OK, NO_VOTES, OVERFLOW, INVALID = 0, 1, 2, -1
 STATUS_NAMES = {OK: "OK", NO_VOTES: "NO_VOTES", OVERFLOW: "OVERFLOW", INVALID: "ERR_INVALID_ARG"}
@@ -38,14 +38,11 @@ def scene_from_lists(kfs, pts, frame, by_key=None, prev_lkf=(), prev_ref=-1):
     for i, k in enumerate(kfs):
         c = list(k.get("covis", ()))[:COVIS]
         s["covis10"][i, :len(c)] = c
-    s["child_start"] = np.concatenate([[0], np.cumsum([len(k.get("children", ())) for k in kfs])]).astype(np.int32)
-    s["child_kf"] = np.array([c for k in kfs for c in k.get("children", ())], np.int32)
+    s["child_start"], s["child_kf"] = S.csr([k.get("children", ()) for k in kfs], np.int32)
     s["kf_by_key"] = np.array(list(by_key) if by_key is not None else list(range(nk)), np.int32)
-    s["kp_start"] = np.concatenate([[0], np.cumsum([len(k.get("pts", ())) for k in kfs])]).astype(np.int32)
-    s["kp_point"] = np.array([p for k in kfs for p in k.get("pts", ())], np.int32)
+    s["kp_start"], s["kp_point"] = S.csr([k.get("pts", ()) for k in kfs], np.int32)
     s["pt_bad"] = np.array([1 if p.get("bad") else 0 for p in pts], np.uint8)
-    s["obs_start"] = np.concatenate([[0], np.cumsum([len(p.get("obs", ())) for p in pts])]).astype(np.int32)
-    s["obs"] = np.array([o for p in pts for o in p.get("obs", ())], np.uint32)
+    s["obs_start"], s["obs"] = S.csr([p.get("obs", ()) for p in pts], np.uint32)
     return s
 
 
@@ -53,20 +50,16 @@ def pack(scenes, cap=None, lcap=None, pcap=None):
     """The flat arrays of viorb_local_map_snapshot for a list of scenes (every array at least one element long), with the totals and the
     row lengths. Defaults: cap = the longest frame, lcap = 96 or the most key frames of a stream, pcap = the most points of a stream."""
     B = len(scenes)
-    cnt = lambda f: np.array([len(s[f]) for s in scenes], np.int64)
-    start = lambda n: np.concatenate([[0], np.cumsum(n)]).astype(np.int32)
-    cat = lambda f: np.concatenate([np.asarray(s[f], _DT[f]).reshape(-1) for s in scenes]) if B else np.zeros(0, _DT[f])
-    P = dict(batch=B, n_kf=int(cnt("kf_bad").sum()), n_child=int(cnt("child_kf").sum()), n_kp=int(cnt("kp_point").sum()), n_pt=int(cnt("pt_bad").sum()),
-             n_obs=int(cnt("obs").sum()))
+    cnt = lambda f: sum(len(s[f]) for s in scenes)
+    P = dict(batch=B, n_kf=cnt("kf_bad"), n_child=cnt("child_kf"), n_kp=cnt("kp_point"), n_pt=cnt("pt_bad"), n_obs=cnt("obs"))
     P["cap"] = int(cap or max(1, max(len(s["frame_point"]) for s in scenes)))
     P["lcap"] = int(lcap or max(96, max(len(s["kf_bad"]) for s in scenes)))
     P["pcap"] = int(pcap or max(1, max(len(s["pt_bad"]) for s in scenes)))
-    P["kf_start"], P["pt_start"] = start(cnt("kf_bad")), start(cnt("pt_bad"))
+    P["kf_start"], P["pt_start"] = S.starts([s["kf_bad"] for s in scenes]), S.starts([s["pt_bad"] for s in scenes])
     for f in ("kf_bad", "kf_parent", "kf_prev", "kf_next", "covis10", "child_kf", "kf_by_key", "kp_point", "pt_bad", "obs"):
-        P[f] = cat(f)
+        P[f] = S.cat(scenes, f, _DT[f])
     for f, src in (("child_start", "child_kf"), ("kp_start", "kp_point"), ("obs_start", "obs")):
-        base = start(cnt(src))
-        P[f] = np.concatenate([np.asarray(s[f][:-1], np.int32) + base[b] for b, s in enumerate(scenes)] + [[base[-1]]]).astype(np.int32)
+        P[f] = S.rebase(scenes, f, src)
     P["frame_point"] = np.full((B, P["cap"]), -1, np.int32)
     P["prev_lkf"] = np.full((B, P["lcap"]), -1, np.int32)
     for b, s in enumerate(scenes):
@@ -75,34 +68,26 @@ def pack(scenes, cap=None, lcap=None, pcap=None):
     P["frame_count"] = np.array([len(s["frame_point"]) for s in scenes], np.int32)
     P["prev_n_lkf"] = np.array([len(s["prev_lkf"]) for s in scenes], np.int32)
     P["prev_ref_kf"] = np.array([s["prev_ref"] for s in scenes], np.int32)
-    for f in capi.LOCAL_MAP_ARRAYS:
-        a = np.ascontiguousarray(P[f], _DT[f]).reshape(-1)
-        P[f] = a if len(a) else np.zeros(1, _DT[f])
-    return P
+    return S.finish(P, capi.LOCAL_MAP_ARRAYS, _DT)
 
 
 def _map_struct(P, arrays=None):
-    arrays = arrays or P
-    return capi.LocalMapSnapshot(*([P[f] for f in capi.LOCAL_MAP_INTS] + [ptr(arrays[f]) for f in capi.LOCAL_MAP_ARRAYS]))
+    return S.struct(capi.LocalMapSnapshot, capi.LOCAL_MAP_INTS, capi.LOCAL_MAP_ARRAYS, P, arrays)
 
 
 def out_len(P, f):
     return P["batch"] * P[_ROW[f]] if f in _ROW else max(P["n_kf"], 1) if f == "kf_votes" else P["batch"]
 
 
-def _host_outputs(P):
-    return {f: np.full(out_len(P, f), 77, np.int32) for f in capi.LOCAL_MAP_RESULT_FIELDS}
-
-
 def split(P, o):
     """One dict per stream from flat result arrays: the fields of viorb_local_map_result cut to the stream; lkf / lpt cut to their counts
-    (what fits), their tails in lkf_tail / lpt_tail. A refused stream has only status and `untouched`: whether all its rows still hold the fill value 77."""
+    (what fits), their tails in lkf_tail / lpt_tail. A refused stream has only status and `untouched`: whether all its rows still hold the fill value."""
     res = []
     for b in range(P["batch"]):
         r = dict(status=int(o["status"][b]))
         rows = {f: np.asarray(o[f]).reshape(P["batch"], -1)[b] for f in _ROW}
         if r["status"] == INVALID:
-            r["untouched"] = all((rows[f] == 77).all() for f in _ROW) and all(int(o[f][b]) == 77 for f in ("n_lkf", "n_voted", "ref_kf", "n_lpt"))
+            r["untouched"] = all((rows[f] == S.FILL).all() for f in _ROW) and all(int(o[f][b]) == S.FILL for f in ("n_lkf", "n_voted", "ref_kf", "n_lpt"))
         else:
             for f in ("n_lkf", "n_voted", "ref_kf", "n_lpt"):
                 r[f] = int(o[f][b])
@@ -116,8 +101,8 @@ def split(P, o):
 
 def _run_host(fn, scenes, packed, **caps):
     P = packed or pack(scenes, **caps)
-    o = _host_outputs(P)
-    m, r = _map_struct(P), capi.LocalMapResult(*[ptr(o[f]) for f in capi.LOCAL_MAP_RESULT_FIELDS])
+    o = S.outputs(capi.LOCAL_MAP_RESULT_FIELDS, lambda f: out_len(P, f), lambda f: np.int32)
+    m, r = _map_struct(P), S.struct(capi.LocalMapResult, (), capi.LOCAL_MAP_RESULT_FIELDS, o)
     check(fn(C.byref(m), C.byref(r), P["cap"], P["lcap"], P["pcap"]))
     return split(P, o)
 
@@ -140,23 +125,19 @@ class LocalMapBatch:
         import torch
         self.torch, self.dev = torch, torch.device("cuda", device)
         self.P = P = packed or pack(scenes, **caps)
-        self.d = {f: _up(P[f].view(np.int32) if P[f].dtype == np.uint32 else P[f], device) for f in capi.LOCAL_MAP_ARRAYS}
+        self.d = S.upload(P, capi.LOCAL_MAP_ARRAYS, device)
         self.map = _map_struct(P, self.d)
-        self.o = {f: torch.full((out_len(P, f),), 77, dtype=torch.int32, device=self.dev) for f in capi.LOCAL_MAP_RESULT_FIELDS}
-        self.res = capi.LocalMapResult(*[ptr(self.o[f]) for f in capi.LOCAL_MAP_RESULT_FIELDS])
+        self.o = S.outputs(capi.LOCAL_MAP_RESULT_FIELDS, lambda f: out_len(P, f), lambda f: np.int32, torch, self.dev)
+        self.res = S.struct(capi.LocalMapResult, (), capi.LOCAL_MAP_RESULT_FIELDS, self.o)
         self._wb = lib().viorb_update_local_map_workspace_bytes(P["batch"], P["n_kf"], P["n_pt"])
-        self._ws = torch.zeros(self._wb + 256, dtype=torch.uint8, device=self.dev)
+        self._ws, self._wp = S.workspace(torch, self.dev, self._wb)
         self._gb = lib().viorb_local_points_gather_workspace_bytes(P["n_pt"])
-        self._gs = torch.zeros(self._gb + 256, dtype=torch.uint8, device=self.dev)
-
-    def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
+        self._gs, self._gp = S.workspace(torch, self.dev, self._gb)
 
     def run(self, outputs=True):
         P = self.P
-        ws = C.c_void_p(self._ws.data_ptr() + (-self._ws.data_ptr()) % 256)
-        check(lib().viorb_update_local_map_device(C.byref(self.map), C.byref(self.res) if outputs else None, P["cap"], P["lcap"], P["pcap"], ws, self._wb,
-                                                  self._stream()))
+        check(lib().viorb_update_local_map_device(C.byref(self.map), C.byref(self.res) if outputs else None, P["cap"], P["lcap"], P["pcap"], self._wp, self._wb,
+                                                  S.stream_ptr(self.torch, self.dev)))
 
     def results(self):
         self.torch.cuda.synchronize(self.dev)
@@ -172,9 +153,8 @@ class LocalMapBatch:
         else:
             pf = torch.full((B, pcap, 8), 7.0, dtype=torch.float32, device=self.dev); pd = torch.full((B, pcap, 32), 7, dtype=torch.uint8, device=self.dev)
             pc = torch.full((B,), 77, dtype=torch.int32, device=self.dev); pfl = torch.full((B, pcap), 77, dtype=torch.uint8, device=self.dev)
-        gs = C.c_void_p(self._gs.data_ptr() + (-self._gs.data_ptr()) % 256)
         check(lib().viorb_local_points_gather_device(C.byref(self.map), C.byref(self.res), P["cap"], pcap, ptr(map_pts_f), ptr(map_pts_desc), ptr(pt_nobs),
-                                                     ptr(pf), ptr(pd), ptr(pc), ptr(pfl), gs, self._gb, self._stream()))
+                                                     ptr(pf), ptr(pd), ptr(pc), ptr(pfl), self._gp, self._gb, S.stream_ptr(self.torch, self.dev)))
         return pf, pd, pc, pfl
 
 

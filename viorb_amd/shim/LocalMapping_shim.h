@@ -196,32 +196,27 @@ template <class KeyFrameT, class MapPointT> struct CullingReport {
 template <class KeyFrameT, class MapPointT>
 inline int key_frame_culling(KeyFrameT* pCur, bool bMonocular, bool bVINSInited, CullingReport<KeyFrameT, MapPointT>* report = 0) {
     const std::vector<KeyFrameT*> cands = pCur->GetVectorCovisibleKeyFrames();
-    std::map<KeyFrameT*, int> kf_slot; std::vector<KeyFrameT*> kfs;
-    std::map<MapPointT*, int> pt_slot; std::vector<MapPointT*> pts;
-    struct Add { static int kf(std::map<KeyFrameT*, int>& m, std::vector<KeyFrameT*>& v, KeyFrameT* k) {
-        typename std::map<KeyFrameT*, int>::iterator it = m.find(k);
-        if (it != m.end()) return it->second;
-        m[k] = (int)v.size(); v.push_back(k); return (int)v.size() - 1; } };
-    Add::kf(kf_slot, kfs, pCur);
+    SlotTable<KeyFrameT> kf_slot; const std::vector<KeyFrameT*>& kfs = kf_slot.items;
+    SlotTable<MapPointT> pt_slot; const std::vector<MapPointT*>& pts = pt_slot.items;
+    kf_slot.add(pCur);
     std::vector<int32_t> cand_kf, kp_start(1, 0), kp_point, pt_nobs, obs_start(1, 0); std::vector<uint8_t> kp_octave, pt_bad; std::vector<float> kp_depth; std::vector<uint32_t> obs;
     for (size_t j = 0; j < cands.size(); j++) {
         KeyFrameT* pKF = cands[j];
-        cand_kf.push_back(Add::kf(kf_slot, kfs, pKF));
-        if (pKF->GetPrevKeyFrame()) Add::kf(kf_slot, kfs, pKF->GetPrevKeyFrame());
-        if (pKF->GetNextKeyFrame()) Add::kf(kf_slot, kfs, pKF->GetNextKeyFrame());
+        cand_kf.push_back(kf_slot.add(pKF));
+        if (pKF->GetPrevKeyFrame()) kf_slot.add(pKF->GetPrevKeyFrame());
+        if (pKF->GetNextKeyFrame()) kf_slot.add(pKF->GetNextKeyFrame());
         const std::vector<MapPointT*> vpMapPoints = pKF->GetMapPointMatches();
         for (size_t i = 0; i < vpMapPoints.size(); i++) {
             MapPointT* pMP = vpMapPoints[i];
             int p = -1;
             if (pMP) {
-                typename std::map<MapPointT*, int>::iterator it = pt_slot.find(pMP);
-                if (it != pt_slot.end()) p = it->second;
-                else {
-                    p = (int)pts.size(); pt_slot[pMP] = p; pts.push_back(pMP);
+                const size_t before = pts.size();
+                p = pt_slot.add(pMP);
+                if (pts.size() != before) {
                     pt_nobs.push_back(pMP->Observations()); pt_bad.push_back(pMP->isBad() ? 1 : 0);
                     const std::map<KeyFrameT*, size_t> observations = pMP->GetObservations();
                     for (typename std::map<KeyFrameT*, size_t>::const_iterator mit = observations.begin(); mit != observations.end(); ++mit) {
-                        const int slot = Add::kf(kf_slot, kfs, mit->first);
+                        const int slot = kf_slot.add(mit->first);
                         if (slot >= 65535) throw std::runtime_error("KeyFrameCulling: more than 65535 key frames in the snapshot");
                         obs.push_back((uint32_t)slot | ((uint32_t)(mit->first->mvKeysUn[mit->second].octave & 0xff) << 16) | (mit->first->mvuRight[mit->second] >= 0 ? 1u << 24 : 0u));
                     }
@@ -237,10 +232,8 @@ inline int key_frame_culling(KeyFrameT* pCur, bool bMonocular, bool bVINSInited,
     for (size_t k = 0; k < nk; k++) {
         kf_flags[k] = (uint8_t)((kfs[k]->mnId == 0 ? VIORB_CULL_KF_FIRST : 0) | (kfs[k]->GetNotErase() ? VIORB_CULL_KF_NOT_ERASE : 0));
         kf_time[k] = kfs[k]->mTimeStamp;
-        typename std::map<KeyFrameT*, int>::iterator it = kf_slot.find(kfs[k]->GetPrevKeyFrame());
-        if (kfs[k]->GetPrevKeyFrame() && it != kf_slot.end()) kf_prev[k] = it->second;
-        it = kf_slot.find(kfs[k]->GetNextKeyFrame());
-        if (kfs[k]->GetNextKeyFrame() && it != kf_slot.end()) kf_next[k] = it->second;
+        if (kfs[k]->GetPrevKeyFrame()) kf_prev[k] = kf_slot.find(kfs[k]->GetPrevKeyFrame());
+        if (kfs[k]->GetNextKeyFrame()) kf_next[k] = kf_slot.find(kfs[k]->GetNextKeyFrame());
     }
     // every array at least one element long: the library refuses a null pointer whatever the count
     cand_kf.resize(std::max<size_t>(nc, 1)); kp_point.resize(std::max<size_t>(kp_point.size(), 1), -1); kp_octave.resize(kp_point.size()); kp_depth.resize(kp_point.size());

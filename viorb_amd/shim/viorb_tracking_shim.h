@@ -206,6 +206,21 @@ inline int relocalization_refine(FrameT& F, KeyFrameT* pKF, const cv::Mat& Tcw, 
     return n_good;
 }
 
+// ---- map snapshots (include/viorb_culling.h, include/viorb_local_map.h) ------------------------------------------------------------------
+// The slots of a snapshot: pointers numbered in the order they are first seen.
+template <class T> struct SlotTable {
+    std::map<T*, int> slot_of; std::vector<T*> items;               // items[slot_of[p]] == p
+    int add(T* p) {                                                  // the slot of p, a new one when it has none
+        typename std::map<T*, int>::iterator it = slot_of.find(p);
+        if (it != slot_of.end()) return it->second;
+        slot_of[p] = (int)items.size(); items.push_back(p); return (int)items.size() - 1;
+    }
+    int find(T* p) const {                                           // the slot of p, or -1
+        typename std::map<T*, int>::const_iterator it = slot_of.find(p);
+        return it != slot_of.end() ? it->second : -1;
+    }
+};
+
 // ---- Tracking::UpdateLocalMap (include/viorb_local_map.h) ------------------------------------------------------------------------------
 // The two calls of Tracking::UpdateLocalMap (src/Tracking.cc:1966-1967) become
 //   viorb_shim::update_local_map<KeyFrame, MapPoint>(mCurrentFrame, mvpLocalKeyFrames, mpReferenceKF, mvpLocalMapPoints);
@@ -218,20 +233,8 @@ inline int relocalization_refine(FrameT& F, KeyFrameT* pKF, const cv::Mat& Tcw, 
 // frame won the vote), mvpLocalMapPoints. Returns VIORB_OK or VIORB_ULM_NO_VOTES; a failure throws.
 template <class KeyFrameT, class MapPointT, class FrameT>
 inline int update_local_map(FrameT& F, std::vector<KeyFrameT*>& mvpLocalKeyFrames, KeyFrameT*& mpReferenceKF, std::vector<MapPointT*>& mvpLocalMapPoints) {
-    std::map<KeyFrameT*, int> kf_slot; std::vector<KeyFrameT*> kfs;
-    std::map<MapPointT*, int> pt_slot; std::vector<MapPointT*> pts;
-    struct Add {
-        static int kf(std::map<KeyFrameT*, int>& m, std::vector<KeyFrameT*>& v, KeyFrameT* k) {
-            typename std::map<KeyFrameT*, int>::iterator it = m.find(k);
-            if (it != m.end()) return it->second;
-            m[k] = (int)v.size(); v.push_back(k); return (int)v.size() - 1;
-        }
-        static int pt(std::map<MapPointT*, int>& m, std::vector<MapPointT*>& v, MapPointT* p) {
-            typename std::map<MapPointT*, int>::iterator it = m.find(p);
-            if (it != m.end()) return it->second;
-            m[p] = (int)v.size(); v.push_back(p); return (int)v.size() - 1;
-        }
-    };
+    SlotTable<KeyFrameT> kf_slot; const std::vector<KeyFrameT*>& kfs = kf_slot.items;
+    SlotTable<MapPointT> pt_slot; const std::vector<MapPointT*>& pts = pt_slot.items;
     const int N = F.N;
     std::vector<int32_t> frame_point(std::max(N, 1), -1);
     std::vector<std::vector<int32_t> > pt_obs;                       // by point index; empty for a point the frame does not hold
@@ -239,12 +242,12 @@ inline int update_local_map(FrameT& F, std::vector<KeyFrameT*>& mvpLocalKeyFrame
         MapPointT* pMP = F.mvpMapPoints[i];
         if (!pMP) continue;
         const size_t before = pts.size();
-        const int p = Add::pt(pt_slot, pts, pMP);
+        const int p = pt_slot.add(pMP);
         frame_point[i] = p;
         if (pts.size() == before) continue;
         pt_obs.resize(pts.size());
         const std::map<KeyFrameT*, size_t> observations = pMP->GetObservations();
-        for (typename std::map<KeyFrameT*, size_t>::const_iterator it = observations.begin(); it != observations.end(); ++it) pt_obs[p].push_back(Add::kf(kf_slot, kfs, it->first));
+        for (typename std::map<KeyFrameT*, size_t>::const_iterator it = observations.begin(); it != observations.end(); ++it) pt_obs[p].push_back(kf_slot.add(it->first));
     }
     const size_t n_visited = kfs.size();                             // slots below: the key frames a vote can reach
     std::vector<int32_t> covis10(n_visited * 10, -1), child_start(1, 0), child_kf;
@@ -252,17 +255,17 @@ inline int update_local_map(FrameT& F, std::vector<KeyFrameT*>& mvpLocalKeyFrame
     for (size_t k = 0; k < n_visited; k++) {
         KeyFrameT* pKF = kfs[k];
         const std::vector<KeyFrameT*> vNeighs = pKF->GetBestCovisibilityKeyFrames(10);
-        for (size_t j = 0; j < vNeighs.size() && j < 10; j++) covis10[k * 10 + j] = Add::kf(kf_slot, kfs, vNeighs[j]);
+        for (size_t j = 0; j < vNeighs.size() && j < 10; j++) covis10[k * 10 + j] = kf_slot.add(vNeighs[j]);
         const std::set<KeyFrameT*> spChilds = pKF->GetChilds();
-        for (typename std::set<KeyFrameT*>::const_iterator sit = spChilds.begin(); sit != spChilds.end(); ++sit) child_kf.push_back(Add::kf(kf_slot, kfs, *sit));
+        for (typename std::set<KeyFrameT*>::const_iterator sit = spChilds.begin(); sit != spChilds.end(); ++sit) child_kf.push_back(kf_slot.add(*sit));
         child_start.push_back((int32_t)child_kf.size());
-        if (pKF->GetParent()) parent[k] = Add::kf(kf_slot, kfs, pKF->GetParent());
-        if (pKF->GetPrevKeyFrame()) prev[k] = Add::kf(kf_slot, kfs, pKF->GetPrevKeyFrame());
-        if (pKF->GetNextKeyFrame()) next[k] = Add::kf(kf_slot, kfs, pKF->GetNextKeyFrame());
+        if (pKF->GetParent()) parent[k] = kf_slot.add(pKF->GetParent());
+        if (pKF->GetPrevKeyFrame()) prev[k] = kf_slot.add(pKF->GetPrevKeyFrame());
+        if (pKF->GetNextKeyFrame()) next[k] = kf_slot.add(pKF->GetNextKeyFrame());
     }
     std::vector<int32_t> prev_lkf;
-    for (size_t j = 0; j < mvpLocalKeyFrames.size(); j++) prev_lkf.push_back(Add::kf(kf_slot, kfs, mvpLocalKeyFrames[j]));
-    const int32_t prev_ref = mpReferenceKF ? Add::kf(kf_slot, kfs, mpReferenceKF) : -1;
+    for (size_t j = 0; j < mvpLocalKeyFrames.size(); j++) prev_lkf.push_back(kf_slot.add(mvpLocalKeyFrames[j]));
+    const int32_t prev_ref = mpReferenceKF ? kf_slot.add(mpReferenceKF) : -1;
     const size_t nk = kfs.size();
     if (nk > 65535) throw std::runtime_error("UpdateLocalMap: more than 65535 key frames in the snapshot");
     covis10.resize(std::max<size_t>(nk, 1) * 10, -1); child_start.resize(nk + 1, (int32_t)child_kf.size());
@@ -272,7 +275,7 @@ inline int update_local_map(FrameT& F, std::vector<KeyFrameT*>& mvpLocalKeyFrame
     for (size_t k = 0; k < nk; k++) {
         kf_bad[k] = kfs[k]->isBad() ? 1 : 0;
         const std::vector<MapPointT*> vpMPs = kfs[k]->GetMapPointMatches();
-        for (size_t i = 0; i < vpMPs.size(); i++) kp_point.push_back(vpMPs[i] ? Add::pt(pt_slot, pts, vpMPs[i]) : -1);
+        for (size_t i = 0; i < vpMPs.size(); i++) kp_point.push_back(vpMPs[i] ? pt_slot.add(vpMPs[i]) : -1);
         kp_start.push_back((int32_t)kp_point.size());
     }
     const size_t np = pts.size();
