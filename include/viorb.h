@@ -725,8 +725,8 @@ int viorb_map_points_update(const int32_t* obs_start, const int32_t* obs_kf, con
  * neighbour. has_point1, n_new[b] and status[b] are in / out (zero n_new and status before the first call of a key frame), so
  * neighbours 0..5 in one call equal 0..2 then 3..5 — the caller's place for the CheckNewKeyFrames() exit. A stream whose points would
  * exceed pcap gets status VIORB_ERR_CAPACITY: its first pcap points are written, n_new[b] = pcap, and its later neighbours are
- * skipped. workspace: viorb_create_new_map_points_workspace_bytes(cap, batch) bytes of device memory, 256-byte aligned. Only
- * enqueues on `stream`: no allocation, no host synchronisation. */
+ * skipped. workspace: viorb_create_new_map_points_workspace_bytes(cap, batch) bytes of device memory, 256-byte aligned; its
+ * contents on entry are ignored. Only enqueues on `stream`: no allocation, no host synchronisation. */
 size_t viorb_create_new_map_points_workspace_bytes(int cap, int batch);
 int viorb_create_new_map_points_device(const viorb_mapping_camera* cam, int monocular, const viorb_keypoint* k1, const uint8_t* d1,
                                        uint8_t* has_point1, const float* uright1, const float* depth1, const float* keys_dist_xy1,
@@ -906,8 +906,9 @@ int viorb_global_ba_navstate(const viorb_gba_config* cfg, const double* kfs, int
                              int ne, const double gw[3], const double cam[16], const volatile int* stop, double* kfs_out,
                              double* points_out, uint8_t* point_included, double info[6]);
 /* The same with the arrays in device memory (kfs_out / points_out are the working states and must not alias the inputs); cfg, gw, cam,
- * stop and info are host pointers. workspace: viorb_global_ba_navstate_workspace_bytes(nk, np, ne) bytes of device memory. The call
- * returns when the solve is done (the Levenberg control reads three doubles per trial from `stream`). */
+ * stop and info are host pointers. workspace: viorb_global_ba_navstate_workspace_bytes(nk, np, ne) bytes of device memory; its
+ * contents on entry are ignored. The call returns when the solve is done (the Levenberg control reads three doubles per trial from
+ * `stream`). */
 int viorb_global_ba_navstate_device(const viorb_gba_config* cfg, const double* kfs, int nk, const int32_t* prev, const uint8_t* fixed,
                                     const double* preint, const double* points, int np, const int32_t* edge_idx,
                                     const double* edge_obs, int ne, const double gw[3], const double cam[16], const volatile int* stop,
@@ -1009,7 +1010,8 @@ int viorb_kfdb_size(const viorb_kfdb* db, int* n_slots, int* n_alive);
  * key frames scored, entries of lScoreAndMatch; common_out / score_out [q*n_slots + s] (may be NULL) = mnLoopWords / mLoopScore
  * (mnRelocWords / mRelocScore): the common-word count (0 for a dead or excluded slot) and the float score, -1 where not scored.
  * A neighbour adds to a group's accScore only if it was scored in this query, in both modes (deviation 10).
- * workspace: viorb_kfdb_query_workspace_bytes(db, n_q) bytes of device memory, 256-byte aligned, sized after the last add. */
+ * workspace: viorb_kfdb_query_workspace_bytes(db, n_q) bytes of device memory, 256-byte aligned, sized after the last add; its
+ * contents on entry are ignored. */
 size_t viorb_kfdb_query_workspace_bytes(const viorb_kfdb* db, int n_q);
 int viorb_kfdb_query_device(viorb_kfdb* db, int mode, int n_q, const int32_t* q_word, const double* q_val, const int32_t* q_count,
                             int q_cap, const float* min_score, const int32_t* excl_start, const int32_t* excl_slot,

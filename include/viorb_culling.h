@@ -76,8 +76,8 @@ typedef struct viorb_cull_result {
     int32_t* pt_nobs_out; uint8_t* pt_bad_out; uint8_t* obs_alive;
 } viorb_cull_result;
 
-/* Device scratch of viorb_key_frame_culling_device (256-byte aligned device memory) for a snapshot of these totals. 0 for sizes outside
- * the limits. */
+/* Device scratch of viorb_key_frame_culling_device (256-byte aligned device memory; its contents on entry are ignored) for a snapshot of
+ * these totals. 0 for sizes outside the limits. */
 size_t viorb_key_frame_culling_workspace_bytes(int batch, int n_kf, int n_cand, int n_pt, int n_obs);
 
 /* LocalMapping::KeyFrameCulling (:1694-1821) for every stream of the snapshot; monocular = mbMonocular. It enqueues two kernels on

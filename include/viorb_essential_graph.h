@@ -35,7 +35,8 @@ int viorb_optimize_essential_graph(const viorb_eg_config* cfg, const double* Scw
                                    const int32_t* edge_idx, const uint8_t* edge_corrected, int ne, const float* points,
                                    const int32_t* point_ref, int np, double* Scw_out, double* Tcw_out, float* points_out, double info[6]);
 /* The same with the arrays in device memory (Scw_out is the working state and must not alias Scw); cfg and info are host pointers.
- * workspace: viorb_essential_graph_workspace_bytes(nk, ne, np) bytes of device memory. The argument checks run in a kernel. */
+ * workspace: viorb_essential_graph_workspace_bytes(nk, ne, np) bytes of device memory; its contents on entry are ignored. The argument
+ * checks run in a kernel. */
 int viorb_optimize_essential_graph_device(const viorb_eg_config* cfg, const double* Scw, const double* Smeas, const uint8_t* fixed, int nk,
                                           const int32_t* edge_idx, const uint8_t* edge_corrected, int ne, const float* points,
                                           const int32_t* point_ref, int np, double* Scw_out, double* Tcw_out, float* points_out,

@@ -30,7 +30,8 @@ int viorb_global_ba_se3(const viorb_gba_config* cfg, const double* kfs, int nk, 
                         const int32_t* edge_idx, const double* edge_obs, int ne, const double intr5[5], const volatile int* stop,
                         double* kfs_out, double* points_out, uint8_t* point_included, double info[6]);
 /* The same with the arrays in device memory (kfs_out / points_out are the working states and must not alias the inputs); cfg, intr5,
- * stop and info are host pointers. workspace: viorb_global_ba_se3_workspace_bytes(nk, np, ne) bytes of device memory. */
+ * stop and info are host pointers. workspace: viorb_global_ba_se3_workspace_bytes(nk, np, ne) bytes of device memory; its
+ * contents on entry are ignored. */
 int viorb_global_ba_se3_device(const viorb_gba_config* cfg, const double* kfs, int nk, const uint8_t* fixed, const double* points, int np,
                                const int32_t* edge_idx, const double* edge_obs, int ne, const double intr5[5], const volatile int* stop,
                                double* kfs_out, double* points_out, uint8_t* point_included, double info[6], void* workspace,

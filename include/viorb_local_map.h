@@ -64,8 +64,8 @@ typedef struct viorb_local_map_result {
     int32_t* frame_point_out; int32_t* kf_votes;
 } viorb_local_map_result;
 
-/* Device scratch of viorb_update_local_map_device (256-byte aligned device memory) for a snapshot of these totals. 0 for sizes outside
- * the limits. */
+/* Device scratch of viorb_update_local_map_device (256-byte aligned device memory; its contents on entry are ignored) for a snapshot of
+ * these totals. 0 for sizes outside the limits. */
 size_t viorb_update_local_map_workspace_bytes(int batch, int n_kf, int n_pt);
 
 /* Tracking::UpdateLocalMap (:1966-1967) for every stream of the snapshot. cap / lcap / pcap: the row lengths of frame_point, of lkf and
@@ -87,7 +87,8 @@ int viorb_update_local_map_shape(int32_t* out4);
  * VIORB_ULM_NO_VOTES, else 0. For j < pts_count[b]: pts_f / pts_desc = the rows of point lpt[b][j]; pts_flags = bit 0 (every local point
  * was !isBad() when listed), bit 1 where a keypoint of frame_point_out holds the point (mnLastFrameSeen == mCurrentFrame.mnId after the
  * first loop of Tracking::SearchLocalPoints, :1907-1923), bit 2 where pt_nobs > 0. Everything from the count on is zero. IncreaseVisible
- * and the other MapPoint counters stay with the caller. Workspace: viorb_local_points_gather_workspace_bytes(n_pt), 256-byte aligned. */
+ * and the other MapPoint counters stay with the caller. Workspace: viorb_local_points_gather_workspace_bytes(n_pt), 256-byte aligned;
+ * its contents on entry are ignored. */
 size_t viorb_local_points_gather_workspace_bytes(int n_pt);
 int viorb_local_points_gather_device(const viorb_local_map_snapshot* map, const viorb_local_map_result* result, int cap, int pcap,
                                      const float* map_pts_f, const uint8_t* map_pts_desc, const int32_t* pt_nobs, float* pts_f, uint8_t* pts_desc,

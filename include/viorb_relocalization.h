@@ -32,7 +32,7 @@
 #define VIORB_S3M_ROTATION              9   /* matched in the loop (:1556-1559), then removed by the rotation histogram (:1586-1596) */
 
 /* Device scratch of viorb_search_by_projection_reloc_device for frames of fcap features, kcap key-frame features and `batch` hypotheses
- * (256-byte aligned device memory). 0 for sizes outside the limits. */
+ * (256-byte aligned device memory; its contents on entry are ignored). 0 for sizes outside the limits. */
 size_t viorb_relocalization_workspace_bytes(int fcap, int kcap, int batch);
 
 /* ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) for `batch` hypotheses. pose12 [batch][12] =
@@ -104,7 +104,8 @@ typedef struct viorb_reloc_outputs {
     int32_t* accepted; int32_t* n_good; int32_t* stage; int32_t* counts; float* out_pose12; double* chi2; int32_t* frame_match; uint8_t* outlier;
 } viorb_reloc_outputs;
 
-/* Device scratch of viorb_relocalization_refine_device; hcap is the capacity of the front-end handle (viorb_frontend_capacity). */
+/* Device scratch of viorb_relocalization_refine_device (its contents on entry are ignored); hcap is the capacity of the front-end handle
+ * (viorb_frontend_capacity). */
 size_t viorb_relocalization_refine_workspace_bytes(int fcap, int kcap, int hcap, int batch);
 
 /* Steps (a) to (g) of :2209-2273 for `batch` hypotheses in lock step on one stream, with no host round trip: the per-hypothesis stage and

@@ -38,7 +38,8 @@ typedef struct viorb_search_init_outputs {
     int32_t* matches21; int32_t* matched_distance; int32_t* rot_hist; int32_t* reason; float* xy1; float* xy2; int32_t* sweeps;
 } viorb_search_init_outputs;
 
-/* Device scratch of viorb_search_for_initialization_device (256-byte aligned device memory). 0 for sizes outside the limits. */
+/* Device scratch of viorb_search_for_initialization_device (256-byte aligned device memory; its contents on entry are ignored). 0 for
+ * sizes outside the limits. */
 size_t viorb_search_init_workspace_bytes(int cap, int batch);
 
 /* ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize) (src/ORBmatcher.cc:405-520) for `batch` streams,

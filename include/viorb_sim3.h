@@ -66,7 +66,8 @@ int viorb_sim3_draw_sets(int n, int iterations, uint64_t seed, int32_t* sets);
  * or a probability outside (0, 1). For n < min_inliers the formula's log has a negative argument; the reference's conversion of a NaN
  * to int is undefined and iterate never reads the result (:146): the value returned is max_iterations. */
 int viorb_sim3_ransac_iterations(int n, double probability, int min_inliers, int max_iterations);
-/* Device scratch of every _device entry below for these sizes (256-byte aligned device memory); 0 for sizes outside the limits. */
+/* Device scratch of every _device entry below for these sizes (256-byte aligned device memory; its contents on entry are ignored); 0 for
+ * sizes outside the limits. */
 size_t viorb_sim3_workspace_bytes(int cap, int iterations, int batch);
 
 /* The stages; viorb_sim3_ransac_device runs exactly these kernels in this order.

@@ -49,8 +49,9 @@ typedef struct viorb_s3m_side {
     viorb_s3m_keyframes kf; const float* pose12; const uint8_t* has_point; const float* pts_f; const uint8_t* pts_desc; const uint8_t* already;
 } viorb_s3m_side;
 
-/* Device scratch of every _device entry below (256-byte aligned device memory) for key frames of `cap` features, `pcap` points per list
- * and `batch` items; for SearchBySim3 cap is the larger of the two sides' and pcap is ignored. 0 for sizes outside the limits. */
+/* Device scratch of every _device entry below (256-byte aligned device memory; its contents on entry are ignored) for key frames of `cap`
+ * features, `pcap` points per list and `batch` items; for SearchBySim3 cap is the larger of the two sides' and pcap is ignored. 0 for
+ * sizes outside the limits. */
 size_t viorb_sim3_match_workspace_bytes(int cap, int pcap, int batch);
 
 /* KeyFrame::mGrid (a copy of Frame::mGrid; Frame::AssignFeaturesToGrid, src/Frame.cc:410-425) without a front-end handle: the CSR that

@@ -57,7 +57,7 @@ typedef struct viorb_two_view_outputs {
  * Host only. VIORB_ERR_INVALID_ARG for n_matches < 8 or iterations < 1. */
 int viorb_two_view_draw_sets(int n_matches, int iterations, uint64_t seed, int32_t* sets);
 
-/* Device scratch of every _device entry below for these sizes (256-byte aligned device memory). */
+/* Device scratch of every _device entry below for these sizes (256-byte aligned device memory; its contents on entry are ignored). */
 size_t viorb_two_view_workspace_bytes(int cap, int iterations, int batch);
 
 /* Initializer::Initialize (:44-121) for `batch` streams: Normalize over all key points of each frame (:749-795), cfg->iterations

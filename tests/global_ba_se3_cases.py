@@ -7,8 +7,11 @@ import numpy as np
 
 ITERATIONS = 10
 # (N, robust, stereo, revisit) -> seed, where the first choice did not keep the margins of tests/test_global_ba_se3_ref.py (seed 505: the
-# checker's own two summation orders end 3.5e-7 apart in lambda; seed 637: 9e-6 apart in one point)
-_SEED = {(3, 0, 0.5, 0.2): 1506, (130, 1, 0.5, 0.2): 1637}
+# checker's own two summation orders end 3.5e-7 apart in lambda; seed 637: 9e-6 apart in one point; with its points scaled by
+# 1 + 1e-15 N(0, 1) seed 517 moves one point by 6.0e-5, seed 597 by 3.3e-6 and seed 1637 by 4.3e-5, against the 2.5e-7 of the perturbation
+# margin: each sits on a discrete event of its own solve. At N = 130 the seeds 1637 + 1000 k were tried in turn: k = 1 .. 5 move a point
+# by 7.6e-6, 3.9e-6, 4.1e-6, 1.8e-6, 2.0e-6; k = 6 by 1.1e-7)
+_SEED = {(3, 0, 0.5, 0.2): 1506, (3, 1, 0.5, 0.2): 2517, (43, 1, 0.5, 0.2): 1597, (130, 1, 0.5, 0.2): 7637}
 
 
 def _seed(i, N, r, s, f):

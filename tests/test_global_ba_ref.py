@@ -1,7 +1,8 @@
 """CPU checks of the global bundle adjustment (no GPU): the numpy checker tests/global_ba_ref.py is pinned against the oracle's window
 solve (whose first optimize(5) is the same computation when key frame 0 is fixed and every other one is local), the oracle's edge
 functions, central differences and a solve of the un-eliminated normal equations; the library exports the new entry points and refuses
-malformed inputs before any GPU call; and every problem the GPU tests solve keeps its Levenberg decisions away from their thresholds."""
+malformed inputs before any GPU call; and every problem the GPU tests solve keeps its Levenberg decisions away from their thresholds and (up
+to N = 60) its result within a quarter of the GPU tests' floors when its points move in their last bit."""
 import ctypes as C
 import functools
 import os
@@ -166,6 +167,34 @@ def _margins(r):
     return rho, term
 
 
+PERTURBATION, PERTURBED_RUNS = 1e-15, 12
+
+
+def _check_perturbation_margin(name, p, r, robust, iterations, rng_seed):
+    """The checker on the problem with its points scaled by 1 + 1e-15 N(0, 1), 12 times (generator seed rng_seed, written by the caller),
+    against its result r on the problem as it stands: the same accept / reject sequence every time, and no key-frame state further than
+    a quarter of the 1e-7, no point further than a quarter of the 1e-6 that tests/test_gpu_global_ba.py holds the device to. A case that
+    fails this sits on a discrete event of its own solve, and the device's unordered FP64 sums land on either side of it."""
+    seq = [t[4] for t in r["trials"]]
+    rng = np.random.default_rng(rng_seed)
+    same, dk, dp = True, 0.0, 0.0
+    for _ in range(PERTURBED_RUNS):
+        q = dict(p, points=p["points"] * (1.0 + PERTURBATION * rng.standard_normal(p["points"].shape)))
+        b = G.global_ba(*GC.args(q), iterations=iterations, robust=bool(robust))
+        same = same and [t[4] for t in b["trials"]] == seq
+        dk, dp = max(dk, np.abs(r["kfs"] - b["kfs"]).max()), max(dp, np.abs(r["points"] - b["points"]).max())
+    print(name, "%d perturbations of %.0e (generator seed %d): same decisions %s, moves: states %.3g points %.3g" % (PERTURBED_RUNS, PERTURBATION, rng_seed, same, dk, dp))
+    assert same, name
+    assert 4 * dk <= 1e-7 and 4 * dp <= 1e-6, name
+
+
+@pytest.mark.parametrize("seed,N,robust,revisit", [c for c in GC.CASES if c[1] <= 60])
+def test_gpu_cases_do_not_move_with_the_last_bit_of_their_points(seed, N, robust, revisit):
+    p = _problem(seed, N, revisit)
+    r = G.global_ba(*GC.args(p), iterations=GC.ITERATIONS, robust=bool(robust))
+    _check_perturbation_margin("seed %d N %d" % (seed, N), p, r, robust, GC.ITERATIONS, rng_seed=10000 + seed)
+
+
 @pytest.mark.parametrize("seed,N,robust,revisit", GC.CASES)
 def test_gpu_cases_keep_their_decisions_away_from_the_thresholds(seed, N, robust, revisit):
     """A device whose chi2 differs from the checker's in the 10th digit takes the same accept / reject and termination decisions only
@@ -182,8 +211,9 @@ def test_gpu_cases_keep_their_decisions_away_from_the_thresholds(seed, N, robust
 def test_the_other_checked_gpu_problems_keep_their_margins():
     """the exact variants the remaining GPU tests compare with the checker (global_ba_cases.checked_variants): same generator arguments,
     same edits, same robust flag and iteration count"""
-    for name, q, robust, iterations in GC.checked_variants(lambda seed, N: _problem(seed, N)):
+    for i, (name, q, robust, iterations) in enumerate(GC.checked_variants(lambda seed, N: _problem(seed, N))):
         r = G.global_ba(*GC.args(q), iterations=iterations, robust=bool(robust))
         rho, term = _margins(r)
         print(name, "trials", "".join("A" if t[4] else "R" for t in r["trials"]), "min |rho| %.3g" % rho, "termination margin %.3g" % term)
         assert rho >= 1e-6 and term >= 1e-6, name
+        _check_perturbation_margin(name, q, r, robust, iterations, rng_seed=20000 + i)

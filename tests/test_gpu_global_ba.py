@@ -76,9 +76,15 @@ def test_global_ba_matches_checker(seed, N, robust, revisit):
     _compare(_solve(p, iterations=GC.ITERATIONS, robust=robust), ref, kf_tol, pt_tol)
 
 
-def test_device_form_equals_host_form():
+# the device form on four cases: every size up to N = 60, both robust flags, both revisit fractions
+DEVICE_FORM_CASES = {1: (3, 0, 0.2), 7: (21, 1, 0.2), 8: (60, 0, 0.0), 11: (60, 1, 0.2)}
+
+
+@pytest.mark.parametrize("index", sorted(DEVICE_FORM_CASES))
+def test_device_form_equals_host_form(index):
     from viorb_amd import GlobalBundleAdjustmentNavStateDevice
-    seed, N, robust, revisit = GC.CASES[7]
+    seed, N, robust, revisit = GC.CASES[index]
+    assert (N, robust, revisit) == DEVICE_FORM_CASES[index]
     p = _problem(seed, N, revisit)
     ref, kf_tol, pt_tol = _reference(seed, N, robust, revisit)
     _compare(GlobalBundleAdjustmentNavStateDevice(*GC.args(p), iterations=GC.ITERATIONS, robust=robust), ref, kf_tol, pt_tol)

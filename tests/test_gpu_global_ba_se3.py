@@ -83,10 +83,15 @@ def test_twenty_robust_iterations_as_the_monocular_initialiser_calls_it():
     _compare(_solve(q, iterations=iterations, robust=robust), ref, kf_tol, pt_tol)
 
 
-def test_device_form_equals_host_form():
+# the device form on six cases of the cross (revisit 0.2): robust 0 / 1 with stereo 0 / 0.5 / 1, alternating between N = 43 and N = 12
+DEVICE_FORM_CASES = {25: (43, 0, 0.0), 15: (12, 0, 0.5), 29: (43, 0, 1.0), 19: (12, 1, 0.0), 33: (43, 1, 0.5), 23: (12, 1, 1.0)}
+
+
+@pytest.mark.parametrize("index", sorted(DEVICE_FORM_CASES))
+def test_device_form_equals_host_form(index):
     from viorb_amd import GlobalBundleAdjustmentSE3Device
-    seed, N, robust, stereo, revisit = GC.CASES[33]
-    assert N == 43
+    seed, N, robust, stereo, revisit = GC.CASES[index]
+    assert (N, robust, stereo) == DEVICE_FORM_CASES[index] and revisit == 0.2
     p = GC.problem(seed, N, stereo, revisit)
     ref, kf_tol, pt_tol = _reference(seed, N, robust, stereo, revisit)
     _compare(GlobalBundleAdjustmentSE3Device(*GC.args(p), iterations=GC.ITERATIONS, robust=robust), ref, kf_tol, pt_tol)

@@ -78,9 +78,8 @@ def main():
             nm, sw = torch.zeros(B, dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.int32, device=dev)
             out = capi.SearchInitOutputs(None, None, None, None, None, None, ptr(sw))
             prev0 = bt.prev.clone()
-            ws = C.c_void_p(bt._ws.data_ptr() + (-bt._ws.data_ptr()) % 256)
             call = lambda: check(L.viorb_search_for_initialization_device(ptr(bt.kps1), ptr(bt.desc1), ptr(bt.count1), C.byref(kf), ptr(bt.prev), cap, B,
-                                                                          ptr(bt.bounds), 100, 0.9, 1, ptr(m12), ptr(nm), C.byref(out), ws, bt._wb, stream()))
+                                                                          ptr(bt.bounds), 100, 0.9, 1, ptr(m12), ptr(nm), C.byref(out), bt.ws.ptr, bt.ws_bytes, stream()))
             r = measure(call, lambda: bt.prev.copy_(prev0), a.reps, "k_si_")
             print(json.dumps(dict(what="viorb_search_for_initialization_device", streams=B, n1=n1, n2=n2, nmatches=int(nm.cpu()[0]), sweeps=int(sw.cpu()[0]), **r)),
                   flush=True)

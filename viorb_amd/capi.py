@@ -547,3 +547,42 @@ def _torch_up(a, device=0):
     if a.dtype.fields is not None:
         a = a.view(np.uint8)
     return torch.from_numpy(a).to(torch.device("cuda", device))
+
+
+WORKSPACE_GUARD = 4096
+
+
+class Workspace:
+    """The one allocator of the caller workspaces the device entry points take: `nbytes` of device memory behind a 256-byte aligned
+    pointer, with WORKSPACE_GUARD bytes behind them that no entry point may touch. fill: 0 (the default, what the wrappers always
+    handed over), a byte value 1 .. 255, or None to leave the memory as the allocator returned it; the guard is filled with it too. The
+    headers promise that a workspace's contents on entry are ignored, and tests/test_gpu_workspace_contents.py holds the library to
+    that by re-filling `tensor` before a call and by handing one allocation to two problems of different sizes. A wrapper passes `ptr`
+    and the byte count its own problem needs, never `nbytes`, which may be larger when an allocation is shared."""
+
+    def __init__(self, torch, device, nbytes, fill=0):
+        self.nbytes = int(nbytes)
+        self.tensor = torch.empty(self.nbytes + 256 + WORKSPACE_GUARD, dtype=torch.uint8, device=device)
+        self.offset = (-self.tensor.data_ptr()) % 256
+        self.ptr = C.c_void_p(self.tensor.data_ptr() + self.offset)
+        self.fill(fill)
+
+    def fill(self, value):
+        """Every byte of the allocation, guard included, set to `value`; None leaves it as it is."""
+        if value is not None:
+            self.tensor.fill_(int(value))
+        return self
+
+    def body(self, nbytes=None):
+        """The first nbytes (default: all) of the workspace as a uint8 view."""
+        n = self.nbytes if nbytes is None else int(nbytes)
+        return self.tensor[self.offset:self.offset + n]
+
+    def guard(self, nbytes=None):
+        """The WORKSPACE_GUARD bytes behind a workspace of nbytes (default: all) as a uint8 view."""
+        n = self.nbytes if nbytes is None else int(nbytes)
+        assert n <= self.nbytes
+        return self.tensor[self.offset + n:self.offset + n + WORKSPACE_GUARD]
+
+    def fits(self, nbytes):
+        return self.nbytes >= int(nbytes)

@@ -129,10 +129,10 @@ class CullBatch:
         self.o = S.outputs(capi.CULL_RESULT_FIELDS, lambda f: max(P[_OUT_LEN[f]], 1), _OUT_DT.get, torch, self.dev)
         self.res = S.struct(capi.CullResult, (), capi.CULL_RESULT_FIELDS, self.o)
         self._wb = lib().viorb_key_frame_culling_workspace_bytes(P["batch"], P["n_kf"], P["n_cand"], P["n_pt"], P["n_obs"])
-        self._ws, self._wp = S.workspace(torch, self.dev, self._wb)
+        self.ws = capi.Workspace(torch, self.dev, self._wb)         # may be re-filled or replaced by a larger one between calls
 
     def run(self, outputs=True):
-        check(lib().viorb_key_frame_culling_device(C.byref(self.map), int(self.monocular), C.byref(self.res) if outputs else None, self._wp, self._wb,
+        check(lib().viorb_key_frame_culling_device(C.byref(self.map), int(self.monocular), C.byref(self.res) if outputs else None, self.ws.ptr, self._wb,
                                                    S.stream_ptr(self.torch, self.dev)))
 
     def inputs(self):

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 from . import capi
 from .capi import lib, check, ptr, _torch_up as up
-from .global_ba import last_trials, INFO  # noqa: F401
+from .global_ba import last_trials, INFO, _workspace  # noqa: F401
 
 _f64 = lambda a: np.ascontiguousarray(a, np.float64)
 _f32 = lambda a: np.ascontiguousarray(a, np.float32)
@@ -42,9 +42,10 @@ def OptimizeEssentialGraph(Scw, Smeas, fixed, edge_idx, edge_corrected, points=N
     return _result(So, To, Po, info)
 
 
-def OptimizeEssentialGraphDevice(Scw, Smeas, fixed, edge_idx, edge_corrected, points=None, point_ref=None, fix_scale=False, iterations=20):
+def OptimizeEssentialGraphDevice(Scw, Smeas, fixed, edge_idx, edge_corrected, points=None, point_ref=None, fix_scale=False, iterations=20, workspace=None):
     """viorb_optimize_essential_graph_device: the arrays are uploaded here as torch tensors on cuda:0 (a map that lives on the device);
-    the results come back as numpy arrays."""
+    the results come back as numpy arrays. workspace: a capi.Workspace at least as large as the problem needs, used as it is; default: a
+    fresh one, not cleared."""
     import torch
     dev = torch.device("cuda", 0)
     Scw, Smeas, fixed, ei, ec, pts, ref = _arrays(Scw, Smeas, fixed, edge_idx, edge_corrected, points, point_ref)
@@ -52,20 +53,20 @@ def OptimizeEssentialGraphDevice(Scw, Smeas, fixed, edge_idx, edge_corrected, po
              pts=up(pts if len(pts) else np.zeros((1, 3), np.float32)), ref=up(ref if len(pts) else np.zeros(1, np.int32)))
     So = torch.zeros_like(t["Scw"]); To = torch.zeros((len(Scw), 12), dtype=torch.float64, device=dev); Po = torch.zeros_like(t["pts"])
     nbytes = essential_graph_workspace_bytes(len(Scw), len(ei), len(pts))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace(torch, dev, nbytes, workspace)
     info = np.zeros(6)
     cfg = capi.EgConfig(int(iterations), int(bool(fix_scale)))
     torch.cuda.synchronize()
     check(lib().viorb_optimize_essential_graph_device(C.byref(cfg), ptr(t["Scw"]), ptr(t["Smeas"]), ptr(t["fixed"]), len(Scw), ptr(t["ei"]), ptr(t["ec"]), len(ei),
-                                                      ptr(t["pts"]), ptr(t["ref"]), len(pts), ptr(So), ptr(To), ptr(Po), ptr(info), ptr(ws), nbytes, None))
+                                                      ptr(t["pts"]), ptr(t["ref"]), len(pts), ptr(So), ptr(To), ptr(Po), ptr(info), ws.ptr, nbytes, None))
     return _result(So.cpu().numpy(), To.cpu().numpy(), Po.cpu().numpy()[:len(pts)], info)
 
 
-def solve(prob, device=False, iterations=20):
-    """A problem dictionary through the host or the device form."""
+def solve(prob, device=False, iterations=20, **kw):
+    """A problem dictionary through the host or the device form (kw: workspace, device form only)."""
     f = OptimizeEssentialGraphDevice if device else OptimizeEssentialGraph
     return f(prob["Scw"], prob["Smeas"], prob["fixed"], prob["edge_idx"], prob["edge_corrected"], prob.get("points"), prob.get("point_ref"),
-             fix_scale=prob["fix_scale"], iterations=iterations)
+             fix_scale=prob["fix_scale"], iterations=iterations, **kw)
 
 
 def debug_sim3_log(S8):

@@ -25,6 +25,14 @@ def _result(ko, po, inc, info):
                 trials=int(info[3]), final_lambda=info[4], failed_factorisations=int(info[5]))
 
 
+def _workspace(torch, dev, nbytes, given):
+    """The caller's capi.Workspace when it gave one, else a fresh one of nbytes; its contents stay as they are either way."""
+    if given is None:
+        return capi.Workspace(torch, dev, nbytes, fill=None)
+    assert given.fits(nbytes)
+    return given
+
+
 def gba_workspace_bytes(nk, n_points, n_edges):
     return int(lib().viorb_global_ba_navstate_workspace_bytes(nk, n_points, n_edges))
 
@@ -44,9 +52,10 @@ def GlobalBundleAdjustmentNavState(kfs, prev, fixed, preint, points, edge_idx, e
     return _result(ko, po, inc[:len(points)], info)
 
 
-def GlobalBundleAdjustmentNavStateDevice(kfs, prev, fixed, preint, points, edge_idx, edge_obs, gw, cam, iterations=10, robust=False, stop=None):
+def GlobalBundleAdjustmentNavStateDevice(kfs, prev, fixed, preint, points, edge_idx, edge_obs, gw, cam, iterations=10, robust=False, stop=None, workspace=None):
     """viorb_global_ba_navstate_device: the arrays are uploaded here as torch tensors on cuda:0 (the mapping thread's device-resident
-    form); the results come back as numpy arrays."""
+    form); the results come back as numpy arrays. workspace: a capi.Workspace at least as large as the problem needs, used as it is (a
+    caller that keeps one allocation across solves); default: a fresh one, not cleared."""
     import torch
     dev = torch.device("cuda", 0)
     kfs = _f64(kfs).reshape(-1, 22); points = _f64(points).reshape(-1, 3); ei = _i32(edge_idx).reshape(-1, 2)
@@ -56,13 +65,13 @@ def GlobalBundleAdjustmentNavStateDevice(kfs, prev, fixed, preint, points, edge_
     ko, po = torch.zeros_like(t["kfs"]), torch.zeros_like(t["points"])
     inc = torch.zeros(max(len(points), 1), dtype=torch.uint8, device=dev)
     nbytes = gba_workspace_bytes(len(kfs), len(points), len(ei))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace(torch, dev, nbytes, workspace)
     info = np.zeros(6)
     cfg = capi.GbaConfig(int(iterations), int(bool(robust)))
     torch.cuda.synchronize()
     check(lib().viorb_global_ba_navstate_device(C.byref(cfg), ptr(t["kfs"]), len(kfs), ptr(t["prev"]), ptr(t["fixed"]), ptr(t["preint"]), ptr(t["points"]),
                                                 len(points), ptr(t["ei"]), ptr(t["eo"]), len(ei), ptr(_f64(gw)), ptr(_f64(cam)),
-                                                ptr(stop) if stop is not None else None, ptr(ko), ptr(po), ptr(inc), ptr(info), ptr(ws), nbytes, None))
+                                                ptr(stop) if stop is not None else None, ptr(ko), ptr(po), ptr(inc), ptr(info), ws.ptr, nbytes, None))
     return _result(ko.cpu().numpy(), po.cpu().numpy()[:len(points)], inc.cpu().numpy()[:len(points)], info)
 
 
@@ -85,8 +94,9 @@ def GlobalBundleAdjustmentSE3(kfs, fixed, points, edge_idx, edge_obs, intr5, ite
     return _result(ko, po, inc[:len(points)], info)
 
 
-def GlobalBundleAdjustmentSE3Device(kfs, fixed, points, edge_idx, edge_obs, intr5, iterations=10, robust=False, stop=None):
-    """viorb_global_ba_se3_device: the arrays are uploaded here as torch tensors on cuda:0; the results come back as numpy arrays."""
+def GlobalBundleAdjustmentSE3Device(kfs, fixed, points, edge_idx, edge_obs, intr5, iterations=10, robust=False, stop=None, workspace=None):
+    """viorb_global_ba_se3_device: the arrays are uploaded here as torch tensors on cuda:0; the results come back as numpy arrays.
+    workspace as GlobalBundleAdjustmentNavStateDevice."""
     import torch
     dev = torch.device("cuda", 0)
     kfs = _f64(kfs).reshape(-1, 7); points = _f64(points).reshape(-1, 3); ei = _i32(edge_idx).reshape(-1, 2)
@@ -95,13 +105,13 @@ def GlobalBundleAdjustmentSE3Device(kfs, fixed, points, edge_idx, edge_obs, intr
     ko, po = torch.zeros_like(t["kfs"]), torch.zeros_like(t["points"])
     inc = torch.zeros(max(len(points), 1), dtype=torch.uint8, device=dev)
     nbytes = gba_se3_workspace_bytes(len(kfs), len(points), len(ei))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace(torch, dev, nbytes, workspace)
     info = np.zeros(6)
     cfg = capi.GbaConfig(int(iterations), int(bool(robust)))
     torch.cuda.synchronize()
     check(lib().viorb_global_ba_se3_device(C.byref(cfg), ptr(t["kfs"]), len(kfs), ptr(t["fixed"]), ptr(t["points"]), len(points), ptr(t["ei"]), ptr(t["eo"]),
                                            len(ei), ptr(_f64(intr5)), ptr(stop) if stop is not None else None, ptr(ko), ptr(po), ptr(inc), ptr(info),
-                                           ptr(ws), nbytes, None))
+                                           ws.ptr, nbytes, None))
     return _result(ko.cpu().numpy(), po.cpu().numpy()[:len(points)], inc.cpu().numpy()[:len(points)], info)
 
 

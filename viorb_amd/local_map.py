@@ -130,13 +130,13 @@ class LocalMapBatch:
         self.o = S.outputs(capi.LOCAL_MAP_RESULT_FIELDS, lambda f: out_len(P, f), lambda f: np.int32, torch, self.dev)
         self.res = S.struct(capi.LocalMapResult, (), capi.LOCAL_MAP_RESULT_FIELDS, self.o)
         self._wb = lib().viorb_update_local_map_workspace_bytes(P["batch"], P["n_kf"], P["n_pt"])
-        self._ws, self._wp = S.workspace(torch, self.dev, self._wb)
+        self.ws = capi.Workspace(torch, self.dev, self._wb)         # both may be re-filled or replaced by larger ones between calls
         self._gb = lib().viorb_local_points_gather_workspace_bytes(P["n_pt"])
-        self._gs, self._gp = S.workspace(torch, self.dev, self._gb)
+        self.gather_ws = capi.Workspace(torch, self.dev, self._gb)
 
     def run(self, outputs=True):
         P = self.P
-        check(lib().viorb_update_local_map_device(C.byref(self.map), C.byref(self.res) if outputs else None, P["cap"], P["lcap"], P["pcap"], self._wp, self._wb,
+        check(lib().viorb_update_local_map_device(C.byref(self.map), C.byref(self.res) if outputs else None, P["cap"], P["lcap"], P["pcap"], self.ws.ptr, self._wb,
                                                   S.stream_ptr(self.torch, self.dev)))
 
     def results(self):
@@ -154,7 +154,7 @@ class LocalMapBatch:
             pf = torch.full((B, pcap, 8), 7.0, dtype=torch.float32, device=self.dev); pd = torch.full((B, pcap, 32), 7, dtype=torch.uint8, device=self.dev)
             pc = torch.full((B,), 77, dtype=torch.int32, device=self.dev); pfl = torch.full((B, pcap), 77, dtype=torch.uint8, device=self.dev)
         check(lib().viorb_local_points_gather_device(C.byref(self.map), C.byref(self.res), P["cap"], pcap, ptr(map_pts_f), ptr(map_pts_desc), ptr(pt_nobs),
-                                                     ptr(pf), ptr(pd), ptr(pc), ptr(pfl), self._gp, self._gb, S.stream_ptr(self.torch, self.dev)))
+                                                     ptr(pf), ptr(pd), ptr(pc), ptr(pfl), self.gather_ws.ptr, self._gb, S.stream_ptr(self.torch, self.dev)))
         return pf, pd, pc, pfl
 
 

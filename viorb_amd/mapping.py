@@ -154,8 +154,7 @@ class CreateNewMapPoints:
         self.new_desc = torch.zeros((B, pcap, 32), dtype=torch.uint8, device=dev)
         self.n_new = torch.zeros(B, dtype=torch.int32, device=dev); self.status = torch.zeros(B, dtype=torch.int32, device=dev)
         self.ws_bytes = lib().viorb_create_new_map_points_workspace_bytes(cap, B)
-        self.ws = torch.zeros(self.ws_bytes + 256, dtype=torch.uint8, device=dev)
-        self.ws_ptr = (self.ws.data_ptr() + 255) & ~255
+        self.ws = capi.Workspace(torch, dev, self.ws_bytes)         # may be re-filled or replaced by a larger one between calls
 
     def __call__(self, j_begin=0, j_end=None):
         torch, dev = _dev()
@@ -165,7 +164,7 @@ class CreateNewMapPoints:
             C.byref(self.cam), self.monocular, ptr(self.k1), ptr(self.d1), ptr(self.hp1), ptr(self.ur1), ptr(self.dep1), ptr(self.xy1), ptr(self.node1), ptr(self.n1),
             ptr(self.T1), ptr(self.O1), ptr(self.k2), ptr(self.d2), ptr(self.hp2), ptr(self.ur2), ptr(self.dep2), ptr(self.xy2), ptr(self.node2), ptr(self.n2),
             ptr(self.T2), ptr(self.O2), ptr(self.F12), ptr(self.md2), ptr(self.kf2_first), ptr(self.n_neigh), self.J, j_begin, j_end, self.cap, self.B, self.pcap,
-            ptr(self.new_idx), ptr(self.new_pts_f), ptr(self.new_desc), ptr(self.n_new), ptr(self.status), C.c_void_p(self.ws_ptr), self.ws_bytes, C.c_void_p(st)))
+            ptr(self.new_idx), ptr(self.new_pts_f), ptr(self.new_desc), ptr(self.n_new), ptr(self.status), self.ws.ptr, self.ws_bytes, C.c_void_p(st)))
         return self
 
     def results(self):

@@ -131,11 +131,12 @@ class KeyFrameDatabase:
                                      ptr(flat) if loop else None, ptr(cov), cand_cap, ptr(cand), ptr(ncand), ptr(stats), ptr(common), ptr(score)))
         return dict(cand=[cand[q, :ncand[q]].tolist() for q in range(n_q)], stats=stats[:n_q], common=common[:n_q, :S], score=score[:n_q, :S])
 
-    def query_device(self, mode, q_word, q_val, q_count, covis10, min_scores=None, excl_start=None, excl_slot=None, cand_cap=64, want_rows=True):
+    def query_device(self, mode, q_word, q_val, q_count, covis10, min_scores=None, excl_start=None, excl_slot=None, cand_cap=64, want_rows=True, workspace=None):
         """viorb_kfdb_query_device on torch tensors (q_word / q_val [n_q, q_cap], q_count [n_q], covis10 [n_slots, 10] int32, loop mode:
         min_scores float32 [n_q], excl_start int32 [n_q + 1], excl_slot int32): dict of device tensors cand [n_q, cand_cap], n_cand, stats,
         common, score. Nothing is copied to the host and the stream is not waited for, also after adds and erasures (they reach the
-        device's alive[] by memsets on the same stream)."""
+        device's alive[] by memsets on the same stream). workspace: a capi.Workspace at least as large as the query needs, used as it is;
+        default: a fresh one, not cleared."""
         import torch
         n_q, q_cap = q_word.shape
         S, dev = self.size()[0], q_word.device
@@ -144,12 +145,12 @@ class KeyFrameDatabase:
         common = z((n_q, max(S, 1)), torch.int32) if want_rows else None
         score = z((n_q, max(S, 1)), torch.float32, -1.0) if want_rows else None
         wb = int(lib().viorb_kfdb_query_workspace_bytes(self.h, n_q))
-        ws = torch.empty(wb + 256, dtype=torch.uint8, device=dev)
-        wp = (ws.data_ptr() + 255) & ~255
+        ws = workspace if workspace is not None else capi.Workspace(torch, dev, wb, fill=None)
+        assert ws.fits(wb)
         check(lib().viorb_kfdb_query_device(self.h, int(mode), n_q, ptr(q_word), ptr(q_val), ptr(q_count), q_cap, ptr(min_scores), ptr(excl_start), ptr(excl_slot),
-                                            ptr(covis10), int(cand_cap), ptr(cand), ptr(ncand), ptr(stats), ptr(common), ptr(score), C.c_void_p(wp), wb,
+                                            ptr(covis10), int(cand_cap), ptr(cand), ptr(ncand), ptr(stats), ptr(common), ptr(score), ws.ptr, wb,
                                             _stream(q_word)))
-        return dict(cand=cand, n_cand=ncand, stats=stats, common=common, score=score, workspace=ws)
+        return dict(cand=cand, n_cand=ncand, stats=stats, common=common, score=score, workspace=ws.tensor)
 
     def detect_loop_candidates(self, bow, min_score, connected, covis10):
         """DetectLoopCandidates(pKF, minScore): the candidate slots in the reference's order. connected = GetConnectedKeyFrames() as slots."""

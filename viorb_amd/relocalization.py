@@ -64,15 +64,16 @@ class RelocBatch:
             for b, r in enumerate(uright):
                 u[b, :len(r)] = _f32(r)
             self.uright = _up(u, device)
-        self._ws = None
+        self.ws = None                                              # a capi.Workspace once a call needed one; a test may put its own here
 
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
 
     def _workspace(self, wb):
-        if self._ws is None or self._ws.numel() < wb + 256:
-            self._ws = self.torch.zeros(wb + 256, dtype=self.torch.uint8, device=self.dev)
-        return C.c_void_p(self._ws.data_ptr() + (-self._ws.data_ptr()) % 256), wb
+        self.ws_bytes = wb                                          # what the last call was handed
+        if self.ws is None or not self.ws.fits(wb):
+            self.ws = capi.Workspace(self.torch, self.dev, wb)
+        return self.ws.ptr, wb
 
     def _pad(self, rows, cap, tail, dtype, fill=0):
         a = np.full((len(rows), cap) + tail, fill, dtype)
@@ -102,7 +103,7 @@ class RelocBatch:
         re = t.zeros((B, kcap), dtype=t.int32, device=self.dev) if with_reason else None
         nm = t.zeros(B, dtype=t.int32, device=self.dev)
         ws, wb = self._workspace(lib().viorb_relocalization_workspace_bytes(self.cap, kcap, B))
-        buf = self._ws                                              # the closures keep the workspace and the uploads alive
+        buf = self.ws.tensor                                        # the closures keep the workspace and the uploads alive
 
         def call():
             check(lib().viorb_search_by_projection_reloc_device(C.byref(self.fr.kf), self.fr.B, ptr(hf), ptr(d["pose12"]), ptr(d["kf_angle"]), ptr(d["kf_valid"]),
@@ -140,7 +141,7 @@ class RelocBatch:
                  chi2=z(B, t.float64), frame_match=z((B, self.cap), t.int32), outlier=z((B, self.cap), t.uint8))
         O = capi.RelocOutputs(**{k: ptr(o[k]) for k in capi.RELOC_OUTPUT_FIELDS})
         ws, wb = self._workspace(lib().viorb_relocalization_refine_workspace_bytes(self.cap, kcap, hcap.value, B))
-        buf = self._ws
+        buf = self.ws.tensor
 
         def call():
             check(lib().viorb_relocalization_refine_device(frontend.h, C.byref(I), C.byref(cfg), C.byref(self.cam), ptr(self.bounds), float(bf), B, C.byref(O), ws, wb,

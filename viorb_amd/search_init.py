@@ -68,8 +68,7 @@ class SearchInitBatch:
             pm[b, :self.n1[b]] = _f32(p).reshape(-1, 2)
         self.prev = _up(pm, device)
         wb = lib().viorb_search_init_workspace_bytes(self.cap, self.B)
-        self._ws = torch.zeros(wb + 256, dtype=torch.uint8, device=self.dev)
-        self._wb = wb
+        self.ws, self.ws_bytes = capi.Workspace(torch, self.dev, wb), wb          # ws may be re-filled or replaced by a larger one between calls
 
     def _frames(self, frames, garbage=None):
         kps, desc = np.zeros((self.B, self.cap), capi.KP_DTYPE), np.zeros((self.B, self.cap, 32), np.uint8)
@@ -102,10 +101,9 @@ class SearchInitBatch:
                  rot_hist=zi(self.B, 30), reason=zi(self.B, self.cap), xy1=t.zeros((self.B, self.cap, 2), dtype=t.float32, device=self.dev),
                  xy2=t.zeros((self.B, self.cap, 2), dtype=t.float32, device=self.dev), sweeps=zi(self.B))
         out = capi.SearchInitOutputs(*[ptr(d[f]) for f in capi.SEARCH_INIT_OUTPUT_FIELDS])
-        ws = C.c_void_p(self._ws.data_ptr() + (-self._ws.data_ptr()) % 256)
         check(lib().viorb_search_for_initialization_device(ptr(self.kps1), ptr(self.desc1), ptr(self.count1), C.byref(kf), ptr(self.prev), self.cap, self.B,
                                                            ptr(self.bounds), int(window_size), float(np.float32(nnratio)), int(bool(check_orientation)),
-                                                           ptr(d["matches12"]), ptr(d["nmatches"]), C.byref(out), ws, self._wb, self._stream()))
+                                                           ptr(d["matches12"]), ptr(d["nmatches"]), C.byref(out), self.ws.ptr, self.ws_bytes, self._stream()))
         if raw:
             self._keep = (kps2, desc2, count2, cs, ci)
             return dict(matches12=d["matches12"], xy1=d["xy1"], xy2=d["xy2"], n1=self.count1, n2=count2)

@@ -91,9 +91,11 @@ class Sim3Batch:
         self.inputs = capi.Sim3Inputs(*[ptr(a) for a in self.d], self.cap)
         self.sets = _up(np.stack([_i32(s).reshape(-1, 3) for s in sets]), device)
         wb = lib().viorb_sim3_workspace_bytes(self.cap, self.iters, self.B)
-        self.ws = torch.zeros(wb + 256, dtype=torch.uint8, device=self.dev)
-        off = (-self.ws.data_ptr()) % 256
-        self.ws_ptr, self.ws_bytes = C.c_void_p(self.ws.data_ptr() + off), wb
+        self.ws, self.ws_bytes = capi.Workspace(torch, self.dev, wb), wb          # ws may be re-filled or replaced by a larger one between calls
+
+    @property
+    def ws_ptr(self):
+        return self.ws.ptr
 
     def _cfg(self, iterations_per_call=5):
         return sim3_config(self.iters, self.min_inliers, self.fix_scale, iterations_per_call)

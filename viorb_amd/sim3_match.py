@@ -106,16 +106,17 @@ class Sim3MatchBatch:
         check(lib().viorb_keyframe_grid_device(ptr(self.kps), ptr(self.count), self.cap, self.B, ptr(self.bounds), ptr(self.cell_start), ptr(self.cell_idx),
                                                self._stream()))
         self.kf = capi.S3mKeyframes(ptr(self.kps), ptr(self.desc), ptr(self.count), ptr(self.cell_start), ptr(self.cell_idx), self.cap)
-        self._ws = None
+        self.ws = None                                              # a capi.Workspace once a call needed one; a test may put its own here
 
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
 
     def _workspace(self, cap, pcap):
         wb = lib().viorb_sim3_match_workspace_bytes(int(cap), int(pcap), self.B)
-        if self._ws is None or self._ws.numel() < wb + 256:
-            self._ws = self.torch.zeros(wb + 256, dtype=self.torch.uint8, device=self.dev)
-        return C.c_void_p(self._ws.data_ptr() + (-self._ws.data_ptr()) % 256), wb
+        self.ws_bytes = wb                                          # what the last call was handed
+        if self.ws is None or not self.ws.fits(wb):
+            self.ws = capi.Workspace(self.torch, self.dev, wb)
+        return self.ws.ptr, wb
 
     def _pad(self, rows, cap, tail, dtype):
         """rows: one array per key frame -> [B, cap, *tail] on the device."""

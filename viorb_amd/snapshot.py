@@ -1,6 +1,6 @@
 """What the wrappers of the map-reading stages (culling.py, local_map.py) share: laying a list of per-stream scenes out as the flat arrays
 of a batched snapshot (stream-local offsets and indices, DESIGN.md "Map snapshots"), the ctypes structs over host or device arrays, the
-result arrays with their fill value, the workspace, and the file that the host test programs' `time` mode reads."""
+result arrays with their fill value, and the file that the host test programs' `time` mode reads."""
 import ctypes as C
 import numpy as np
 from .capi import ptr, _torch_up as _up
@@ -55,12 +55,6 @@ def outputs(fields, length, dtype, torch=None, dev=None):
     if torch is None:
         return {f: np.full(length(f), FILL, dtype(f)) for f in fields}
     return {f: torch.full((length(f),), FILL, dtype=getattr(torch, np.dtype(dtype(f)).name), device=dev) for f in fields}
-
-
-def workspace(torch, dev, nbytes):
-    """(the tensor that owns it, a 256-byte aligned pointer to nbytes of zeroed device memory)."""
-    t = torch.zeros(nbytes + 256, dtype=torch.uint8, device=dev)
-    return t, C.c_void_p(t.data_ptr() + (-t.data_ptr()) % 256)
 
 
 def stream_ptr(torch, dev):

@@ -84,9 +84,11 @@ class TwoViewBatch:
         self.sets = _up(np.stack([_i32(s).reshape(-1, 8) for s in sets]), device)
         self.N = [int((np.asarray(p["matches12"]) >= 0).sum()) for p in probs]
         wb = lib().viorb_two_view_workspace_bytes(self.cap, self.iters, self.B)
-        self.ws = torch.zeros(wb + 256, dtype=torch.uint8, device=self.dev)
-        off = (-self.ws.data_ptr()) % 256
-        self.ws_ptr, self.ws_bytes = C.c_void_p(self.ws.data_ptr() + off), wb
+        self.ws, self.ws_bytes = capi.Workspace(torch, self.dev, wb), wb          # ws may be re-filled or replaced by a larger one between calls
+
+    @property
+    def ws_ptr(self):
+        return self.ws.ptr
 
     def _in(self):
         d = self.d
