@@ -6,7 +6,7 @@
 //
 // Deliberately NOT shared, because the solves differ there on purpose:
 //   * the two Cholesky designs (one-workgroup MFMA solve of the window, blocked launch chain of the map)
-//   * the Levenberg control (device-side ctl of the window, gba_lm_trial on the host for the map)
+//   * where the Levenberg control runs (device-side ctl of the window, the host for the map); its rule is lm_core.h's
 //   * the window's pair-gathered Schur complement, and the window's back-substitution: it subtracts term by term where the map's
 //     subtracts a finished sum — a different rounding, hence two functions
 //   * pose_opt_mp.inc and proj_edge / se3_edge of vio_core.h: the only-pose edges, which divide by z differently

@@ -14,6 +14,7 @@
 #include "viorb_common.h"
 #include "sim3_match_core.h"        // match_core.h, s3m_predict_level
 #include "vio_core.h"
+#include "lm_core.h"
 
 namespace viorb {
 
@@ -1442,7 +1443,7 @@ __global__ __launch_bounds__(256) void k_pose_opt_se3(Se3Args A) {
         for (int it = 0; it < 10; it++) {
             double currentChi = evaluate(true);
             const double iniChi = currentChi;
-            if (it == 0) { double mx = 0; for (int i = 0; i < 6; i++) mx = fmax(fabs(S.H[i * 7]), mx); lambda = 1e-5 * mx; ni = 2; nBadLM = 0; }
+            if (it == 0) { double mx = 0; for (int i = 0; i < 6; i++) mx = fmax(fabs(S.H[i * 7]), mx); lambda = lm_lambda_init(mx); ni = 2; nBadLM = 0; }
             double rho = 0; int qmax = 0;
             do {
                 if (t < 7) S.bak[t] = S.est[t];
@@ -1459,21 +1460,16 @@ __global__ __launch_bounds__(256) void k_pose_opt_se3(Se3Args A) {
                 }
                 __syncthreads();
                 if (t < 7) S.ev[t] = S.est[t];
-                double tempChi = evaluate(false);
-                if (!ok2) tempChi = 1.7976931348623157e308;
-                double scale = 0; for (int j = 0; j < 6; j++) scale += S.x[j] * (lambda * S.x[j] + S.b[j]);
-                scale += 1e-3;
-                rho = (currentChi - tempChi) / scale;
-                last_rejected = !(rho > 0 && isfinite(tempChi));
-                if (!last_rejected) { double alpha = 1. - pow(2 * rho - 1, 3); alpha = fmin(alpha, 2. / 3.); lambda *= fmax(1. / 3., alpha); ni = 2; currentChi = tempChi; }
-                else { lambda *= ni; ni *= 2; if (t < 7) S.est[t] = S.bak[t]; }
+                const double tempChi = lm_trial_chi2(ok2, evaluate(false));
+                rho = lm_rho(currentChi, tempChi, lm_scale<6>(S.x, S.b, lambda));
+                last_rejected = !lm_accepted(rho, tempChi);
+                if (!last_rejected) { lm_good_step(lambda, ni, lm_cube_pow(2 * rho - 1)); currentChi = tempChi; }
+                else { lm_bad_step(lambda, ni); if (t < 7) S.est[t] = S.bak[t]; }
                 __syncthreads();
                 qmax++;
-            } while (rho < 0 && qmax < 10);
+            } while (lm_retry(rho, qmax));
             if (t == 0) { S.flag[1]++; S.sc[7] = currentChi; }
-            if (qmax == 10 || rho == 0) break;
-            if ((iniChi - currentChi) * 1e3 < iniChi) nBadLM++; else nBadLM = 0;
-            if (nBadLM >= 3) break;
+            if (lm_iteration_stops(rho, qmax, iniChi, currentChi, nBadLM)) break;
         }
         __syncthreads();
         {

@@ -538,8 +538,8 @@ int gba_run(const viorb_gba_config* cfg, GbaDev& D, const GbaOps& ops, void* wor
     VIORB_TRY(ops.linearise(D, st));
     VIORB_LAUNCH(k_gba_max_diag, gba_blocks((size_t)D.n + 3 * (size_t)D.np, 256 * 8), 256, 0, st, D);
     if (int rc = read_scal()) return rc;
-    gba_lm L; L.cur = pinned[GBA_S_CHI]; L.lambda = ops.lambda_init > 0 ? ops.lambda_init : 1e-5 * pinned[GBA_S_MAXDIAG]; L.ni = 2;
-    const double chi_before = L.cur;
+    double cur = pinned[GBA_S_CHI], lambda = ops.lambda_init > 0 ? ops.lambda_init : lm_lambda_init(pinned[GBA_S_MAXDIAG]), ni = 2;
+    const double chi_before = cur;
     int its = 0, trials = 0, nfail = 0, nbad = 0;
     gba_trials().clear();
     bool stale = false;
@@ -548,22 +548,24 @@ int gba_run(const viorb_gba_config* cfg, GbaDev& D, const GbaOps& ops, void* wor
             if (stale) { VIORB_TRY(ops.errors(D, st)); stale = false; }   // unless the last trial was rejected and restored
             VIORB_TRY(ops.linearise(D, st));
         }
-        const double ini = L.cur;
+        const double ini = cur;
         VIORB_HIP_TRY(hipMemcpyAsync(D.kf_bak, D.kf, (size_t)D.nk * D.kf_w * sizeof(double), hipMemcpyDeviceToDevice, st));
         if (D.np) VIORB_HIP_TRY(hipMemcpyAsync(D.pt_bak, D.pt, (size_t)D.np * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
         double rho = 0; int qmax = 0;
         do {
             VIORB_HIP_TRY(hipMemsetAsync(D.scal, 0, 3 * sizeof(double), st));
             VIORB_HIP_TRY(hipMemsetAsync(D.S, 0, S_bytes, st));
-            VIORB_TRY(ops.reduce(D, L.lambda, st));
+            VIORB_TRY(ops.reduce(D, lambda, st));
             VIORB_TRY(gba_factor_solve(D, st, true));
-            VIORB_TRY(ops.step(D, L.lambda, st));
+            VIORB_TRY(ops.step(D, lambda, st));
             VIORB_TRY(ops.errors(D, st));
             if (int rc = read_scal()) return rc;
             const bool ok = pinned[GBA_S_FAIL] == 0.0;
             if (!ok) nfail++;
-            bool accepted;
-            rho = gba_lm_trial(L, ok ? pinned[GBA_S_CHI] : DBL_MAX, ok ? pinned[GBA_S_SCALE] : 0.0, &accepted);
+            const double tmp = lm_trial_chi2(ok, pinned[GBA_S_CHI]);
+            rho = lm_rho(cur, tmp, ok ? pinned[GBA_S_SCALE] : 0.0);
+            const bool accepted = lm_accepted(rho, tmp);
+            if (accepted) { lm_good_step(lambda, ni, lm_cube_pow(2 * rho - 1)); cur = tmp; } else lm_bad_step(lambda, ni);
             stale = !accepted;
             gba_trials().push_back(accepted ? 1 : 0);
             if (!accepted) {
@@ -571,13 +573,11 @@ int gba_run(const viorb_gba_config* cfg, GbaDev& D, const GbaOps& ops, void* wor
                 if (D.np) VIORB_HIP_TRY(hipMemcpyAsync(D.pt, D.pt_bak, (size_t)D.np * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
             }
             qmax++; trials++;
-        } while (rho < 0 && qmax < 10 && !stopped());
+        } while (lm_retry(rho, qmax) && !stopped());
         its++;
-        if (qmax == 10 || rho == 0) break;
-        if ((ini - L.cur) * 1e3 < ini) nbad++; else nbad = 0;
-        if (nbad >= 3) break;
+        if (lm_iteration_stops(rho, qmax, ini, cur, nbad)) break;
     }
-    info[0] = chi_before; info[1] = L.cur; info[2] = its; info[3] = trials; info[4] = L.lambda; info[5] = nfail;
+    info[0] = chi_before; info[1] = cur; info[2] = its; info[3] = trials; info[4] = lambda; info[5] = nfail;
     return VIORB_OK;
 }
 

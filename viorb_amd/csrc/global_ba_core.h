@@ -1,16 +1,16 @@
 // viorb_amd/csrc/global_ba_core.h — what the global bundle adjustment (global_ba.hip) shares between host and device: sizes, the
 // argument predicates both the host form (before any GPU call) and the device form (in a kernel) apply, the 9 x 9 inverse behind the
-// IMU factor's information matrix and the Levenberg step of g2o.
+// IMU factor's information matrix. The Levenberg control of gba_run is lm_core.h's.
 //
 // What is restated (reference file:line):
 //   Optimizer::GlobalBundleAdjustmentNavState           src/Optimizer.cc:50-320
-//   OptimizationAlgorithmLevenberg::solve               Thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp:61-164
 // The edges, the blocks of the normal equations and the Huber deltas are those of ba_core.h, which the window solves use too; the IMU
 // factor, the retraction and the Huber kernel those of vio_core.h.
 #pragma once
 #include <float.h>
 #include <cmath>
 #include "ba_core.h"
+#include "lm_core.h"
 
 #define GBA_NB 64                      // block order of the Cholesky: tile factor, panel solve and trailing update work on 64 x 64 tiles
 #define GBA_MAX_FREE_KF 2048           // documented limit: a reduced system of order 24576 (4.8 GB); more returns VIORB_ERR_CAPACITY
@@ -38,21 +38,6 @@ VIO_HD bool gba_inverse9(const double* a_in, double* inv) {
         for (int i = 0; i < 9; i++) if (i != col) { const double f = a[i * 9 + col]; if (f == 0) continue; for (int j = 0; j < 9; j++) { a[i * 9 + j] -= f * a[col * 9 + j]; inv[i * 9 + j] -= f * inv[col * 9 + j]; } }
     }
     return true;
-}
-
-// One Levenberg trial's decision (optimization_algorithm_levenberg.cpp:104-141). In: the chi2 before the trial, the trial's chi2
-// (DBL_MAX after a failed factorisation), sum x (lambda x + b). Updates lambda / ni; returns rho; *accepted tells whether the state stays.
-struct gba_lm { double lambda, ni, cur; };
-inline double gba_lm_trial(gba_lm& L, double tmp, double scale, bool* accepted) {
-    scale += 1e-3;
-    const double rho = (L.cur - tmp) / scale;
-    *accepted = rho > 0 && std::isfinite(tmp);
-    if (*accepted) {
-        double alpha = 1. - pow((2 * rho - 1), 3);
-        alpha = alpha < 2. / 3. ? alpha : 2. / 3.;
-        L.lambda *= (alpha > 1. / 3. ? alpha : 1. / 3.); L.ni = 2; L.cur = tmp;
-    } else { L.lambda *= L.ni; L.ni *= 2; }
-    return rho;
 }
 
 } // namespace viorb

@@ -127,7 +127,7 @@ inline unsigned gba_blocks(size_t n, unsigned per) { return (unsigned)std::max<s
 // The launches a solve supplies to gba_run. setup: free ranks (fidx, status[GBA_ST_NFREE]) and the solve's own argument checks;
 // errors: err[] and the robust chi2 into scal[GBA_S_CHI]; linearise: Jacobians, Hll / bl, Hd / bp; reduce: Dinv, S = Hpp + lambda I,
 // the right-hand side and the Schur complement; step: point increments, the retraction of every vertex and scal[GBA_S_SCALE].
-// lambda_init: setUserLambdaInit; zero = g2o's own rule, 1e-5 * the largest diagonal entry.
+// lambda_init: setUserLambdaInit; zero = g2o's own rule, lm_lambda_init of the largest diagonal entry.
 struct GbaOps {
     int max_free;
     int (*setup)(const GbaDev&, hipStream_t);

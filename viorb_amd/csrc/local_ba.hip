@@ -11,7 +11,7 @@
 // factor), k_ba_dinv (one thread per point: (Hll + lambda I)^-1), k_ba_schur (one wavefront per key-frame pair: its 6x6 block of
 // -W D^-1 W^T gathered over the points both key frames observe, W blocks precomputed with the linearisation, no atomics), k_ba_chol_solve (dense Cholesky of the <= 240x240 reduced system by
 // one 512-thread workgroup, register tiles + v_mfma_f64_16x16x4), k_ba_backsub, k_ba_update. The LM control flow (accept / reject, lambda
-// schedule, stop rule) runs on the device (k_ba_decide / the lock-step batch's control block); the host polls a few scalars per chunk.
+// schedule, stop rule) runs on the device (k_ba_decide_body / the lock-step batch's control block); the host polls a few scalars per chunk.
 #include <hip/hip_runtime.h>
 #include <memory>
 #include <string>
@@ -21,9 +21,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include <limits>
 #include "viorb_common.h"
 #include "ba_core.h"
+#include "lm_core.h"
 
 namespace viorb {
 
@@ -55,7 +55,7 @@ struct BaDev {
 };
 
 // Device-side Levenberg control (g2o optimization_algorithm_levenberg.cpp:61-164) for the common case of an LM iteration whose first
-// trial is accepted: the host enqueues several iterations back to back, k_ba_decide takes the accept / stop decisions on the device, and
+// trial is accepted: the host enqueues several iterations back to back, k_ba_decide_body takes the accept / stop decisions on the device, and
 // after a REJECTED trial every later kernel of the chunk returns at once (ctl[HALT] = 1) so that the host finds the system, the trial
 // state and the trial's scalars untouched and continues with its own trial loop (lambda *= ni, restore, retry).
 enum { BA_CTL_LAMBDA = 0, BA_CTL_NI, BA_CTL_CHI, BA_CTL_INICHI, BA_CTL_NBAD, BA_CTL_HALT, BA_CTL_ITS, BA_CTL_IT, BA_CTL_RHO, BA_CTL_N = 32 };
@@ -654,37 +654,29 @@ __device__ __forceinline__ void k_ba_clear_body(const BaDev& D, int first, int b
         }
     }
 }
-// lambda_0 = 1e-5 * max diagonal (:166-180), after k_ba_max_diag on the first iteration of a phase
+// lambda_0 (:166-180), after k_ba_max_diag on the first iteration of a phase
 __device__ __forceinline__ void k_ba_lambda0_body(const BaDev& D) {
     if (ba_skip(D)) return;
-    if (blockIdx.x == 0 && threadIdx.x == 0) { D.ctl[BA_CTL_LAMBDA] = 1e-5 * D.scal[3]; D.ctl[BA_CTL_NI] = 2.0; }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { D.ctl[BA_CTL_LAMBDA] = lm_lambda_init(D.scal[3]); D.ctl[BA_CTL_NI] = 2.0; }
 }
-// after the trial's k_ba_*_errors: rho = (chi - chi_trial) / (sum x (lambda x + b) + 1e-3) (:129-132); accepted -> lambda update, stop
-// tests; rejected -> HALT = 1 and nothing else changes (the host takes over from ST_AFTER_TRIAL with the scalars as they are)
+// after the trial's k_ba_*_errors: accepted -> lambda update, stop tests (qmax = 1: the iteration's only trial); rejected -> HALT = 1 and
+// nothing else changes (the host takes over from ST_AFTER_TRIAL with the scalars as they are)
 __device__ __forceinline__ void k_ba_decide_body(const BaDev& D, int last_of_phase) {     // one thread
     if (ba_skip(D)) return;
     double* c = D.ctl;
-    double tempChi = __hip_atomic_load(&D.scal[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const bool ok2 = D.scal[2] > 0.5;
-    if (!ok2) tempChi = 1.7976931348623157e308;
-    const double scale = (ok2 ? D.scal[1] : 0.0) + 1e-3;
-    const double rho = (c[BA_CTL_CHI] - tempChi) / scale;
+    const double tempChi = lm_trial_chi2(ok2, __hip_atomic_load(&D.scal[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    const double rho = lm_rho(c[BA_CTL_CHI], tempChi, ok2 ? D.scal[1] : 0.0);
     c[BA_CTL_RHO] = rho;
-    if (!(rho > 0 && isfinite(tempChi))) { c[BA_CTL_HALT] = 1.0; return; }
-    const double t = 2 * rho - 1;
-    double alpha = 1. - t * t * t;
-    alpha = fmin(alpha, 2. / 3.);
-    c[BA_CTL_LAMBDA] *= fmax(1. / 3., alpha); c[BA_CTL_NI] = 2.0;
-    const double iniChi = c[BA_CTL_INICHI];
+    if (!lm_accepted(rho, tempChi)) { c[BA_CTL_HALT] = 1.0; return; }
+    lm_good_step(c[BA_CTL_LAMBDA], c[BA_CTL_NI], lm_cube_mul(2 * rho - 1));
     c[BA_CTL_CHI] = tempChi;
     c[BA_CTL_ITS] += 1.0; c[BA_CTL_IT] += 1.0;
-    // "if ((iniChi - currentChi) * 1e3 < iniChi) nBad++ else nBad = 0; if (nBad >= 3) stop" (:154-161)
-    double nBad = c[BA_CTL_NBAD];
-    if ((iniChi - tempChi) * 1e3 < iniChi) nBad += 1.0; else nBad = 0.0;
+    int nBad = (int)c[BA_CTL_NBAD];
+    const bool stop_opt = lm_iteration_stops(rho, 1, c[BA_CTL_INICHI], tempChi, nBad);
     c[BA_CTL_NBAD] = nBad;
-    if (nBad >= 3.0 || last_of_phase || ba_abort_requested(D)) c[BA_CTL_HALT] = 2.0;      // this optimize() call is over (or "!terminate()" failed)
+    if (stop_opt || last_of_phase || ba_abort_requested(D)) c[BA_CTL_HALT] = 2.0;      // this optimize() call is over (or "!terminate()" failed)
 }
-__global__ void k_ba_decide(BaDev D, int last_of_phase) { if (blockIdx.x == 0 && threadIdx.x == 0) k_ba_decide_body(D, last_of_phase); }
 
 
 // ---- by-value kernels of the single-window driver ---------------------------------------------------------------------------------
@@ -701,7 +693,6 @@ __global__ void k_ba_backsub(BaDev D, double lambda_arg) { k_ba_backsub_body(D, 
 __global__ void k_ba_update(BaDev D) { k_ba_update_body(D); }
 __global__ void k_ba_restore(BaDev D) { k_ba_restore_body(D); }
 __global__ void k_ba_gate(BaDev D, uint8_t* out, int set_level) { k_ba_gate_body(D, out, set_level); }
-__global__ void k_ba_clear(BaDev D, int first) { k_ba_clear_body(D, first); }
 __global__ void k_ba_lambda0(BaDev D) { k_ba_lambda0_body(D); }
 
 // ---- lock-step batch: one launch covers every window of a batch (blockIdx.y = window) ------------------------------------------------
@@ -736,7 +727,7 @@ __global__ void k_bab_lambda0(const BaDev* __restrict__ Dv, int nwin) {
     if (w >= nwin) return;
     const BaDev& D = Dv[w]; double* c = D.ctl;
     if (c[BA_B_DONE] != 0.0 || c[BA_B_ABORT] != 0.0 || c[BA_B_NEED_LIN] == 0.0) return;
-    if (c[BA_B_FIRST] != 0.0) { c[BA_CTL_LAMBDA] = 1e-5 * D.scal[3]; c[BA_CTL_NI] = 2.0; c[BA_CTL_NBAD] = 0.0; c[BA_B_FIRST] = 0.0; }
+    if (c[BA_B_FIRST] != 0.0) { c[BA_CTL_LAMBDA] = lm_lambda_init(D.scal[3]); c[BA_CTL_NI] = 2.0; c[BA_CTL_NBAD] = 0.0; c[BA_B_FIRST] = 0.0; }
     c[BA_B_NEED_LIN] = 0.0;
 }
 // The batch's grid is (pairs, windows) linearised and dealt so that all pairs of a window run on ONE XCD (workgroup ids go round-robin over the
@@ -759,35 +750,22 @@ __global__ void k_bab_decide(const BaDev* __restrict__ Dv, int nwin) {
     if (c[BA_B_DONE] != 0.0) return;
     if (c[BA_B_ABORT] != 0.0) { c[BA_B_GATE] = 2.0; return; }            // the host saw the stop flag between rounds (this round's trial kernels were skipped): final gate on the state as it is
     const bool abort_now = ba_abort_requested(D);                        // the flag went up during this trial: take the trial's decision, then leave both loops ("&& !terminate()")
-    double tempChi = D.scal[0];
     const bool ok2 = D.scal[2] > 0.5;
-    if (!ok2) tempChi = 1.7976931348623157e308;
-    const double scale = (ok2 ? D.scal[1] : 0.0) + 1e-3;
-    const double rho = (c[BA_CTL_CHI] - tempChi) / scale;
+    const double tempChi = lm_trial_chi2(ok2, D.scal[0]);
+    const double rho = lm_rho(c[BA_CTL_CHI], tempChi, ok2 ? D.scal[1] : 0.0);
     c[BA_CTL_RHO] = rho;
     int qmax = (int)c[BA_B_QMAX];
-    if (rho > 0 && isfinite(tempChi)) {
-        const double t = 2 * rho - 1;
-        double alpha = 1. - t * t * t;
-        alpha = fmin(alpha, 2. / 3.);
-        c[BA_CTL_LAMBDA] *= fmax(1. / 3., alpha); c[BA_CTL_NI] = 2.0; c[BA_CTL_CHI] = tempChi;
-    } else {
-        c[BA_CTL_LAMBDA] *= c[BA_CTL_NI]; c[BA_CTL_NI] *= 2.0;
-        c[BA_B_RESTORE] = 1.0;
-    }
+    if (lm_accepted(rho, tempChi)) { lm_good_step(c[BA_CTL_LAMBDA], c[BA_CTL_NI], lm_cube_mul(2 * rho - 1)); c[BA_CTL_CHI] = tempChi; }
+    else { lm_bad_step(c[BA_CTL_LAMBDA], c[BA_CTL_NI]); c[BA_B_RESTORE] = 1.0; }
     qmax++;
     if (abort_now) { c[BA_B_GATE] = 2.0; return; }                       // a rejected trial is restored by k_bab_restore before the gate
-    if (rho < 0 && qmax < 10) { c[BA_B_QMAX] = qmax; return; }           // another trial of the same iteration (no re-linearisation)
+    if (lm_retry(rho, qmax)) { c[BA_B_QMAX] = qmax; return; }            // another trial of the same iteration (no re-linearisation)
     // the iteration is over
     const int phase = (int)c[BA_B_PHASE];
     c[BA_B_ITS0 + phase] += 1.0; c[BA_B_CHI0 + phase] = c[BA_CTL_CHI];
-    bool stop_opt = (qmax == 10 || rho == 0);
-    if (!stop_opt) {
-        double nBad = c[BA_CTL_NBAD];
-        if ((c[BA_CTL_INICHI] - c[BA_CTL_CHI]) * 1e3 < c[BA_CTL_INICHI]) nBad += 1.0; else nBad = 0.0;
-        c[BA_CTL_NBAD] = nBad;
-        if (nBad >= 3.0) stop_opt = true;
-    }
+    int nBad = (int)c[BA_CTL_NBAD];
+    const bool stop_opt = lm_iteration_stops(rho, qmax, c[BA_CTL_INICHI], c[BA_CTL_CHI], nBad);
+    c[BA_CTL_NBAD] = nBad;
     c[BA_CTL_IT] += 1.0; c[BA_B_QMAX] = 0.0;
     if (stop_opt || c[BA_CTL_IT] >= c[BA_B_ITERS]) c[BA_B_GATE] = phase == 0 ? 1.0 : 2.0;
     else c[BA_B_NEED_LIN] = 1.0;
@@ -1136,7 +1114,7 @@ struct BaSolve {
     // Device-side LM control (k_ba_decide_body): iterations are enqueued FAST_CHUNK at a time with no host round trip in between (8 launches
     // each, k_ba_f_*); the host looks at the control block once per chunk and only takes the per-trial path below after a trial was
     // rejected. The caller's stop flag, which g2o polls once per iteration, is polled on the device through its page-locked mirror.
-    // VIORB_LBA_HOST_LM=1 forces the per-trial path (tests compare both).
+    // VIORB_LBA_HOST_LM=1 forces the per-trial path (tests/test_gpu_local_ba.py holds it to the oracle as it does the default path).
     enum { FAST_CHUNK = 10 };          // a whole optimize() call per round trip (5 and 10 iterations); the stop flag is polled on the device (k_ba_decide_body)
     bool fast_phase = false; int fast_enq = 0;
     int phase = 0, iterations = 5, it = 0, nBad = 0, qmax = 0, mono_kernel = 1;
@@ -1235,7 +1213,7 @@ struct BaSolve {
                 state = ST_TRIAL_ENQ;
                 break;
             case ST_AFTER_DIAG:
-                lambda = 1e-5 * h[3]; ni = 2; nBad = 0; state = ST_TRIAL_ENQ;
+                lambda = lm_lambda_init(h[3]); ni = 2; nBad = 0; state = ST_TRIAL_ENQ;
                 break;
             case ST_TRIAL_ENQ:
                 hipLaunchKernelGGL(k_ba_init_reduced, dim3((unsigned)((nl2 + TB - 1) / TB)), dim3(TB), 0, st, D, lambda);
@@ -1254,23 +1232,19 @@ struct BaSolve {
                 state = ST_AFTER_TRIAL;
                 return BA_WAIT;
             case ST_AFTER_TRIAL: {
-                double tempChi = h[0];
                 const bool ok2 = h[2] > 0.5;
-                if (!ok2) tempChi = std::numeric_limits<double>::max();
-                const double scale = (ok2 ? h[1] : 0.0) + 1e-3;
-                rho = (currentChi - tempChi) / scale;
-                if (rho > 0 && std::isfinite(tempChi)) { double alpha = 1. - std::pow((2 * rho - 1), 3); alpha = std::min(alpha, 2. / 3.); lambda *= std::max(1. / 3., alpha); ni = 2; currentChi = tempChi; }
+                const double tempChi = lm_trial_chi2(ok2, h[0]);
+                rho = lm_rho(currentChi, tempChi, ok2 ? h[1] : 0.0);
+                if (lm_accepted(rho, tempChi)) { lm_good_step(lambda, ni, lm_cube_pow(2 * rho - 1)); currentChi = tempChi; }
                 else {
-                    lambda *= ni; ni *= 2;
+                    lm_bad_step(lambda, ni);
                     hipLaunchKernelGGL(k_ba_restore, dim3(std::max(gP, 1)), dim3(TB), 0, st, D);
                 }
                 qmax++;
-                if (rho < 0 && qmax < 10 && !terminate()) { state = ST_TRIAL_ENQ; break; }
+                if (lm_retry(rho, qmax) && !terminate()) { state = ST_TRIAL_ENQ; break; }
                 its[phase]++; chi[phase] = currentChi;
-                bool stop_opt = (qmax == 10 || rho == 0);
-                if (!stop_opt) { if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0; if (nBad >= 3) stop_opt = true; }
                 it++;
-                if (stop_opt) it = iterations;                   // leaves the iteration loop through ST_ITER_BEGIN
+                if (lm_iteration_stops(rho, qmax, iniChi, currentChi, nBad)) it = iterations;    // leaves the iteration loop through ST_ITER_BEGIN
                 state = ST_ITER_BEGIN;
                 break;
             }

@@ -803,9 +803,9 @@ __global__ __launch_bounds__(64 * P * WPP, POSE_MIN_WAVES) POSE_VGPR_ATTR void k
             if (!mode) {                                                  // first evaluation of a round: computeActiveErrors + buildSystem of iteration 0
                 currentChi = chi; hb_last = cur; iniChi = chi;
                 double mx = 0; for (int i = 0; i < n; i++) mx = fmax(fabs(Hc[i * n + i]), mx);
-                lambda = 1e-5 * mx; ni = 2; nBadLM = 0; qmax = 0; mode = 1;
+                lambda = lm_lambda_init(mx); ni = 2; nBadLM = 0; qmax = 0; mode = 1;
             } else {
-                double tempChi = ok2 ? chi : 1.7976931348623157e308;
+                const double tempChi = lm_trial_chi2(ok2, chi);
                 double scale = 0;                                        // computeScale(): sum_j x_j (lambda x_j + b_j), in order
                 {
                     double xs[24], bs[24];
@@ -815,27 +815,18 @@ __global__ __launch_bounds__(64 * P * WPP, POSE_MIN_WAVES) POSE_VGPR_ATTR void k
 #pragma unroll
                     for (int j = 0; j < 24; j++) if (j < n) scale += xs[j] * (lambda * xs[j] + bs[j]);
                 }
-                scale += 1e-3;
-                const double rho = (currentChi - tempChi) / scale;
-                const bool accepted = rho > 0 && isfinite(tempChi);
-                if (accepted) {
-                    const double tr1 = 2 * rho - 1;
-                    double alpha = 1. - tr1 * tr1 * tr1;
-                    alpha = fmin(alpha, 2. / 3.);
-                    lambda *= fmax(1. / 3., alpha); ni = 2; currentChi = tempChi;
-                } else {
-                    lambda *= ni; ni *= 2;
+                const double rho = lm_rho(currentChi, tempChi, scale);
+                const bool accepted = lm_accepted(rho, tempChi);
+                if (accepted) { lm_good_step(lambda, ni, lm_cube_mul(2 * rho - 1)); currentChi = tempChi; }
+                else {
+                    lm_bad_step(lambda, ni);
                     if (lane < 20) S.est[lane / 10][lane % 10] = S.bak[lane / 10][lane % 10]; else if (lane < 26) S.bias[(lane - 20) / 3][(lane - 20) % 3] = S.bakb[(lane - 20) / 3][(lane - 20) % 3];
                 }
                 qmax++;
-                if (!(rho < 0 && qmax < 10)) {                           // the iteration is over
+                if (!lm_retry(rho, qmax)) {                              // the iteration is over
                     if (accepted) cur ^= 1;                               // the speculative buffer is the next iteration's system
                     if (lane == 0) { S.flag[1]++; S.sc[7] = currentChi; }
-                    bool brk = qmax == 10 || rho == 0;
-                    if (!brk) {
-                        if ((iniChi - currentChi) * 1e3 < iniChi) nBadLM++; else nBadLM = 0;
-                        brk = nBadLM >= 3;
-                    }
+                    const bool brk = lm_iteration_stops(rho, qmax, iniChi, currentChi, nBadLM);
                     it++;
                     if (brk || it == 10) { end_round = 1; if (lane == 0) S.lmi[10] = accepted ? 0 : 1; }
                     else { hb_last = cur; iniChi = currentChi; qmax = 0; }

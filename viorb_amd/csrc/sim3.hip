@@ -13,6 +13,7 @@
 #include <vector>
 #include "viorb_common.h"
 #include "sim3_core.h"
+#include "lm_core.h"
 
 namespace viorb {
 
@@ -300,7 +301,7 @@ __global__ __launch_bounds__(256) void k_sim3_optimize(S3OptArgs A) {
         for (int it = 0; it < max_it; it++) {
             double currentChi = evaluate(true);
             const double iniChi = currentChi;
-            if (it == 0) { double mx = 0; for (int i = 0; i < 7; i++) mx = fmax(fabs(S.H[i * 8]), mx); lambda = 1e-5 * mx; ni = 2; nBadLM = 0; }
+            if (it == 0) { double mx = 0; for (int i = 0; i < 7; i++) mx = fmax(fabs(S.H[i * 8]), mx); lambda = lm_lambda_init(mx); ni = 2; nBadLM = 0; }
             double rho = 0; int qmax = 0;
             do {
                 if (t < 8) S.bak[t] = S.est[t];
@@ -314,23 +315,18 @@ __global__ __launch_bounds__(256) void k_sim3_optimize(S3OptArgs A) {
                 __syncthreads();
                 const int ok2 = S.flag[0];
                 if (t < 8) S.ev[t] = S.est[t];
-                double tempChi = evaluate(false);
-                if (!ok2) tempChi = 1.7976931348623157e308;
-                double scale = 0; for (int j = 0; j < 7; j++) scale += S.x[j] * (lambda * S.x[j] + S.b[j]);
-                scale += 1e-3;
-                rho = (currentChi - tempChi) / scale;
-                const bool rejected = !(rho > 0 && isfinite(tempChi));
-                if (!rejected) { double alpha = 1. - pow(2 * rho - 1, 3); alpha = fmin(alpha, 2. / 3.); lambda *= fmax(1. / 3., alpha); ni = 2; currentChi = tempChi; }
-                else { lambda *= ni; ni *= 2; if (t < 8) S.est[t] = S.bak[t]; }
+                const double tempChi = lm_trial_chi2(ok2, evaluate(false));
+                rho = lm_rho(currentChi, tempChi, lm_scale<7>(S.x, S.b, lambda));
+                const bool rejected = !lm_accepted(rho, tempChi);
+                if (!rejected) { lm_good_step(lambda, ni, lm_cube_pow(2 * rho - 1)); currentChi = tempChi; }
+                else { lm_bad_step(lambda, ni); if (t < 8) S.est[t] = S.bak[t]; }
                 if (t == 0) S.flag[rejected ? 2 : 1]++;
                 __syncthreads();
                 qmax++;
-            } while (rho < 0 && qmax < 10);
+            } while (lm_retry(rho, qmax));
             its++;
             chi_round[round] = currentChi;
-            if (qmax == 10 || rho == 0) break;
-            if ((iniChi - currentChi) * 1e3 < iniChi) nBadLM++; else nBadLM = 0;
-            if (nBadLM >= 3) break;
+            if (lm_iteration_stops(rho, qmax, iniChi, currentChi, nBadLM)) break;
         }
         its_done[round] = its;
         // e->chi2() reads the error of the last computeActiveErrors, the last trial's state: stale after a rejected last trial
