@@ -509,7 +509,8 @@ int viorb_pose_opt_se3(const float pose12[12], const float intr5[5], const doubl
  * stop: the reference's pbStopFlag (may be NULL). g2o polls it once per iteration and once per LM trial; here the waiting host thread
  * mirrors it into a page-locked word that the device-side Levenberg control reads after every trial, so a raised flag ends the solve
  * after the trial in flight (a rejected one is restored first), as "&& !terminate()" does in the reference. Outputs: kfs_out [n_local][22],
- * points_out [np][3], erase [ne], info = chi2 after optimize(5), final chi2, iterations of both runs, 0, 0.
+ * points_out [np][3], erase [ne], info = chi2 after optimize(5), final chi2, iterations of both runs, the number of
+ * Levenberg trials taken over both runs, and how many of them were rejected (rho <= 0 or a failed factorisation; the estimate was restored).
  * Host buffers in and out (the caller is the LocalMapping thread); all arithmetic runs on the GPU in FP64, on the device
  * chosen with viorb_local_ba_set_device (default: the calling thread's current HIP device). Re-entrant: concurrent callers get their own stream and device arena. */
 /* Device of all window solves of this process: >= 0 fixes it, < 0 (default) = the calling thread's current HIP device. */

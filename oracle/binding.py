@@ -439,6 +439,19 @@ def stereo_match(ex_left, ex_right, kl, dl, kr, dr, bf, fx):
     return u[:n], d[:n], sad[:n]
 
 
+BA_TRIAL_COLUMNS = ("phase", "iteration", "qmax", "solved", "rho", "temp_chi", "lambda_after", "chi_before")
+
+
+def _ba_trials(L):
+    """The Levenberg trials of this thread's last window solve, one row per trial in the order taken: [n, 8] float64, BA_TRIAL_COLUMNS.
+    A trial was accepted when rho > 0 and temp_chi is finite (temp_chi = DBL_MAX after a failed factorisation)."""
+    L.ora_local_ba_trials.argtypes = [C.c_void_p, C.c_int]
+    n = L.ora_local_ba_trials(None, 0)
+    rows = np.zeros((max(n, 1), 8))
+    L.ora_local_ba_trials(_p(rows), n)
+    return rows[:n]
+
+
 def local_ba(kfs, n_local, prev_kf, preint, points, edge_idx, edge_obs, gw, cam, stop=None):
     """Optimizer::LocalBundleAdjustmentNavState on the oracle. kfs [NK,22] local first; preint [W,142]; points [NP,3];
     edge_idx [NE,2] int32 (point, kf) grouped by point; edge_obs [NE,3] = u v invSigma2."""
@@ -451,7 +464,8 @@ def local_ba(kfs, n_local, prev_kf, preint, points, edge_idx, edge_obs, gw, cam,
     st = np.ascontiguousarray(stop, np.int32) if stop is not None else None
     L.ora_local_ba(_p(kfs), len(kfs), n_local, prev_kf, _p(preint), _p(points), len(points), _p(ei), _p(eo), len(ei), _p(_f64(gw, 3)),
                    _p(_f64(cam, 16)), _p(st) if st is not None else None, _p(ko), _p(po), _p(er), _p(info))
-    return dict(kfs=ko, points=po, erase=er[:len(ei)], chi2_first=info[0], chi2_final=info[1], its_first=int(info[2]), its_second=int(info[3]))
+    return dict(kfs=ko, points=po, erase=er[:len(ei)], chi2_first=info[0], chi2_final=info[1], its_first=int(info[2]), its_second=int(info[3]),
+                n_trials=int(info[4]), n_rejected=int(info[5]), trials=_ba_trials(L))
 
 
 def bow_transform(voc, desc, levelsup=4):
@@ -519,7 +533,8 @@ def local_ba_se3(kfs, n_local, points, edge_idx, edge_obs, intr5, stop=None):
     st = np.ascontiguousarray(stop, np.int32) if stop is not None else None
     L.ora_local_ba_se3(_p(kfs), len(kfs), n_local, _p(points), len(points), _p(ei), _p(eo), len(ei), _p(_f64(intr5, 5)), _p(st) if st is not None else None,
                        _p(ko), _p(po), _p(er), _p(info))
-    return dict(kfs=ko, points=po, erase=er[:len(ei)], chi2_first=info[0], chi2_final=info[1], its_first=int(info[2]), its_second=int(info[3]))
+    return dict(kfs=ko, points=po, erase=er[:len(ei)], chi2_first=info[0], chi2_final=info[1], its_first=int(info[2]), its_second=int(info[3]),
+                n_trials=int(info[4]), n_rejected=int(info[5]), trials=_ba_trials(L))
 
 
 def undistort_points(xy, K4, dist5):

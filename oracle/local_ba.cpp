@@ -145,7 +145,7 @@ BaResult local_ba_navstate(const BaProblem& P, const volatile int* stop) {
         for (int p = 0; p < NP; p++) { const V3 v = Dinv[p] * V3{cl[3 * p], cl[3 * p + 1], cl[3 * p + 2]}; xl[3 * p] = v.x; xl[3 * p + 1] = v.y; xl[3 * p + 2] = v.z; }
         return true;
     };
-    double lambda = 0, ni = 2;
+    double lambda = 0, ni = 2; int phase_no = 0;
     auto optimize = [&](int iterations, int& its_done) -> double {
         double currentChi = 0; int nBad = 0;
         // points without any active edge and key frames are all "active"; g2o only indexes vertices with active edges,
@@ -170,8 +170,10 @@ BaResult local_ba_navstate(const BaProblem& P, const volatile int* stop) {
                 if (ok2) { for (int j = 0; j < np; j++) scale += xp[j] * (lambda * xp[j] + bp[j]); for (size_t j = 0; j < xl.size(); j++) scale += xl[j] * (lambda * xl[j] + bl[j]); }
                 scale += 1e-3;
                 rho = (currentChi - tempChi) / scale;
+                const double chi_before = currentChi;
                 if (rho > 0 && std::isfinite(tempChi)) { double alpha = 1. - std::pow((2 * rho - 1), 3); alpha = std::min(alpha, 2. / 3.); lambda *= std::max(1. / 3., alpha); ni = 2; currentChi = tempChi; }
                 else { lambda *= ni; ni *= 2; kf = bk; pt = bp_; }
+                R.trials.push_back(BaTrial{phase_no, it, qmax, ok2 ? 1 : 0, rho, tempChi, lambda, chi_before});
                 qmax++;
             } while (rho < 0 && qmax < 10 && !terminate());
             its_done++; R.trace.push_back(currentChi);
@@ -187,7 +189,7 @@ BaResult local_ba_navstate(const BaProblem& P, const volatile int* stop) {
             const V3 Pc = pc_of(kf[P.edges[k].kf], P.cam, pt[P.edges[k].point]);
             if (chi_e(k) > 5.991 || !(Pc.z > 0.0)) level[k] = 1;
         }
-        mono_kernel = false;
+        mono_kernel = false; phase_no = 1;
         // a point left without active edges has Hll = 0: g2o drops it from the active set; give it an identity block
         R.chi2_final = optimize(10, R.its_second);
     }

@@ -18,6 +18,9 @@ struct BaProblem {
     std::vector<BaEdge> edges;          // grouped by point, in the reference's construction order
     V3 gw; Camera cam;
 };
+// one row per Levenberg trial, in the order taken: phase (0: optimize(5), 1: optimize(10)), iteration within the phase, qmax before the
+// trial, whether the linear solve succeeded, rho, the trial's chi2 (tempChi), lambda after the decision, currentChi before the trial
+struct BaTrial { int phase, iteration, qmax, solved; double rho, temp_chi, lambda_after, chi_before; };
 struct BaResult {
     std::vector<NavState> kfs;          // optimised local key frames (dBias updated)
     std::vector<V3> points;
@@ -25,6 +28,7 @@ struct BaResult {
     double chi2_after_first = 0, chi2_final = 0;
     int its_first = 0, its_second = 0;
     std::vector<double> trace;
+    std::vector<BaTrial> trials;
 };
 // stop: checked where g2o polls terminate() (before each optimize iteration and each LM trial); may be null.
 BaResult local_ba_navstate(const BaProblem& P, const volatile int* stop);

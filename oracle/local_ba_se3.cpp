@@ -130,7 +130,7 @@ BaSe3Result local_ba_se3(const BaSe3Problem& P, const volatile int* stop) {
         for (int p = 0; p < NP; p++) { const V3 v = Dinv[p] * V3{cl[3 * p], cl[3 * p + 1], cl[3 * p + 2]}; xl[3 * p] = v.x; xl[3 * p + 1] = v.y; xl[3 * p + 2] = v.z; }
         return true;
     };
-    double lambda = 0, ni = 2;
+    double lambda = 0, ni = 2; int phase_no = 0;
     auto optimize = [&](int iterations, int& its_done) -> double {
         double currentChi = 0; int nBad = 0;
         for (int it = 0; it < iterations && !terminate(); it++) {
@@ -153,8 +153,10 @@ BaSe3Result local_ba_se3(const BaSe3Problem& P, const volatile int* stop) {
                 if (ok2) { for (int j = 0; j < np; j++) scale += xp[j] * (lambda * xp[j] + bp[j]); for (size_t j = 0; j < xl.size(); j++) scale += xl[j] * (lambda * xl[j] + bl[j]); }
                 scale += 1e-3;
                 rho = (currentChi - tempChi) / scale;
+                const double chi_before = currentChi;
                 if (rho > 0 && std::isfinite(tempChi)) { double alpha = 1. - std::pow((2 * rho - 1), 3); alpha = std::min(alpha, 2. / 3.); lambda *= std::max(1. / 3., alpha); ni = 2; currentChi = tempChi; }
                 else { lambda *= ni; ni *= 2; kf = bk; pt = bpt; }
+                R.trials.push_back(BaTrial{phase_no, it, qmax, ok2 ? 1 : 0, rho, tempChi, lambda, chi_before});
                 qmax++;
             } while (rho < 0 && qmax < 10 && !terminate());
             its_done++;
@@ -171,7 +173,7 @@ BaSe3Result local_ba_se3(const BaSe3Problem& P, const volatile int* stop) {
     R.chi2_after_first = optimize(5, R.its_first);
     if (!terminate()) {
         for (int k = 0; k < NE; k++) if (bad_edge(k)) level[k] = 1;       // :4170-4200; kernels dropped on every edge
-        kernels = false;
+        kernels = false; phase_no = 1;
         R.chi2_final = optimize(10, R.its_second);
     }
     for (int k = 0; k < NE; k++) R.erase[k] = bad_edge(k) ? 1 : 0;         // :4207-4235 (stale _error on excluded edges, fresh depth)

@@ -7,6 +7,7 @@
 // PARITY UNPINNED (no reference fixture); pinned by tests/test_oracle_local_ba.py (dense scipy re-optimisation).
 #pragma once
 #include "vio.h"
+#include "local_ba.h"                                               // BaTrial
 namespace ora {
 struct Se3Pose { Quat r; V3 t; };                                  // g2o::SE3Quat (Tcw)
 struct BaSe3Edge { int point, kf; double u, v, ur, inv_sigma2; };   // ur < 0: monocular observation
@@ -18,6 +19,7 @@ struct BaSe3Problem {
 struct BaSe3Result {
     std::vector<Se3Pose> kfs; std::vector<V3> points; std::vector<uint8_t> erase;
     double chi2_after_first = 0, chi2_final = 0; int its_first = 0, its_second = 0;
+    std::vector<BaTrial> trials;
 };
 BaSe3Result local_ba_se3(const BaSe3Problem& P, const volatile int* stop);
 }

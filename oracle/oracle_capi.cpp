@@ -371,7 +371,22 @@ int ora_stereo_match(void* hl, void* hr, const KeyPoint* kl, const uint8_t* dl, 
 #include "local_ba.h"
 extern "C" {
 // Local BA on flat arrays: kfs[NK][22] (local first), preint[W][142], points[NP][3], edge_idx[NE][2] = (point, kf),
-// edge_obs[NE][3] = u v invSigma2 (edges grouped by point). info6 = chi2_first chi2_final its_first its_second 0 0.
+// edge_obs[NE][3] = u v invSigma2 (edges grouped by point). info6 = chi2_first chi2_final its_first its_second trials rejected_trials.
+// The trial rows of the calling thread's last window solve (either kind) are read back with ora_local_ba_trials.
+static thread_local std::vector<BaTrial> g_ba_trials;
+static void ba_trial_counts(const std::vector<BaTrial>& t, double* info) {
+    int rej = 0; for (const BaTrial& r : t) if (!(r.rho > 0 && std::isfinite(r.temp_chi))) rej++;
+    info[4] = (double)t.size(); info[5] = rej;
+}
+// rows[n][8] = phase iteration qmax solved rho tempChi lambda_after chi_before; returns the number of trials (rows may be null to ask for it)
+int ora_local_ba_trials(double* rows, int cap) {
+    const int n = (int)g_ba_trials.size();
+    for (int i = 0; rows && i < n && i < cap; i++) {
+        const BaTrial& r = g_ba_trials[i]; double* o = rows + 8 * i;
+        o[0] = r.phase; o[1] = r.iteration; o[2] = r.qmax; o[3] = r.solved; o[4] = r.rho; o[5] = r.temp_chi; o[6] = r.lambda_after; o[7] = r.chi_before;
+    }
+    return n;
+}
 void ora_local_ba(const double* kfs, int nk, int n_local, int prev_kf, const double* preint, const double* points, int np_,
                   const int* edge_idx, const double* edge_obs, int ne, const double* gw, const double* cam16, const int* stop,
                   double* kfs_out, double* points_out, uint8_t* erase, double* info6) {
@@ -386,7 +401,8 @@ void ora_local_ba(const double* kfs, int nk, int n_local, int prev_kf, const dou
     for (int i = 0; i < n_local; i++) ns_out(kfs_out + 22 * i, R.kfs[i]);
     for (int i = 0; i < np_; i++) put3(points_out + 3 * i, R.points[i]);
     for (int k = 0; k < ne; k++) erase[k] = R.erase[k];
-    info6[0] = R.chi2_after_first; info6[1] = R.chi2_final; info6[2] = R.its_first; info6[3] = R.its_second; info6[4] = 0; info6[5] = 0;
+    info6[0] = R.chi2_after_first; info6[1] = R.chi2_final; info6[2] = R.its_first; info6[3] = R.its_second;
+    g_ba_trials = R.trials; ba_trial_counts(R.trials, info6);
 }
 } // extern "C"
 
@@ -466,6 +482,7 @@ int ora_local_ba_se3(const double* kfs, int nk, int n_local, const double* point
     for (int i = 0; i < np; i++) { points_out[3 * i] = R.points[i].x; points_out[3 * i + 1] = R.points[i].y; points_out[3 * i + 2] = R.points[i].z; }
     for (int k = 0; k < ne; k++) erase[k] = R.erase[k];
     info[0] = R.chi2_after_first; info[1] = R.chi2_final; info[2] = R.its_first; info[3] = R.its_second;
+    g_ba_trials = R.trials; ba_trial_counts(R.trials, info);
     return 0;
 }
 } // extern "C"

@@ -33,6 +33,7 @@ def test_local_ba_matches_oracle(oracle, seed, W, npts, extra):
     ref = oracle.local_ba(*_args(p, pre))
     got = LocalBundleAdjustmentNavState(*_args(p, pre))
     assert (got["its_first"], got["its_second"]) == (ref["its_first"], ref["its_second"])
+    assert (got["n_trials"], got["n_rejected"]) == (ref["n_trials"], ref["n_rejected"])  # info[4], info[5]: Levenberg trials taken / rejected
     assert abs(got["chi2_first"] - ref["chi2_first"]) <= 1e-5 * ref["chi2_first"]        # north_star tolerance
     assert abs(got["chi2_final"] - ref["chi2_final"]) <= 1e-5 * ref["chi2_final"]
     assert np.array_equal(got["erase"], ref["erase"])
@@ -195,6 +196,7 @@ def test_local_ba_se3_matches_oracle(oracle, seed, W, nfix, npts, stereo):
     ref = oracle.local_ba_se3(*a)
     got = LocalBundleAdjustment(*a)
     assert (got["its_first"], got["its_second"]) == (ref["its_first"], ref["its_second"])
+    assert (got["n_trials"], got["n_rejected"]) == (ref["n_trials"], ref["n_rejected"])
     assert abs(got["chi2_first"] - ref["chi2_first"]) <= 1e-5 * ref["chi2_first"]
     assert abs(got["chi2_final"] - ref["chi2_final"]) <= 1e-5 * ref["chi2_final"]
     assert np.array_equal(got["erase"], ref["erase"])

@@ -58,7 +58,9 @@ struct BaDev {
 // trial is accepted: the host enqueues several iterations back to back, k_ba_decide_body takes the accept / stop decisions on the device, and
 // after a REJECTED trial every later kernel of the chunk returns at once (ctl[HALT] = 1) so that the host finds the system, the trial
 // state and the trial's scalars untouched and continues with its own trial loop (lambda *= ni, restore, retry).
-enum { BA_CTL_LAMBDA = 0, BA_CTL_NI, BA_CTL_CHI, BA_CTL_INICHI, BA_CTL_NBAD, BA_CTL_HALT, BA_CTL_ITS, BA_CTL_IT, BA_CTL_RHO, BA_CTL_N = 32 };
+enum { BA_CTL_LAMBDA = 0, BA_CTL_NI, BA_CTL_CHI, BA_CTL_INICHI, BA_CTL_NBAD, BA_CTL_HALT, BA_CTL_ITS, BA_CTL_IT, BA_CTL_RHO,
+       BA_CTL_TRIALS, BA_CTL_REJECTS,     // Levenberg trials taken / rejected (info[4], info[5]): the lock-step batch counts here (k_bab_decide)
+       BA_CTL_N = 32 };
 __device__ __forceinline__ bool ba_skip(const BaDev& D) { return D.use_ctl && D.ctl[BA_CTL_HALT] != 0.0; }
 // g2o polls terminate() once per iteration and once per LM trial (optimization_algorithm_levenberg.cpp / sparse_optimizer.cpp:354-432); the
 // device-side LM control does the same through a system-scope load of the mirrored flag, so an abort costs at most the trial in flight
@@ -755,8 +757,9 @@ __global__ void k_bab_decide(const BaDev* __restrict__ Dv, int nwin) {
     const double rho = lm_rho(c[BA_CTL_CHI], tempChi, ok2 ? D.scal[1] : 0.0);
     c[BA_CTL_RHO] = rho;
     int qmax = (int)c[BA_B_QMAX];
+    c[BA_CTL_TRIALS] += 1.0;
     if (lm_accepted(rho, tempChi)) { lm_good_step(c[BA_CTL_LAMBDA], c[BA_CTL_NI], lm_cube_mul(2 * rho - 1)); c[BA_CTL_CHI] = tempChi; }
-    else { lm_bad_step(c[BA_CTL_LAMBDA], c[BA_CTL_NI]); c[BA_B_RESTORE] = 1.0; }
+    else { lm_bad_step(c[BA_CTL_LAMBDA], c[BA_CTL_NI]); c[BA_B_RESTORE] = 1.0; c[BA_CTL_REJECTS] += 1.0; }
     qmax++;
     if (abort_now) { c[BA_B_GATE] = 2.0; return; }                       // a rejected trial is restored by k_bab_restore before the gate
     if (lm_retry(rho, qmax)) { c[BA_B_QMAX] = qmax; return; }            // another trial of the same iteration (no re-linearisation)
@@ -1119,6 +1122,7 @@ struct BaSolve {
     bool fast_phase = false; int fast_enq = 0;
     int phase = 0, iterations = 5, it = 0, nBad = 0, qmax = 0, mono_kernel = 1;
     int its[2] = {0, 0}; double chi[2] = {0, 0};
+    int ntrials[2] = {0, 0}, nrejects = 0;     // Levenberg trials per phase, rejected ones (info[4], info[5])
     double lambda = 0, ni = 2, currentChi = 0, iniChi = 0, rho = 0;
     bool terminate() const { return stop && *stop; }
     int advance() {
@@ -1181,6 +1185,7 @@ struct BaSolve {
             case ST_FAST_WAIT: {
                 const double* c = h + 8;
                 its[phase] = (int)c[BA_CTL_ITS]; chi[phase] = c[BA_CTL_CHI]; it = (int)c[BA_CTL_IT];
+                ntrials[phase] = its[phase];       // the device chunk: every iteration it finished was one accepted trial; the rejected one is counted below
                 currentChi = c[BA_CTL_CHI]; iniChi = c[BA_CTL_INICHI]; lambda = c[BA_CTL_LAMBDA]; ni = c[BA_CTL_NI]; nBad = (int)c[BA_CTL_NBAD];
                 const int halt = (int)c[BA_CTL_HALT];
                 if (halt == 1) { qmax = 0; rho = 0; fast_phase = false; state = ST_AFTER_TRIAL; break; }      // a rejected trial: h[0..2] hold its scalars
@@ -1235,9 +1240,10 @@ struct BaSolve {
                 const bool ok2 = h[2] > 0.5;
                 const double tempChi = lm_trial_chi2(ok2, h[0]);
                 rho = lm_rho(currentChi, tempChi, ok2 ? h[1] : 0.0);
+                ntrials[phase]++;
                 if (lm_accepted(rho, tempChi)) { lm_good_step(lambda, ni, lm_cube_pow(2 * rho - 1)); currentChi = tempChi; }
                 else {
-                    lm_bad_step(lambda, ni);
+                    lm_bad_step(lambda, ni); nrejects++;
                     hipLaunchKernelGGL(k_ba_restore, dim3(std::max(gP, 1)), dim3(TB), 0, st, D);
                 }
                 qmax++;
@@ -1263,7 +1269,7 @@ struct BaSolve {
                 state = ST_AFTER_FINAL;
                 return BA_WAIT;
             case ST_AFTER_FINAL:
-                info[0] = chi[0]; info[1] = chi[1]; info[2] = its[0]; info[3] = its[1];
+                info[0] = chi[0]; info[1] = chi[1]; info[2] = its[0]; info[3] = its[1]; info[4] = ntrials[0] + ntrials[1]; info[5] = nrejects;
                 state = ST_DONE;
                 return BA_DONE;
             case ST_DONE:
@@ -1638,6 +1644,7 @@ static int ba_run_lockstep(Win* w, int n, int max_in_flight, Prepare prepare) {
                 const double* c = reinterpret_cast<const double*>(hb + offs[4 * a + 3]);
                 double* info = B.info;
                 info[0] = c[BA_B_CHI0]; info[1] = c[BA_B_CHI1]; info[2] = c[BA_B_ITS0]; info[3] = c[BA_B_ITS1];
+                info[4] = c[BA_CTL_TRIALS]; info[5] = c[BA_CTL_REJECTS];
             }
         }
         return VIORB_OK;

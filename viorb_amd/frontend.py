@@ -155,12 +155,14 @@ def LocalBundleAdjustmentNavState(kfs, n_local, prev_kf, preint, points, edge_id
     check(lib().viorb_local_ba_navstate(ptr(kfs), len(kfs), n_local, prev_kf, ptr(preint), ptr(points), len(points), ptr(ei), ptr(eo), len(ei),
                                         ptr(np.ascontiguousarray(gw, np.float64)), ptr(np.ascontiguousarray(cam, np.float64)),
                                         ptr(stop) if stop is not None else None, ptr(ko), ptr(po), ptr(er), ptr(info)))
-    return dict(kfs=ko, points=po, erase=er[:len(ei)], chi2_first=info[0], chi2_final=info[1], its_first=int(info[2]), its_second=int(info[3]))
+    return dict(kfs=ko, points=po, erase=er[:len(ei)], chi2_first=info[0], chi2_final=info[1], its_first=int(info[2]), its_second=int(info[3]),
+                n_trials=int(info[4]), n_rejected=int(info[5]))
 
 
 def LocalBundleAdjustmentNavStateBatch(problems, max_in_flight=128):
     """Several LocalBundleAdjustmentNavState windows solved concurrently (viorb_local_ba_navstate_batch): `problems` is a list of dicts
-    with the keyword arguments of LocalBundleAdjustmentNavState (kfs, n_local, prev_kf, preint, points, edge_idx, edge_obs, gw, cam);
+    with the keyword arguments of LocalBundleAdjustmentNavState (kfs, n_local, prev_kf, preint, points, edge_idx, edge_obs, gw, cam) and
+    optionally `stop` (an int32 array of one element, the window's pbStopFlag);
     returns the list of result dicts, each identical to what the single call returns."""
     n = len(problems)
     W = (capi.LbaWindow * max(n, 1))()
@@ -172,15 +174,16 @@ def LocalBundleAdjustmentNavStateBatch(problems, max_in_flight=128):
         gw = np.ascontiguousarray(q["gw"], np.float64); cam = np.ascontiguousarray(q["cam"], np.float64)
         ko, po = np.zeros((q["n_local"], 22)), np.zeros_like(points)
         er, info = np.zeros(max(len(ei), 1), np.uint8), np.zeros(6)
-        keep.append((kfs, preint, points, ei, eo, gw, cam, ko, po, er, info))
+        stop = np.ascontiguousarray(q["stop"], np.int32) if q.get("stop") is not None else None
+        keep.append((kfs, preint, points, ei, eo, gw, cam, ko, po, er, info, stop))
         w = W[i]
         w.kfs = kfs.ctypes.data; w.nk = len(kfs); w.n_local = int(q["n_local"]); w.prev_kf = int(q["prev_kf"]); w.preint = preint.ctypes.data
         w.points = points.ctypes.data; w.np = len(points); w.edge_idx = ei.ctypes.data; w.edge_obs = eo.ctypes.data; w.ne = len(ei)
-        w.gw = gw.ctypes.data; w.cam = cam.ctypes.data; w.stop = None
+        w.gw = gw.ctypes.data; w.cam = cam.ctypes.data; w.stop = stop.ctypes.data if stop is not None else None
         w.kfs_out = ko.ctypes.data; w.points_out = po.ctypes.data; w.erase = er.ctypes.data; w.info = info.ctypes.data; w.status = 0
     check(lib().viorb_local_ba_navstate_batch(C.cast(W, C.c_void_p), n, int(max_in_flight)))
     return [dict(kfs=k[7], points=k[8], erase=k[9][:len(k[3])], chi2_first=k[10][0], chi2_final=k[10][1], its_first=int(k[10][2]),
-                 its_second=int(k[10][3])) for k in keep]
+                 its_second=int(k[10][3]), n_trials=int(k[10][4]), n_rejected=int(k[10][5])) for k in keep]
 
 
 def LocalBundleAdjustment(kfs, n_local, points, edge_idx, edge_obs, intr5, stop=None):
@@ -192,12 +195,13 @@ def LocalBundleAdjustment(kfs, n_local, points, edge_idx, edge_obs, intr5, stop=
     er, info = np.zeros(max(len(ei), 1), np.uint8), np.zeros(6)
     check(lib().viorb_local_ba_se3(ptr(kfs), len(kfs), n_local, ptr(points), len(points), ptr(ei), ptr(eo), len(ei), ptr(np.ascontiguousarray(intr5, np.float64)),
                                    ptr(stop) if stop is not None else None, ptr(ko), ptr(po), ptr(er), ptr(info)))
-    return dict(kfs=ko, points=po, erase=er[:len(ei)], chi2_first=info[0], chi2_final=info[1], its_first=int(info[2]), its_second=int(info[3]))
+    return dict(kfs=ko, points=po, erase=er[:len(ei)], chi2_first=info[0], chi2_final=info[1], its_first=int(info[2]), its_second=int(info[3]),
+                n_trials=int(info[4]), n_rejected=int(info[5]))
 
 
 def LocalBundleAdjustmentBatch(problems, max_in_flight=128):
     """Several vision-only LocalBundleAdjustment windows kept in flight together (viorb_local_ba_se3_batch): `problems` is a list of
-    dicts with the keyword arguments of LocalBundleAdjustment (kfs, n_local, points, edge_idx, edge_obs, intr5)."""
+    dicts with the keyword arguments of LocalBundleAdjustment (kfs, n_local, points, edge_idx, edge_obs, intr5) and optionally `stop`."""
     n = len(problems)
     W = (capi.LbaSe3Window * max(n, 1))()
     keep = []
@@ -207,14 +211,15 @@ def LocalBundleAdjustmentBatch(problems, max_in_flight=128):
         intr = np.ascontiguousarray(q["intr5"], np.float64)
         ko, po = np.zeros((q["n_local"], 7)), np.zeros_like(points)
         er, info = np.zeros(max(len(ei), 1), np.uint8), np.zeros(6)
-        keep.append((kfs, points, ei, eo, intr, ko, po, er, info))
+        stop = np.ascontiguousarray(q["stop"], np.int32) if q.get("stop") is not None else None
+        keep.append((kfs, points, ei, eo, intr, ko, po, er, info, stop))
         w = W[i]
         w.kfs = kfs.ctypes.data; w.nk = len(kfs); w.n_local = int(q["n_local"]); w.points = points.ctypes.data; w.np = len(points)
-        w.edge_idx = ei.ctypes.data; w.edge_obs = eo.ctypes.data; w.ne = len(ei); w.intr5 = intr.ctypes.data; w.stop = None
+        w.edge_idx = ei.ctypes.data; w.edge_obs = eo.ctypes.data; w.ne = len(ei); w.intr5 = intr.ctypes.data; w.stop = stop.ctypes.data if stop is not None else None
         w.kfs_out = ko.ctypes.data; w.points_out = po.ctypes.data; w.erase = er.ctypes.data; w.info = info.ctypes.data; w.status = 0
     check(lib().viorb_local_ba_se3_batch(C.cast(W, C.c_void_p), n, int(max_in_flight)))
     return [dict(kfs=k[5], points=k[6], erase=k[7][:len(k[2])], chi2_first=k[8][0], chi2_final=k[8][1], its_first=int(k[8][2]),
-                 its_second=int(k[8][3])) for k in keep]
+                 its_second=int(k[8][3]), n_trials=int(k[8][4]), n_rejected=int(k[8][5])) for k in keep]
 
 
 class ORBVocabulary:
