@@ -657,9 +657,9 @@ int viorb_fuse(const viorb_keypoint* kps, const uint8_t* desc, const float* urig
 /* ---- Map-point creation (reference src/LocalMapping.cc:1227-1483, src/MapPoint.cc:249-314, :337-378, src/KeyFrame.cc:952-968) -----
  * The piece of LocalMapping::Run between SearchForTriangulation and Fuse: triangulate and vet the matched pairs, and give every new
  * (or changed) map point its representative descriptor, normal and depth range, in the pts_f[p][8] / pts_desc[p][32] layout that
- * viorb_fuse, viorb_frontend_fuse_device and the local-point search read. The map graph itself (new MapPoint, AddObservation,
- * covisibility) stays with the caller, who passes flat snapshots (the decisions of the two culling routines are the library's:
- * viorb_culling.h). One camera per call: every key frame of a map shares fx fy cx cy mb mbf and the scale tables, as the reference's
+ * viorb_fuse, viorb_frontend_fuse_device and the local-point search read. The map graph itself (new MapPoint, AddObservation)
+ * stays with the caller, who passes flat snapshots (the decisions of the two culling routines are the library's: viorb_culling.h;
+ * the covisibility graph that follows the new observations: viorb_covisibility.h). One camera per call: every key frame of a map shares fx fy cx cy mb mbf and the scale tables, as the reference's
  * single Tracking object gives them. */
 typedef struct viorb_mapping_camera {
     float   fx, fy, cx, cy;               /* KeyFrame::fx.. (invfx = 1.0f / fx as Frame computes it) */
@@ -950,6 +950,10 @@ int viorb_debug_gba_last_trials(uint8_t* accepted, int cap, int* n);
 /* The local map of the tracking thread (Tracking::UpdateLocalMap: UpdateLocalKeyFrames, ordered and exact, and UpdateLocalPoints) and
  * the packing of its points for viorb_frontend_search_local_points_device, in a header of their own. */
 #include "viorb_local_map.h"
+
+/* The covisibility graph those stages consume (KeyFrame::UpdateConnections with AddConnection and UpdateBestCovisibles, ordered and
+ * exact, and the LoopConnections of LoopClosing::CorrectLoop), in a header of its own. */
+#include "viorb_covisibility.h"
 
 /* Relocalisation after the PnP hypothesis (Tracking::Relocalization): the key-frame projection search
  * ORBmatcher::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) and the solve / search / solve cascade, in a header of

@@ -11,7 +11,8 @@
  * src/LoopClosing.cc:593): a pose graph over every key frame of the map as a Sim3 (VertexSim3Expmap, 7), one EdgeSim3 per edge of the
  * essential graph (error = log(C * S_i * S_j^-1), information = identity, no robust kernel, numeric Jacobians), ONE
  * optimize(cfg->iterations) of g2o's Levenberg with setUserLambdaInit(1e-16), then the write-back of key-frame poses and map points.
- * The choice of edges, CorrectLoop's propagation and the covisibility update stay with the caller; this is the solve.
+ * The choice of edges and CorrectLoop's propagation stay with the caller (the covisibility update and LoopConnections are
+ * viorb_update_connections, viorb_covisibility.h); this is the solve.
  * A Sim3 is 8 doubles r(x y z w) t s, as viorb_sim3_opt_inputs::S12.
  *   Scw [nk][8]        vScw, the vertex estimate: the CorrectedSim3 entry where there is one, else (Rcw, tcw, 1)
  *   Smeas [nk][8]      the NonCorrectedSim3 entry where there is one, else the same row as Scw

@@ -6,8 +6,8 @@
  * The call works on a snapshot of the map around the current frame, for `batch` independent streams, and returns mvpLocalKeyFrames,
  * mpReferenceKF, mvpLocalMapPoints and the frame's mvpMapPoints with the bad points cleared. Every output equals the reference's loops
  * exactly: the routine is integer throughout. Pointer order enters in one place only, the walk of std::map<KeyFrame*, int>
- * keyframeCounter, and is passed in as the permutation kf_by_key. KeyFrame::UpdateConnections stays with the caller:
- * GetBestCovisibilityKeyFrames(10) is the input table covis10. The index semantics of the neighbour loop are followed: what a
+ * keyframeCounter, and is passed in as the permutation kf_by_key. GetBestCovisibilityKeyFrames(10) is the input table covis10:
+ * the first ten of ord_kf_out of viorb_update_connections (viorb_covisibility.h), which is KeyFrame::UpdateConnections. The index semantics of the neighbour loop are followed: what a
  * reallocation of mvpLocalKeyFrames under its live iterators would do is not reproduced.
  *
  * Every entry checks its arguments before any GPU call. VIORB_ERR_INVALID_ARG: a null struct or array, batch outside 1..65535, a

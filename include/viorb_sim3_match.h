@@ -10,7 +10,7 @@
  * is a viorb_mapping_camera (fx fy cx cy, nlevels, scale_factors; the logarithm of scale_factors[1] is taken on the host as viorb_fuse
  * takes it) plus bounds4 = mnMinX mnMaxX mnMinY mnMaxY; the grid is the CSR cell_start[64*48+1] / cell_idx[cap] in storage order
  * ix*48 + iy. What stays with the caller: the map writes (Replace, AddObservation, AddMapPoint; viorb_amd/shim), the mnLoopPointForKF
- * de-duplication that builds mvpLoopMapPoints, the covisibility graph.
+ * de-duplication that builds mvpLoopMapPoints (the covisibility graph that follows them is viorb_update_connections, viorb_covisibility.h).
  *
  * Every entry checks its arguments before any GPU call. VIORB_ERR_INVALID_ARG: a null array, cap < 1 (pcap < 1), batch outside 1..65535,
  * th <= 0, nlevels outside 1..16, empty bounds, a workspace that is too small or not 256-byte aligned. VIORB_ERR_CAPACITY: cap above

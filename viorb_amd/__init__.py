@@ -18,5 +18,6 @@ from .relocalization import RelocBatch, search_by_projection_reloc  # noqa: F401
 from .search_init import SearchInitBatch, search_for_initialization, scene_median_depth, scene_median_depth_batch  # noqa: F401
 from .culling import CullBatch, key_frame_culling, map_point_culling, map_point_culling_batch  # noqa: F401
 from .local_map import LocalMapBatch, update_local_map  # noqa: F401
+from .covisibility import CovisBatch, update_connections  # noqa: F401
 from .essential_graph import OptimizeEssentialGraph, OptimizeEssentialGraphDevice, essential_graph_workspace_bytes  # noqa: F401
 from .sim3 import draw_sets as sim3_draw_sets  # noqa: F401  (draw_sets is the two-view initialiser's)

@@ -2,7 +2,7 @@
 declared entry point of viorb.h is exported, has a signature here and that the argument counts agree; tests/test_global_ba_se3_ref.py
 does the same for SIGNATURES_GLOBAL_BA_SE3, tests/test_two_view_ref.py for SIGNATURES_TWO_VIEW, tests/test_sim3_ref.py for SIGNATURES_SIM3,
 tests/test_sim3_match_ref.py for SIGNATURES_SIM3_MATCH, tests/test_kf_culling_ref.py for SIGNATURES_CULLING, tests/test_reloc_ref.py for
-SIGNATURES_RELOCALIZATION, tests/test_local_map_ref.py for SIGNATURES_LOCAL_MAP)."""
+SIGNATURES_RELOCALIZATION, tests/test_local_map_ref.py for SIGNATURES_LOCAL_MAP, tests/test_covis_ref.py for SIGNATURES_COVISIBILITY)."""
 import ctypes as C
 import os
 import numpy as np
@@ -188,6 +188,24 @@ class LocalMapSnapshot(C.Structure):
 class LocalMapResult(C.Structure):
     """viorb_local_map_result (include/viorb_local_map.h)."""
     _fields_ = [(n, C.c_void_p) for n in LOCAL_MAP_RESULT_FIELDS]
+
+
+COVIS_INTS = ("batch", "n_kf", "n_kp", "n_pt", "n_obs", "n_conn", "n_ord", "n_target")
+COVIS_ARRAYS = ("kf_start", "kf_by_key", "kf_flags", "kf_parent", "kp_start", "kp_point", "pt_start", "pt_bad", "obs_start", "obs",
+                "conn_start", "conn_kf", "conn_w", "ord_start", "ord_kf", "ord_w", "target_start", "target_kf")
+COVIS_RESULT_REQUIRED = ("conn_kf_out", "conn_w_out", "conn_n_out", "ord_kf_out", "ord_w_out", "ord_n_out", "status")
+COVIS_RESULT_FIELDS = COVIS_RESULT_REQUIRED + ("need", "kf_parent_out", "kf_flags_out", "kf_touched", "t_observers", "t_max_kf", "t_max_w", "t_added",
+                                               "t_parent", "loop_conn", "n_loop_conn")
+
+
+class CovisMap(C.Structure):
+    """viorb_covis_map (include/viorb_covisibility.h)."""
+    _fields_ = [(n, C.c_int32) for n in COVIS_INTS] + [(n, C.c_void_p) for n in COVIS_ARRAYS]
+
+
+class CovisResult(C.Structure):
+    """viorb_covis_result (include/viorb_covisibility.h)."""
+    _fields_ = [(n, C.c_void_p) for n in COVIS_RESULT_FIELDS]
 
 
 class TrackerConfig(C.Structure):
@@ -495,6 +513,16 @@ SIGNATURES_LOCAL_MAP = {
     "viorb_debug_update_local_map_host": (i32, [PP(LocalMapSnapshot), PP(LocalMapResult), i32, i32, i32]),
 }
 
+# mirrors include/viorb_covisibility.h (KeyFrame::UpdateConnections for ordered targets); tests/test_covis_ref.py checks names and
+# argument counts against it
+SIGNATURES_COVISIBILITY = {
+    "viorb_update_connections_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "viorb_update_connections_device": (i32, [PP(CovisMap), PP(CovisResult), i32, i32, vp, sz, vp]),
+    "viorb_update_connections": (i32, [PP(CovisMap), PP(CovisResult), i32, i32]),
+    "viorb_update_connections_shape": (i32, [vp]),
+    "viorb_debug_update_connections_host": (i32, [PP(CovisMap), PP(CovisResult), i32, i32]),
+}
+
 _lib = None
 
 
@@ -517,7 +545,7 @@ def lib():
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GLOBAL_BA_SE3.items()) + list(SIGNATURES_TWO_VIEW.items()) \
                 + list(SIGNATURES_SIM3.items()) + list(SIGNATURES_SIM3_MATCH.items()) + list(SIGNATURES_ESSENTIAL_GRAPH.items()) \
                 + list(SIGNATURES_SEARCH_INIT.items()) + list(SIGNATURES_CULLING.items()) + list(SIGNATURES_RELOCALIZATION.items()) \
-                + list(SIGNATURES_LOCAL_MAP.items()):
+                + list(SIGNATURES_LOCAL_MAP.items()) + list(SIGNATURES_COVISIBILITY.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
