@@ -525,8 +525,7 @@ int viorb_local_ba_navstate(const double* kfs, int nk, int n_local, int prev_kf,
  * LOCK STEP, max_in_flight at a time (<= 0: 128; at most 512): one launch per solver step covers every window of the group and each
  * window's Levenberg / two-phase state machine lives in its control block on the device — a single window is a chain of small
  * latency-bound launches that leaves most of the GPU idle. The windows of a group are prepared (checks, graph bookkeeping, upload) by a
- * few host threads. With VIORB_LBA_STREAMS=1 the round-1 driver runs instead (one HIP stream and host LM loop per window, max_in_flight
- * of them, <= 0: 16). When a group fails (a HIP error), every window of it that has no result yet and every later window gets that
+ * few host threads. The single calls run the same decision functions on the device (csrc/lba_ctl.h), one window per stream. When a group fails (a HIP error), every window of it that has no result yet and every later window gets that
  * error in `status`. Results are those of the individual calls (to rounding: the order of the terms of a Schur block's sum is not
  * fixed from run to run). */
 typedef struct viorb_lba_window {

@@ -1,11 +1,6 @@
 """GPU parity of Optimizer::LocalBundleAdjustmentNavState (viorb_local_ba_navstate, csrc/local_ba.hip) against the oracle
 (oracle/local_ba.cpp): same LM trajectory (iteration counts), chi2 within 1e-5 relative, identical erase flags, key-frame
 states and points to solver precision; stop flag honoured; argument checks."""
-import os
-import subprocess
-import sys
-import textwrap
-
 import numpy as np
 import pytest
 from viorb_amd.synth import make_local_ba_problem
@@ -39,49 +34,6 @@ def test_local_ba_matches_oracle(oracle, seed, W, npts, extra):
     assert np.array_equal(got["erase"], ref["erase"])
     np.testing.assert_allclose(got["kfs"], ref["kfs"], rtol=0, atol=1e-7)
     np.testing.assert_allclose(got["points"], ref["points"], rtol=0, atol=1e-6)
-
-
-# the child of test_local_ba_host_lm_path_matches_oracle: solves the windows named on its command line with the pre-integrations the
-# parent wrote, and writes what the solver returned
-_HOST_LM_CHILD = textwrap.dedent("""
-    import sys
-    sys.path.insert(0, %r)
-    import numpy as np
-    from viorb_amd import LocalBundleAdjustmentNavState
-    from viorb_amd.synth import make_local_ba_problem
-    tmp = sys.argv[1]
-    for a in sys.argv[2:]:
-        seed, W, npts, extra = (int(v) for v in a.split(","))
-        p = make_local_ba_problem(seed, W=W, n_points=npts, n_fixed_extra=extra)
-        pre = np.load("%%s/pre_%%d.npy" %% (tmp, seed))
-        got = LocalBundleAdjustmentNavState(p["kfs"], p["n_local"], p["prev_kf"], pre, p["points"], p["edge_idx"], p["edge_obs"], p["gw"], p["cam"])
-        np.savez("%%s/got_%%d.npz" %% (tmp, seed), **got)
-    print("host lm ok")
-""") % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def test_local_ba_host_lm_path_matches_oracle(oracle, tmp_path):
-    """VIORB_LBA_HOST_LM=1: every Levenberg trial is decided on the host (BaSolve::advance, ST_AFTER_TRIAL), the path the default solve
-    enters only after a rejected trial. The switch is read once per process, hence a fresh child. The two smallest windows of
-    test_local_ba_matches_oracle, held to that test's bars."""
-    cases = [(2, 4, 80, 2), (4, 1, 60, 2)]
-    refs = {}
-    for seed, W, npts, extra in cases:
-        p = make_local_ba_problem(seed, W=W, n_points=npts, n_fixed_extra=extra)
-        pre = _preints(oracle, p)
-        np.save(str(tmp_path / ("pre_%d.npy" % seed)), pre)
-        refs[seed] = oracle.local_ba(*_args(p, pre))
-    r = subprocess.run([sys.executable, "-c", _HOST_LM_CHILD, str(tmp_path)] + ["%d,%d,%d,%d" % c for c in cases],
-                       env=dict(os.environ, VIORB_LBA_HOST_LM="1"), capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "host lm ok" in r.stdout, (r.stdout[-1000:], r.stderr[-2000:])
-    for seed, _, _, _ in cases:
-        ref, got = refs[seed], np.load(str(tmp_path / ("got_%d.npz" % seed)))
-        assert (int(got["its_first"]), int(got["its_second"])) == (ref["its_first"], ref["its_second"])
-        assert abs(float(got["chi2_first"]) - ref["chi2_first"]) <= 1e-5 * ref["chi2_first"]
-        assert abs(float(got["chi2_final"]) - ref["chi2_final"]) <= 1e-5 * ref["chi2_final"]
-        assert np.array_equal(got["erase"], ref["erase"])
-        np.testing.assert_allclose(got["kfs"], ref["kfs"], rtol=0, atol=1e-7)
-        np.testing.assert_allclose(got["points"], ref["points"], rtol=0, atol=1e-6)
 
 
 def test_local_ba_batch_equals_single_calls(oracle):

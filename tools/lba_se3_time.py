@@ -1,5 +1,5 @@
 """Throughput of viorb_local_ba_se3_batch (vision-only LocalBundleAdjustment windows, W = 8 key frames, 600 points, half stereo):
-lock-step batch by default, VIORB_LBA_STREAMS=1 = the per-stream driver."""
+the lock-step batch."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from viorb_amd.synth import make_local_ba_se3_problem

@@ -19,7 +19,7 @@ for name, f in (("oracle", o.local_ba), ("gpu", LocalBundleAdjustmentNavState)):
         r = f(*a)
     print(name, "ms/solve %.2f" % ((time.perf_counter() - t0) / 5 * 1e3), r["its_first"], r["its_second"], r["chi2_final"], flush=True)
 
-# throughput with several windows in flight (viorb_local_ba_navstate_batch: one host thread, one HIP stream per window)
+# throughput with several windows in flight (viorb_local_ba_navstate_batch: the lock-step batch, max_in_flight windows per group)
 from viorb_amd import LocalBundleAdjustmentNavStateBatch
 q = dict(kfs=a[0], n_local=a[1], prev_kf=a[2], preint=a[3], points=a[4], edge_idx=a[5], edge_obs=a[6], gw=a[7], cam=a[8])
 for nwin, fl in ((8, 1), (8, 2), (16, 4), (32, 8), (64, 16), (64, 32)):

@@ -1,6 +1,6 @@
-// viorb_amd/csrc/lm_core.h — g2o's Levenberg control, written once for the seven solver loops ("Where the Levenberg rule
-// lives"): gba_run (global_ba.hip), BaSolve::advance, k_ba_lambda0_body / k_ba_decide_body and k_bab_lambda0 / k_bab_decide
-// (local_ba.hip), k_pose_opt_vi_mp (pose_opt_mp.inc), k_pose_opt_se3 (frontend_kernels.hip), k_sim3_optimize (sim3.hip). Host and device
+// viorb_amd/csrc/lm_core.h — g2o's Levenberg control, written once for the solver loops ("Where the Levenberg rule
+// lives"): gba_run (global_ba.hip), lba_lambda0 / lba_decide (lba_ctl.h: both drivers of the window solves in local_ba.hip),
+// k_pose_opt_vi_mp (pose_opt_mp.inc), k_pose_opt_se3 (frontend_kernels.hip), k_sim3_optimize (sim3.hip). Host and device
 // (VIO_HD), no state: every function takes and returns scalars, because the sites keep lambda / ni / chi2 / the counters in a host
 // struct, in a control block of doubles, in LDS words or in registers. The library is built with -ffp-contract=off and everything here
 // is inlined, so an expression rounds here exactly as it did at the site it was copied from. Where the state is stored, barriers, the
@@ -30,8 +30,8 @@ VIO_HD bool lm_accepted(double rho, double tempChi) { return rho > 0 && isfinite
 // (2 rho - 1)^3 of the good-step factor, in two spellings that differ in the last bit: over 2 000 000 rho uniform in (0, 1.5) on the
 // host (g++ -O2 -ffp-contract=off) the two cubes differ in 514 512 draws and the factor below in 23 034 (1.2 %). Each site keeps the
 // spelling it had, so no solve changes; unifying them would (DESIGN.md lists it as open).
-VIO_HD double lm_cube_pow(double t) { return pow(t, 3); }   // as g2o spells it: gba_run, BaSolve::advance, k_pose_opt_se3, k_sim3_optimize
-VIO_HD double lm_cube_mul(double t) { return t * t * t; }   // k_ba_decide_body, k_bab_decide, k_pose_opt_vi_mp
+VIO_HD double lm_cube_pow(double t) { return pow(t, 3); }   // as g2o spells it: gba_run, k_pose_opt_se3, k_sim3_optimize
+VIO_HD double lm_cube_mul(double t) { return t * t * t; }   // lba_decide, k_pose_opt_vi_mp
 // an accepted trial (:135-141): lambda *= max(1/3, min(1 - (2 rho - 1)^3, 2/3)), ni = 2; cube = lm_cube_pow / lm_cube_mul (2 * rho - 1)
 VIO_HD void lm_good_step(double& lambda, double& ni, double cube) {
     lambda *= fmax(LM_GOOD_STEP_LOWER_SCALE, fmin(1. - cube, LM_GOOD_STEP_UPPER_SCALE)); ni = 2;

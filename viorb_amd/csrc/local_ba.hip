@@ -6,12 +6,13 @@
 // Solver: g2o's Levenberg-Marquardt (optimization_algorithm_levenberg.cpp:61-189) with the Schur complement of the point
 // block (block_solver.hpp:367-486), 5 + 10 iterations with the chi2 / depth gate in between.
 //
-// Kernels (all FP64): k_ba_errors (per edge residuals + robust chi2), k_ba_lin_points (one thread per point: Jacobians,
-// weights, Hll, bl), k_ba_hpp (one workgroup per local key frame: its 6x6 (P,Phi) block), k_ba_imu (one workgroup per IMU
-// factor), k_ba_dinv (one thread per point: (Hll + lambda I)^-1), k_ba_schur (one wavefront per key-frame pair: its 6x6 block of
-// -W D^-1 W^T gathered over the points both key frames observe, W blocks precomputed with the linearisation, no atomics), k_ba_chol_solve (dense Cholesky of the <= 240x240 reduced system by
-// one 512-thread workgroup, register tiles + v_mfma_f64_16x16x4), k_ba_backsub, k_ba_update. The LM control flow (accept / reject, lambda
-// schedule, stop rule) runs on the device (k_ba_decide_body / the lock-step batch's control block); the host polls a few scalars per chunk.
+// Device code (all FP64), as bodies that the single window's launches (k_ba_*) and the lock-step batch's (k_bab_*) share: errors (per
+// edge residuals + robust chi2), the linearisation (one thread per edge, or per point: Jacobians, weights, W blocks, Hll, bl), hpp (one
+// workgroup per local key frame: its 6x6 (P,Phi) block), imu (one workgroup per IMU factor), dinv (one thread per point:
+// (Hll + lambda I)^-1), schur (one wavefront per key-frame pair: its 6x6 block of -W D^-1 W^T gathered over the points both key frames
+// observe, no atomics), chol_solve (dense Cholesky of the <= 240x240 reduced system by one 512-thread workgroup, register tiles +
+// v_mfma_f64_16x16x4), backsub8_update. The LM control flow (accept / reject, restore and retry, lambda schedule, stop rules, the phase
+// change) runs on the device, in the window's control block (lba_ctl.h); the host reads the block once per chunk of trials / few rounds.
 #include <hip/hip_runtime.h>
 #include <memory>
 #include <string>
@@ -20,10 +21,9 @@
 #include <vector>
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include "viorb_common.h"
 #include "ba_core.h"
-#include "lm_core.h"
+#include "lba_ctl.h"
 
 namespace viorb {
 
@@ -46,22 +46,17 @@ struct BaDev {
     const double *preint, *info_pvr; // [W][142], [W][81] (NavState window)
     double *e_pvr, *e_b;            // [W][9], [W][3] (NavState window)
     double *scal;                   // [8]: 0 chi2, 1 scale, 2 ok, 3 max diag
-    double *ctl;                    // device-side LM control (BA_CTL_*), used when use_ctl != 0: kernels return at once while ctl[HALT] != 0
+    double *ctl;                    // the window's control block (lba_ctl.h): kernels return at once while ctl[BA_B_GATE] != 0
     int *ticket;                    // block counter of k_ba_f_errors_decide (the last block to add its chi2 takes the trial's decision)
-    int use_ctl;                    // and take lambda from ctl[LAMBDA] instead of their argument
+    int use_ctl;                    // 1 in both drivers: the two lines above, and lambda from ctl[BA_CTL_LAMBDA]
     const unsigned long long* abort_host;   // page-locked word the waiting host thread sets when the caller's pbStopFlag goes up (nullptr: no flag)
     double cam[16], gw[3];          // NavState window: cam[16], gw; SE3 window: cam[0..4] = fx fy cx cy bf
     double acc_bias_rw2;
 };
 
-// Device-side Levenberg control (g2o optimization_algorithm_levenberg.cpp:61-164) for the common case of an LM iteration whose first
-// trial is accepted: the host enqueues several iterations back to back, k_ba_decide_body takes the accept / stop decisions on the device, and
-// after a REJECTED trial every later kernel of the chunk returns at once (ctl[HALT] = 1) so that the host finds the system, the trial
-// state and the trial's scalars untouched and continues with its own trial loop (lambda *= ni, restore, retry).
-enum { BA_CTL_LAMBDA = 0, BA_CTL_NI, BA_CTL_CHI, BA_CTL_INICHI, BA_CTL_NBAD, BA_CTL_HALT, BA_CTL_ITS, BA_CTL_IT, BA_CTL_RHO,
-       BA_CTL_TRIALS, BA_CTL_REJECTS,     // Levenberg trials taken / rejected (info[4], info[5]): the lock-step batch counts here (k_bab_decide)
-       BA_CTL_N = 32 };
-__device__ __forceinline__ bool ba_skip(const BaDev& D) { return D.use_ctl && D.ctl[BA_CTL_HALT] != 0.0; }
+// Once an optimize() call is over (ctl[BA_B_GATE] != 0) every solver kernel still in the stream returns at once: the single window's host
+// enqueues trials ahead of the decisions (BaSolve::run); in the lock-step batch the word is 0 whenever these bodies run (k_bab_phase).
+__device__ __forceinline__ bool ba_skip(const BaDev& D) { return D.use_ctl && D.ctl[BA_B_GATE] != 0.0; }
 // g2o polls terminate() once per iteration and once per LM trial (optimization_algorithm_levenberg.cpp / sparse_optimizer.cpp:354-432); the
 // device-side LM control does the same through a system-scope load of the mirrored flag, so an abort costs at most the trial in flight
 __device__ __forceinline__ bool ba_abort_requested(const BaDev& D) {
@@ -105,33 +100,9 @@ __device__ __forceinline__ void k_ba_errors_body(const BaDev& D, int mono_kernel
     if (threadIdx.x == 0) { double t = 0; for (int w = 0; w < (int)(blockDim.x >> 6); w++) t += s_red[w]; atomicAdd(&D.scal[0], t); }
 }
 
-// one thread per point: Jacobians + weights of its active edges (stored per edge), Hll and bl of the point
-__device__ __forceinline__ void k_ba_lin_points_body(const BaDev& D, int mono_kernel) {
-    if (ba_skip(D)) return;
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= D.NP) return;
-    double H[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
-    for (int k = D.pt_start[p]; k < D.pt_start[p + 1]; k++) {
-        if (D.level[k] != 0) continue;
-        const cam_t K = ld_cam(D.cam);
-        double Jp[6], Jk[12];
-        ba_nav_jac(K, ba_edge_geom(D, k, K), Jp, Jk);
-        const double e[2] = {D.err[2 * k], D.err[2 * k + 1]}, is2 = D.e_obs[3 * k + 2];
-        double r0, r1;
-        ba_robust(mono_kernel, is2 * (e[0] * e[0] + e[1] * e[1]), ba_delta_mono_window(), &r0, &r1);
-        const double w = r1 * is2;
-        D.wgt[k] = w;
-        for (int a = 0; a < 6; a++) D.Jp[6 * k + a] = Jp[a];
-        for (int a = 0; a < 12; a++) D.Jk[12 * k + a] = Jk[a];
-        ba_w_block<2>(w, Jk, Jp, D.We + 18 * (size_t)k);
-        ba_point_add<2>(H, b, w, Jp, e);
-    }
-    ba_point_store(D.Hll + (size_t)p * 9, D.bl + (size_t)p * 3, H, b);
-}
-
-// The same linearisation with one thread per EDGE (Jacobians, weight, W block) and the point blocks summed afterwards by one thread per
-// point from the stored Jacobians (k_ba_hll_body: same terms in the same order as k_ba_lin_points_body, bit for bit): a single window
-// has 2000 points = 8 workgroups for the version above but 43 for this one.
+// The NavState linearisation with one thread per EDGE (Jacobians, weight, W block); the point blocks Hll, bl are summed afterwards by one
+// thread per point from the stored Jacobians (k_ba_hll_body), in the order of the point's edges. A single window has 2000 points = 8
+// workgroups with one thread per point (the form k_ba_se3_lin_points_body still has) but 43 with one per edge.
 __device__ __forceinline__ void k_ba_lin_edges_body(const BaDev& D, int mono_kernel) {
     if (ba_skip(D)) return;
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -582,51 +553,10 @@ __device__ __forceinline__ void k_ba_chol_solve_body(const BaDev& D, double* s_d
 #ifdef VIORB_CHOL_TIMING
     if (lane == 0 && (wv == 0 || wv == BA_CHOL_OWNERS) && blockIdx.x == 0) printf("chol cycles wave %d: [0] %llu [1] %llu [2] %llu [3] %llu [4] %llu [5] %llu [6] %llu\n", wv, ct_[0], ct_[1], ct_[2], ct_[3], ct_[4], ct_[5], ct_[6]);
 #endif
-    if (t == 0) { D.scal[2] = s_ok ? 1.0 : 0.0; D.scal[1] = 0.0; D.scal[0] = 0.0; }      // [1], [0]: accumulators of k_ba_backsub and k_ba_*_errors, which follow
+    if (t == 0) { D.scal[2] = s_ok ? 1.0 : 0.0; D.scal[1] = 0.0; D.scal[0] = 0.0; }      // [1], [0]: accumulators of the back-substitution and of the error pass, which follow
 }
 
-// xl = Dinv (bl - W^T xp) per point, and the LM scale term sum x (lambda x + b)
-__device__ __forceinline__ void k_ba_backsub_body(const BaDev& D, double lambda_arg) {
-    if (ba_skip(D)) return;
-    const double lambda = ba_lambda(D, lambda_arg);
-    __shared__ double s_red[4];
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    double sc = 0;
-    if (p < D.NP) {
-        double c0 = D.bl[3 * p], c1 = D.bl[3 * p + 1], c2 = D.bl[3 * p + 2];
-        for (int k = D.pt_start[p]; k < D.pt_start[p + 1]; k++) {
-            if (D.level[k] != 0 || D.e_kf[k] >= D.W) continue;
-            const double* Wk = D.We + (size_t)18 * k;
-            const int ba = D.pose_dim * D.e_kf[k];
-#pragma unroll
-            for (int r = 0; r < 6; r++) {
-                const double x = D.xp[ba + ba_loc(D, r)];
-                c0 -= Wk[3 * r] * x; c1 -= Wk[3 * r + 1] * x; c2 -= Wk[3 * r + 2] * x;
-            }
-        }
-        const double* Di = D.Dinv + (size_t)p * 9;
-        const double x0 = Di[0] * c0 + Di[1] * c1 + Di[2] * c2, x1 = Di[3] * c0 + Di[4] * c1 + Di[5] * c2, x2 = Di[6] * c0 + Di[7] * c1 + Di[8] * c2;
-        D.xl[3 * p] = x0; D.xl[3 * p + 1] = x1; D.xl[3 * p + 2] = x2;
-        sc = x0 * (lambda * x0 + D.bl[3 * p]) + x1 * (lambda * x1 + D.bl[3 * p + 1]) + x2 * (lambda * x2 + D.bl[3 * p + 2]);
-    }
-    if (blockIdx.x == 0) for (int q = threadIdx.x; q < D.np; q += blockDim.x) sc += D.xp[q] * (lambda * D.xp[q] + D.bp[q]);
-    sc = ba_block_sum(sc, s_red);
-    if (threadIdx.x == 0) atomicAdd(&D.scal[1], sc);
-}
-
-__device__ __forceinline__ void k_ba_update_body(const BaDev& D) {
-    if (ba_skip(D)) return;
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < D.W) {
-        double* k = D.kf + (size_t)q * 22;
-        for (int c = 0; c < 22; c++) D.kf_bak[(size_t)q * 22 + c] = k[c];      // what a rejected LM trial goes back to (k_ba_restore)
-        const pvr s = inc_small_pvr(ld_pvr(k), D.xp + 12 * q);
-        st_pvr(k, s);
-        for (int c = 0; c < 3; c++) k[19 + c] += D.xp[12 * q + 9 + c];
-    }
-    if (q < D.NP) for (int c = 0; c < 3; c++) { D.pt_bak[3 * q + c] = D.pt[3 * q + c]; D.pt[3 * q + c] += D.xl[3 * q + c]; }
-}
-// a rejected trial: local key frames and points back to what k_ba_update / k_ba_se3_update saved
+// a rejected trial: local key frames and points back to what k_ba_backsub8_update_body saved
 __device__ __forceinline__ void k_ba_restore_body(const BaDev& D) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x, stride = D.kf_stride;
     if (q < D.W) for (int c = 0; c < stride; c++) D.kf[(size_t)q * stride + c] = D.kf_bak[(size_t)q * stride + c];
@@ -643,7 +573,8 @@ __device__ __forceinline__ void k_ba_gate_body(const BaDev& D, uint8_t* out, int
     if (set_level) { if (bad) D.level[k] = 1; } else out[k] = (uint8_t)bad;
 }
 
-// zero Hpp / bp (and the max-diagonal accumulator) for the linearisation of an iteration; first = 1 on the first iteration of a phase
+// zero Hpp / bp (and the max-diagonal accumulator) for the linearisation of an iteration; first = 1 on the first iteration of a single
+// window's phase (the lock-step round has launches of its own for that: k_bab_round_begin, k_bab_take_chi, k_bab_lambda0)
 __device__ __forceinline__ void k_ba_clear_body(const BaDev& D, int first, int bid = blockIdx.x, int nblk = gridDim.x) {
     if (ba_skip(D)) return;
     const size_t n2 = (size_t)D.np * D.np;
@@ -656,46 +587,19 @@ __device__ __forceinline__ void k_ba_clear_body(const BaDev& D, int first, int b
         }
     }
 }
-// lambda_0 (:166-180), after k_ba_max_diag on the first iteration of a phase
-__device__ __forceinline__ void k_ba_lambda0_body(const BaDev& D) {
-    if (ba_skip(D)) return;
-    if (blockIdx.x == 0 && threadIdx.x == 0) { D.ctl[BA_CTL_LAMBDA] = lm_lambda_init(D.scal[3]); D.ctl[BA_CTL_NI] = 2.0; }
-}
-// after the trial's k_ba_*_errors: accepted -> lambda update, stop tests (qmax = 1: the iteration's only trial); rejected -> HALT = 1 and
-// nothing else changes (the host takes over from ST_AFTER_TRIAL with the scalars as they are)
-__device__ __forceinline__ void k_ba_decide_body(const BaDev& D, int last_of_phase) {     // one thread
-    if (ba_skip(D)) return;
-    double* c = D.ctl;
-    const bool ok2 = D.scal[2] > 0.5;
-    const double tempChi = lm_trial_chi2(ok2, __hip_atomic_load(&D.scal[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    const double rho = lm_rho(c[BA_CTL_CHI], tempChi, ok2 ? D.scal[1] : 0.0);
-    c[BA_CTL_RHO] = rho;
-    if (!lm_accepted(rho, tempChi)) { c[BA_CTL_HALT] = 1.0; return; }
-    lm_good_step(c[BA_CTL_LAMBDA], c[BA_CTL_NI], lm_cube_mul(2 * rho - 1));
-    c[BA_CTL_CHI] = tempChi;
-    c[BA_CTL_ITS] += 1.0; c[BA_CTL_IT] += 1.0;
-    int nBad = (int)c[BA_CTL_NBAD];
-    const bool stop_opt = lm_iteration_stops(rho, 1, c[BA_CTL_INICHI], tempChi, nBad);
-    c[BA_CTL_NBAD] = nBad;
-    if (stop_opt || last_of_phase || ba_abort_requested(D)) c[BA_CTL_HALT] = 2.0;      // this optimize() call is over (or "!terminate()" failed)
-}
 
-
-// ---- by-value kernels of the single-window driver ---------------------------------------------------------------------------------
+// ---- by-value kernels of the single-window driver (its fused launches follow the vision-only bodies below) ---------------------------
 __global__ void k_ba_errors(BaDev D, int mono_kernel) { k_ba_errors_body(D, mono_kernel); }
-__global__ void k_ba_lin_points(BaDev D, int mono_kernel) { k_ba_lin_points_body(D, mono_kernel); }
-__global__ __launch_bounds__(256) void k_ba_hpp(BaDev D) { k_ba_hpp_body(D); }
-__global__ __launch_bounds__(256) void k_ba_imu(BaDev D) { k_ba_imu_body(D); }
-__global__ void k_ba_init_reduced(BaDev D, double lambda_arg) { k_ba_init_reduced_body(D, lambda_arg); }
 __global__ void k_ba_max_diag(BaDev D) { k_ba_max_diag_body(D); }
-__global__ void k_ba_dinv(BaDev D, double lambda_arg) { k_ba_dinv_body(D, lambda_arg); }
 __global__ __launch_bounds__(64) void k_ba_schur(BaDev D) { k_ba_schur_body(D, blockIdx.x); }
 __global__ __launch_bounds__(BA_CHOL_THREADS) void k_ba_chol_solve(BaDev D) { extern __shared__ __attribute__((aligned(16))) double s_chol[]; k_ba_chol_solve_body(D, s_chol); }
-__global__ void k_ba_backsub(BaDev D, double lambda_arg) { k_ba_backsub_body(D, lambda_arg); }
-__global__ void k_ba_update(BaDev D) { k_ba_update_body(D); }
 __global__ void k_ba_restore(BaDev D) { k_ba_restore_body(D); }
 __global__ void k_ba_gate(BaDev D, uint8_t* out, int set_level) { k_ba_gate_body(D, out, set_level); }
-__global__ void k_ba_lambda0(BaDev D) { k_ba_lambda0_body(D); }
+// the control block at the start of the solve and at its phase change: the host applies the same functions to its copy (BaSolve::run)
+__global__ void k_ba_ctl_init(BaDev D) { if (threadIdx.x < BA_B_N) D.ctl[threadIdx.x] = lba_ctl_init(threadIdx.x); }
+__global__ void k_ba_phase(BaDev D) { if (threadIdx.x == 0) lba_phase(D.ctl); }
+// lambda_0, after k_ba_max_diag on the first iteration of a phase
+__global__ void k_ba_lambda0(BaDev D) { if (!ba_skip(D) && blockIdx.x == 0 && threadIdx.x == 0) lba_lambda0(D.ctl, D.scal[3]); }
 
 // ---- lock-step batch: one launch covers every window of a batch (blockIdx.y = window) ------------------------------------------------
 // viorb_local_ba_navstate_batch used to give every window its own stream and host-driven LM loop; the streams share four hardware queues,
@@ -703,10 +607,8 @@ __global__ void k_ba_lambda0(BaDev D) { k_ba_lambda0_body(D); }
 // same ROUND of launches — [chi2 of a new phase] [linearise if the last trial was accepted] [lambda_0 on a phase's first iteration]
 // [one LM trial] [decide] [restore a rejected trial] [phase gate] — and the per-window state machine of g2o's Levenberg loop
 // (optimization_algorithm_levenberg.cpp:61-164) plus LocalBundleAdjustmentNavState's two optimize() calls (src/Optimizer.cc:2026-2099)
-// lives in the window's control block on the device. A round is 15 launches for the whole batch (the k_bab_f_* ones cover several solver steps by block range); the host only counts finished windows
+// lives in the window's control block on the device (lba_ctl.h). A round is 16 launches for the whole batch (the k_bab_f_* ones cover several solver steps by block range); the host only counts finished windows
 // every few rounds.
-enum { BA_B_DONE = 16, BA_B_NEED_CHI, BA_B_NEED_LIN, BA_B_FIRST, BA_B_PHASE, BA_B_MONO, BA_B_QMAX, BA_B_GATE, BA_B_RESTORE, BA_B_ITERS,
-       BA_B_ITS0, BA_B_ITS1, BA_B_CHI0, BA_B_CHI1, BA_B_ABORT, BA_B_N = 32 };
 #define BA_B_WINDOW() const BaDev& D = Dv[blockIdx.y]; const double* c = D.ctl; if (c[BA_B_DONE] != 0.0 || c[BA_B_ABORT] != 0.0) return
 __global__ void k_bab_round_begin(const BaDev* __restrict__ Dv, int nwin) {
     const int w = blockIdx.x * blockDim.x + threadIdx.x;
@@ -729,7 +631,7 @@ __global__ void k_bab_lambda0(const BaDev* __restrict__ Dv, int nwin) {
     if (w >= nwin) return;
     const BaDev& D = Dv[w]; double* c = D.ctl;
     if (c[BA_B_DONE] != 0.0 || c[BA_B_ABORT] != 0.0 || c[BA_B_NEED_LIN] == 0.0) return;
-    if (c[BA_B_FIRST] != 0.0) { c[BA_CTL_LAMBDA] = lm_lambda_init(D.scal[3]); c[BA_CTL_NI] = 2.0; c[BA_CTL_NBAD] = 0.0; c[BA_B_FIRST] = 0.0; }
+    if (c[BA_B_FIRST] != 0.0) lba_lambda0(c, D.scal[3]);
     c[BA_B_NEED_LIN] = 0.0;
 }
 // The batch's grid is (pairs, windows) linearised and dealt so that all pairs of a window run on ONE XCD (workgroup ids go round-robin over the
@@ -751,27 +653,7 @@ __global__ void k_bab_decide(const BaDev* __restrict__ Dv, int nwin) {
     const BaDev& D = Dv[w]; double* c = D.ctl;
     if (c[BA_B_DONE] != 0.0) return;
     if (c[BA_B_ABORT] != 0.0) { c[BA_B_GATE] = 2.0; return; }            // the host saw the stop flag between rounds (this round's trial kernels were skipped): final gate on the state as it is
-    const bool abort_now = ba_abort_requested(D);                        // the flag went up during this trial: take the trial's decision, then leave both loops ("&& !terminate()")
-    const bool ok2 = D.scal[2] > 0.5;
-    const double tempChi = lm_trial_chi2(ok2, D.scal[0]);
-    const double rho = lm_rho(c[BA_CTL_CHI], tempChi, ok2 ? D.scal[1] : 0.0);
-    c[BA_CTL_RHO] = rho;
-    int qmax = (int)c[BA_B_QMAX];
-    c[BA_CTL_TRIALS] += 1.0;
-    if (lm_accepted(rho, tempChi)) { lm_good_step(c[BA_CTL_LAMBDA], c[BA_CTL_NI], lm_cube_mul(2 * rho - 1)); c[BA_CTL_CHI] = tempChi; }
-    else { lm_bad_step(c[BA_CTL_LAMBDA], c[BA_CTL_NI]); c[BA_B_RESTORE] = 1.0; c[BA_CTL_REJECTS] += 1.0; }
-    qmax++;
-    if (abort_now) { c[BA_B_GATE] = 2.0; return; }                       // a rejected trial is restored by k_bab_restore before the gate
-    if (lm_retry(rho, qmax)) { c[BA_B_QMAX] = qmax; return; }            // another trial of the same iteration (no re-linearisation)
-    // the iteration is over
-    const int phase = (int)c[BA_B_PHASE];
-    c[BA_B_ITS0 + phase] += 1.0; c[BA_B_CHI0 + phase] = c[BA_CTL_CHI];
-    int nBad = (int)c[BA_CTL_NBAD];
-    const bool stop_opt = lm_iteration_stops(rho, qmax, c[BA_CTL_INICHI], c[BA_CTL_CHI], nBad);
-    c[BA_CTL_NBAD] = nBad;
-    c[BA_CTL_IT] += 1.0; c[BA_B_QMAX] = 0.0;
-    if (stop_opt || c[BA_CTL_IT] >= c[BA_B_ITERS]) c[BA_B_GATE] = phase == 0 ? 1.0 : 2.0;
-    else c[BA_B_NEED_LIN] = 1.0;
+    lba_decide(c, D.scal[0], D.scal[1], D.scal[2], ba_abort_requested(D));   // a rejected trial is restored by k_bab_restore, before the gate
 }
 __global__ void k_bab_restore(const BaDev* __restrict__ Dv) { BA_B_WINDOW(); if (c[BA_B_RESTORE] == 0.0) return; k_ba_restore_body(D); }
 // after the gate: phase 0 -> second optimize() without the mono kernel (src/Optimizer.cc:2037-2099), phase 1 -> the window is finished
@@ -780,14 +662,7 @@ __global__ void k_bab_phase(const BaDev* __restrict__ Dv, int nwin, int* __restr
     if (w >= nwin) return;
     const BaDev& D = Dv[w]; double* c = D.ctl;
     if (c[BA_B_DONE] != 0.0) return;
-    c[BA_B_RESTORE] = 0.0;
-    if (c[BA_B_GATE] == 1.0) {
-        c[BA_B_PHASE] = 1.0; c[BA_B_MONO] = 0.0; c[BA_B_ITERS] = 10.0; c[BA_CTL_IT] = 0.0; c[BA_B_QMAX] = 0.0;
-        c[BA_B_NEED_CHI] = 1.0; c[BA_B_NEED_LIN] = 1.0; c[BA_B_FIRST] = 1.0; c[BA_B_GATE] = 0.0;
-    } else if (c[BA_B_GATE] == 2.0) {
-        c[BA_B_GATE] = 0.0; c[BA_B_DONE] = 1.0;
-        atomicAdd(n_done, 1);
-    }
+    if (lba_phase(c)) atomicAdd(n_done, 1);
 }
 
 // ---- vision-only LocalBundleAdjustment (reference src/Optimizer.cc:3980-4311): SE3 key frames (kf = qx qy qz qw tx ty tz of Tcw),
@@ -837,16 +712,6 @@ __device__ __forceinline__ void k_ba_se3_lin_points_body(const BaDev& D, int ker
     }
     ba_point_store(D.Hll + (size_t)p * 9, D.bl + (size_t)p * 3, H, b);
 }
-__device__ __forceinline__ void k_ba_se3_update_body(const BaDev& D) {
-    if (ba_skip(D)) return;
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < D.W) {                                                   // VertexSE3Expmap::oplusImpl: T <- exp(update) * T
-        double* k = D.kf + (size_t)q * 7;
-        for (int c = 0; c < 7; c++) D.kf_bak[(size_t)q * 7 + c] = k[c];
-        se3_oplus7(k, D.xp + 6 * q);
-    }
-    if (q < D.NP) for (int c = 0; c < 3; c++) { D.pt_bak[3 * q + c] = D.pt[3 * q + c]; D.pt[3 * q + c] += D.xl[3 * q + c]; }
-}
 // chi2 (5.991 mono / 7.815 stereo, stale error on excluded edges) / depth gate, Optimizer.cc:4170-4200 and :4207-4235
 __device__ __forceinline__ void k_ba_se3_gate_body(const BaDev& D, uint8_t* out, int set_level) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -858,34 +723,49 @@ __device__ __forceinline__ void k_ba_se3_gate_body(const BaDev& D, uint8_t* out,
     if (set_level) { if (bad) D.level[k] = 1; } else out[k] = (uint8_t)bad;
 }
 __global__ void k_ba_se3_errors(BaDev D, int kernels) { k_ba_se3_errors_body(D, kernels); }
-__global__ void k_ba_se3_lin_points(BaDev D, int kernels) { k_ba_se3_lin_points_body(D, kernels); }
-__global__ void k_ba_se3_update(BaDev D) { k_ba_se3_update_body(D); }
 __global__ void k_ba_se3_gate(BaDev D, uint8_t* out, int set_level) { k_ba_se3_gate_body(D, out, set_level); }
 
-// ---- fused launches of the single window's device-side LM chunk (BaSolve::advance, ST_FAST_CHUNK): kernels with no dependency between
-// them share a launch (by block range), the per-point back-substitution applies its own update, and the last block of the error pass
-// takes the trial's decision — 8 launches per LM iteration instead of 13. A single window is a chain of latency-bound launches of
-// 5-25 us each: every launch removed is ~7 us of the ~230 us a trial takes.
-__global__ __launch_bounds__(256) void k_ba_f_lin_clear(BaDev D, int mono_kernel, int first, int gP, int gC) {
-    if ((int)blockIdx.x < gP) { if (D.pose_dim == 12) k_ba_lin_points_body(D, mono_kernel); else k_ba_se3_lin_points_body(D, mono_kernel); }
-    else k_ba_clear_body(D, first, (int)blockIdx.x - gP, gC);
+// ---- fused launches of the single window's slots (BaSolve::run): kernels with no dependency between them share a launch
+// (by block range), the per-point back-substitution applies its own update, and the last block of the error pass takes the trial's
+// decision — 8 launches per Levenberg trial. A single window is a chain of latency-bound launches of 5-25 us each: every launch removed
+// is ~7 us of the ~230 us a trial takes. The host enqueues slots ahead of the decisions, so what a slot does is read from the control
+// block: after an iteration has ended it linearises (its first two launches); after a rejected trial it is a retry — the first launch
+// puts the estimate back instead and the second returns at once, the system of the last linearisation is solved again with the new
+// lambda. (A rejected trial that ends its iteration without a Terminate — rho NaN — is handled like a retry: the linearisation at hand is
+// the one of the restored estimate.)
+enum { BA_SLOT_IDLE = 0, BA_SLOT_LINEARISE, BA_SLOT_RESTORE };
+__device__ __forceinline__ int ba_slot(const BaDev& D) {
+    const double* c = D.ctl;
+    if (c[BA_B_GATE] != 0.0) return BA_SLOT_IDLE;                         // the phase is over
+    if (c[BA_B_RESTORE] != 0.0) return BA_SLOT_RESTORE;
+    return c[BA_B_NEED_LIN] != 0.0 ? BA_SLOT_LINEARISE : BA_SLOT_IDLE;
 }
-__global__ __launch_bounds__(256) void k_ba_f_line_clear(BaDev D, int mono_kernel, int first, int gE, int gC) {      // NavState window: one thread per edge
-    if ((int)blockIdx.x < gE) k_ba_lin_edges_body(D, mono_kernel); else k_ba_clear_body(D, first, (int)blockIdx.x - gE, gC);
+// gL blocks of the linearisation (at least as many as k_ba_restore_body needs), gC of the clear
+template <int MODEL> __device__ __forceinline__ void k_ba_f_lin_clear_body(const BaDev& D, int mono_kernel, int gL, int gC) {
+    const int slot = ba_slot(D);
+    if (slot == BA_SLOT_RESTORE) { k_ba_restore_body(D); return; }
+    if (slot != BA_SLOT_LINEARISE) return;
+    if ((int)blockIdx.x >= gL) k_ba_clear_body(D, D.ctl[BA_B_FIRST] != 0.0, (int)blockIdx.x - gL, gC);
+    else if (MODEL == 0) k_ba_lin_edges_body(D, mono_kernel);
+    else k_ba_se3_lin_points_body(D, mono_kernel);
 }
+__global__ __launch_bounds__(256) void k_ba_f_lin_clear(BaDev D, int mono_kernel, int gL, int gC) { k_ba_f_lin_clear_body<1>(D, mono_kernel, gL, gC); }    // vision-only window: one thread per point
+__global__ __launch_bounds__(256) void k_ba_f_line_clear(BaDev D, int mono_kernel, int gL, int gC) { k_ba_f_lin_clear_body<0>(D, mono_kernel, gL, gC); }   // NavState window: one thread per edge
 __global__ __launch_bounds__(256) void k_ba_f_hpp_imu_hll(BaDev D) {
+    if (ba_slot(D) != BA_SLOT_LINEARISE) return;
     const int b = blockIdx.x;
     if (b < D.W) k_ba_hpp_body(D, b); else if (b < 2 * D.W) k_ba_imu_body(D, b - D.W); else k_ba_hll_body(D, b - 2 * D.W);
 }
-__global__ __launch_bounds__(256) void k_ba_f_hpp_imu(BaDev D) {
-    if ((int)blockIdx.x < D.W) k_ba_hpp_body(D, blockIdx.x); else k_ba_imu_body(D, (int)blockIdx.x - D.W);
+__global__ __launch_bounds__(256) void k_ba_f_hpp(BaDev D) {                 // vision-only window (its linearisation wrote the point blocks itself)
+    if (ba_slot(D) != BA_SLOT_LINEARISE) return;
+    k_ba_hpp_body(D, blockIdx.x);
 }
 __global__ __launch_bounds__(256) void k_ba_f_init_dinv(BaDev D, int gR) {
     if ((int)blockIdx.x < gR) k_ba_init_reduced_body(D, 0.0); else k_ba_dinv_body(D, 0.0, (int)blockIdx.x - gR);
 }
 // back-substitution of the point block with EIGHT lanes per point (one observation each per trip, shuffle reduction) + the update: the
-// thread-per-point form (k_ba_backsub_body + k_ba_*_update_body) is 8 workgroups for a 2000-point window and the latency of a lane
-// walking its point's observations one after the other
+// thread-per-point form was 8 workgroups for a 2000-point window and the latency of a lane walking its point's observations one after
+// the other. xl = Dinv (bl - W^T xp) per point, the LM scale term sum x (lambda x + b), and the backup a rejected trial goes back to
 __device__ __forceinline__ void k_ba_backsub8_update_body(const BaDev& D) {
     if (ba_skip(D)) return;
     const double lambda = ba_lambda(D, 0.0);
@@ -914,12 +794,12 @@ __device__ __forceinline__ void k_ba_backsub8_update_body(const BaDev& D) {
         D.xl[3 * p] = x0; D.xl[3 * p + 1] = x1; D.xl[3 * p + 2] = x2;
         sc = x0 * (lambda * x0 + b0) + x1 * (lambda * x1 + b1) + x2 * (lambda * x2 + b2);
         const double xs[3] = {x0, x1, x2};
-        for (int c = 0; c < 3; c++) { D.pt_bak[3 * p + c] = D.pt[3 * p + c]; D.pt[3 * p + c] += xs[c]; }      // k_ba_*_update_body's point part
+        for (int c = 0; c < 3; c++) { D.pt_bak[3 * p + c] = D.pt[3 * p + c]; D.pt[3 * p + c] += xs[c]; }      // the backup a rejected trial goes back to (k_ba_restore_body)
     }
     if (blockIdx.x == 0) for (int q = threadIdx.x; q < D.np; q += blockDim.x) sc += D.xp[q] * (lambda * D.xp[q] + D.bp[q]);
     sc = ba_block_sum(sc, s_red);
     if (threadIdx.x == 0) atomicAdd(&D.scal[1], sc);
-    if (g < D.W) {                                                       // the key frames (k_ba_update_body / k_ba_se3_update_body)
+    if (g < D.W) {                                                       // the key frames, backup first
         if (D.pose_dim == 12) {
             double* k = D.kf + (size_t)g * 22;
             for (int c = 0; c < 22; c++) D.kf_bak[(size_t)g * 22 + c] = k[c];
@@ -929,7 +809,7 @@ __device__ __forceinline__ void k_ba_backsub8_update_body(const BaDev& D) {
         } else {
             double* k = D.kf + (size_t)g * 7;
             for (int c = 0; c < 7; c++) D.kf_bak[(size_t)g * 7 + c] = k[c];
-            se3_oplus7(k, D.xp + 6 * g);
+            se3_oplus7(k, D.xp + 6 * g);                                 // VertexSE3Expmap::oplusImpl: T <- exp(update) * T
         }
     }
 }
@@ -952,12 +832,19 @@ __global__ __launch_bounds__(256) void k_bab_f_init_dinv(const BaDev* __restrict
     if ((int)blockIdx.x < gR) k_ba_init_reduced_body(D, 0.0); else k_ba_dinv_body(D, 0.0, (int)blockIdx.x - gR);
 }
 __global__ __launch_bounds__(256) void k_bab_f_backsub8_update(const BaDev* __restrict__ Dv) { BA_B_WINDOW(); k_ba_backsub8_update_body(D); }
-__global__ __launch_bounds__(256) void k_ba_f_errors_decide(BaDev D, int mono_kernel, int last_of_phase) {
+// the single window's error pass; its last block takes the trial's decision (one thread) and so says what the next slot is
+__global__ __launch_bounds__(256) void k_ba_f_errors_decide(BaDev D, int mono_kernel) {
     if (D.pose_dim == 12) k_ba_errors_body(D, mono_kernel); else k_ba_se3_errors_body(D, mono_kernel);
     __shared__ int s_last;
     if (threadIdx.x == 0) { __threadfence(); s_last = atomicAdd(D.ticket, 1) == (int)gridDim.x - 1; }
     __syncthreads();
-    if (s_last && threadIdx.x == 0) { *D.ticket = 0; __threadfence(); k_ba_decide_body(D, last_of_phase); }
+    if (s_last && threadIdx.x == 0) {
+        *D.ticket = 0; __threadfence();
+        if (ba_skip(D)) return;
+        double* c = D.ctl;
+        c[BA_B_NEED_LIN] = 0.0; c[BA_B_RESTORE] = 0.0;                    // this slot's first launches have acted on them
+        lba_decide(c, __hip_atomic_load(&D.scal[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), D.scal[1], D.scal[2], ba_abort_requested(D));
+    }
 }
 // lock-step batch, the launches whose body depends on the kind of window (pose_dim 12: NavState, 6: vision-only SE3)
 __global__ void k_bab_errors_chi(const BaDev* __restrict__ Dv) {
@@ -972,7 +859,7 @@ __global__ void k_bab_errors(const BaDev* __restrict__ Dv) {
 __global__ void k_bab_ctl_init(const BaDev* __restrict__ Dv) {
     double* c = Dv[blockIdx.x].ctl;
     const int t = threadIdx.x;
-    if (t < BA_B_N) c[t] = (t == BA_B_NEED_CHI || t == BA_B_NEED_LIN || t == BA_B_FIRST || t == BA_B_MONO) ? 1.0 : (t == BA_B_ITERS ? 5.0 : 0.0);
+    if (t < BA_B_N) c[t] = lba_ctl_init(t);
 }
 // results of a group's windows into one device buffer (one copy back for the group instead of four per window): per window, at offs[4 w ..],
 // key frames | points | erase flags | control block
@@ -1086,10 +973,10 @@ bool host_inverse9(const double* a_in, double* inv) {
 }
 } // namespace
 
-// The Levenberg-Marquardt control flow of g2o (optimization_algorithm_levenberg.cpp:61-189) shared by both window solves:
-// optimize(5) -> gate / drop kernels -> optimize(10) -> erase flags. model 0: NavState window, 1: SE3 (vision-only) window.
-// The LM driver reads three scalars per trial: it polls the stream instead of blocking in hipStreamSynchronize (whose wake-up costs more
-// than the kernels of a trial take).
+// One window on the host: optimize(5) -> gate / drop kernels -> optimize(10) -> erase flags (reference src/Optimizer.cc:2100-2160 and the
+// vision-only twin; model 0: NavState window, 1: SE3 window). g2o's Levenberg loop itself (optimization_algorithm_levenberg.cpp:61-189)
+// runs on the device, in the window's control block; the host enqueues trial slots ahead of it and reads the block after each chunk. It
+// polls the stream instead of blocking in hipStreamSynchronize (whose wake-up costs more than the kernels of a trial take).
 struct BaSolve;
 static int ba_launch_pairs(const BaDev& D, hipStream_t st);      // the Schur complement's gather lists (k_ba_pairs_build, below)
 static void ba_mirror_stop_flags(BaSolve* const* S, int n);
@@ -1101,191 +988,84 @@ static hipError_t ba_wait(hipStream_t st, BaSolve* const* S = nullptr, int n = 0
         if (e != hipErrorNotReady) return e;
     }
 }
-// The LM driver (g2o's optimize(5) -> gate -> optimize(10), reference src/Optimizer.cc:2100-2160 and the vision-only twin) as a
-// resumable state machine: advance() runs the host logic up to the next point where device scalars are needed, enqueues the work on
-// the solve's stream and returns BA_WAIT; the caller resumes it once the stream has drained. One window blocks on its stream between
-// calls; a batch keeps several windows in flight from one host thread (several host threads slow each other down inside the HIP runtime).
-enum { BA_WAIT = 0, BA_DONE = 1, BA_PIN_ABORT = 56 };              // pinned[56]: the mirrored stop flag (a 64-bit word; 0..39 LM scalars, 48 the batch's done counter)
+// what a finished window's control block says about the solve
+static void ba_info_from_ctl(const double* c, double info[6]) {
+    info[0] = c[BA_B_CHI0]; info[1] = c[BA_B_CHI1]; info[2] = c[BA_B_ITS0]; info[3] = c[BA_B_ITS1];
+    info[4] = c[BA_CTL_TRIALS]; info[5] = c[BA_CTL_REJECTS];
+}
+enum { BA_PIN_CTL = 8, BA_PIN_ABORT = 56 };                        // pinned[8..39]: the single window's copy of its control block; [48]: the batch's done counter; [56]: the mirrored stop flag (a 64-bit word)
 struct BaSolve {
     StreamCtxLease lease;         // of the calling thread's current device: the caller has selected it (hipSetDevice(lba_device()))
-    BaDev D; hipStream_t st = nullptr; double* h = nullptr;       // h: 64 page-locked doubles (0..7 scal, 8..39 ctl)
+    BaDev D; hipStream_t st = nullptr; double* h = nullptr;       // h: 64 page-locked doubles
     int model = 0; const volatile int* stop = nullptr; uint8_t* d_erase = nullptr;
     double* kfs_out = nullptr; double* points_out = nullptr; uint8_t* erase = nullptr; double* info = nullptr;
-    // LM state
-    enum State { ST_OPT_BEGIN, ST_ITER_BEGIN, ST_AFTER_CHI, ST_AFTER_DIAG, ST_TRIAL_ENQ, ST_AFTER_TRIAL, ST_FINISH, ST_AFTER_FINAL, ST_DONE,
-                 ST_FAST_CHUNK, ST_FAST_WAIT } state = ST_OPT_BEGIN;
-    // Device-side LM control (k_ba_decide_body): iterations are enqueued FAST_CHUNK at a time with no host round trip in between (8 launches
-    // each, k_ba_f_*); the host looks at the control block once per chunk and only takes the per-trial path below after a trial was
-    // rejected. The caller's stop flag, which g2o polls once per iteration, is polled on the device through its page-locked mirror.
-    // VIORB_LBA_HOST_LM=1 forces the per-trial path (tests/test_gpu_local_ba.py holds it to the oracle as it does the default path).
-    enum { FAST_CHUNK = 10 };          // a whole optimize() call per round trip (5 and 10 iterations); the stop flag is polled on the device (k_ba_decide_body)
-    bool fast_phase = false; int fast_enq = 0;
-    int phase = 0, iterations = 5, it = 0, nBad = 0, qmax = 0, mono_kernel = 1;
-    int its[2] = {0, 0}; double chi[2] = {0, 0};
-    int ntrials[2] = {0, 0}, nrejects = 0;     // Levenberg trials per phase, rejected ones (info[4], info[5])
-    double lambda = 0, ni = 2, currentChi = 0, iniChi = 0, rho = 0;
+    enum State { ST_READY, ST_DONE } state = ST_READY;           // ST_DONE: the stop flag was up on entry, the outputs hold the inputs
     bool terminate() const { return stop && *stop; }
-    int advance() {
-        const int nk = D.NK, npts = D.NP, ne = D.NE, n_local = D.W;
+    // The single call. A slot is one Levenberg trial: 8 launches (k_ba_f_*), + k_ba_max_diag and k_ba_lambda0 on a phase's first. What a
+    // slot does (linearise first, or restore and retry, or nothing because the phase is over) the device decides (ba_slot), so the host
+    // enqueues as many slots as the phase has iterations left — all it needs when no trial is rejected — then reads the control block and
+    // enqueues more if the phase is not over. The caller's stop flag, which g2o polls once per iteration and once per trial, is polled
+    // here before every chunk and on the device after every trial, through its page-locked mirror.
+    int run() {
+        if (state == ST_DONE) return VIORB_OK;
+        VIORB_TRY(ba_launch_pairs(D, st));
+        const int npts = D.NP, ne = D.NE, n_local = D.W, TB = 256, gE = (ne + TB - 1) / TB, gP = (npts + TB - 1) / TB;
+        const int gL = model == 0 ? std::max(gE, gP) : std::max(gP, 1);        // the linearisation's blocks also carry the restore (one thread per point / local key frame)
         const size_t n2 = (size_t)D.np * D.np, nl2 = (size_t)D.ld * D.ld;
-        const int TB = 256, gE = (ne + TB - 1) / TB, gP = (npts + TB - 1) / TB;
-        auto enqueue_errors = [&]() -> int {
+        const unsigned gC = (unsigned)std::min<size_t>((n2 + TB - 1) / TB, 256), gR = (unsigned)((nl2 + TB - 1) / TB);
+        (void)raise_dynamic_lds(reinterpret_cast<const void*>(k_ba_chol_solve), BA_CHOL_LDS_BYTES);
+        BaSolve* self = this;
+        double* c = h + BA_PIN_CTL;
+        D.use_ctl = 1;
+        for (int t = 0; t < BA_B_N; t++) c[t] = lba_ctl_init(t);
+        hipLaunchKernelGGL(k_ba_ctl_init, dim3(1), dim3(64), 0, st, D);
+        do {
+            // an optimize() call: chi2 at the starting point (computeActiveErrors of the first iteration)
+            const int mono_kernel = c[BA_B_MONO] != 0.0;
             VIORB_HIP_TRY(hipMemsetAsync(D.scal, 0, sizeof(double), st));
             if (model == 0) hipLaunchKernelGGL(k_ba_errors, dim3(gE), dim3(TB), 0, st, D, mono_kernel);
             else hipLaunchKernelGGL(k_ba_se3_errors, dim3(gE), dim3(TB), 0, st, D, mono_kernel);
-            return VIORB_OK;
-        };
-        int rc;
-        for (;;) {
-            switch (state) {
-            case ST_OPT_BEGIN: {
-                it = 0; currentChi = 0; nBad = 0;
-                static const bool host_lm = getenv("VIORB_LBA_HOST_LM") != nullptr;
-                fast_phase = !host_lm;
-                D.use_ctl = 0;
-                if (!fast_phase) { state = ST_ITER_BEGIN; break; }
-                // chi2 at the phase's starting point (computeActiveErrors of the first iteration) and a clean control block
-                VIORB_HIP_TRY(hipMemsetAsync(D.ctl, 0, BA_CTL_N * sizeof(double), st));
-                if ((rc = enqueue_errors()) != VIORB_OK) return rc;
-                fast_enq = 0; state = ST_FAST_CHUNK;
-                break;
-            }
-            case ST_FAST_CHUNK: {
-                if (terminate() || fast_enq >= iterations) { state = ST_FINISH; break; }
-                D.use_ctl = 1;
-                const int n = std::min((int)FAST_CHUNK, iterations - fast_enq);
-                const unsigned gC = (unsigned)std::min<size_t>((n2 + TB - 1) / TB, 256);
-                for (int i = 0; i < n; i++, fast_enq++) {
-                    const int first = fast_enq == 0;
-                    const unsigned gR = (unsigned)((nl2 + TB - 1) / TB);
+            while (c[BA_B_GATE] == 0.0 && !terminate()) {
+                const double trials = c[BA_CTL_TRIALS];
+                const int n = std::max(1, (int)(c[BA_B_ITERS] - c[BA_CTL_IT]));
+                for (int i = 0; i < n; i++) {
                     if (model == 0) {
-                        hipLaunchKernelGGL(k_ba_f_line_clear, dim3(gE + gC), dim3(TB), 0, st, D, mono_kernel, first, (int)gE, (int)gC);
+                        hipLaunchKernelGGL(k_ba_f_line_clear, dim3(gL + gC), dim3(TB), 0, st, D, mono_kernel, gL, (int)gC);
                         hipLaunchKernelGGL(k_ba_f_hpp_imu_hll, dim3(2 * n_local + gP), dim3(256), 0, st, D);
                     } else {
-                        hipLaunchKernelGGL(k_ba_f_lin_clear, dim3(gP + gC), dim3(TB), 0, st, D, mono_kernel, first, (int)gP, (int)gC);
-                        hipLaunchKernelGGL(k_ba_f_hpp_imu, dim3(n_local), dim3(256), 0, st, D);
+                        hipLaunchKernelGGL(k_ba_f_lin_clear, dim3(gL + gC), dim3(TB), 0, st, D, mono_kernel, gL, (int)gC);
+                        hipLaunchKernelGGL(k_ba_f_hpp, dim3(n_local), dim3(256), 0, st, D);
                     }
-                    if (first) {
+                    if (i == 0 && c[BA_B_FIRST] != 0.0) {
                         hipLaunchKernelGGL(k_ba_max_diag, dim3(32), dim3(256), 0, st, D);
                         hipLaunchKernelGGL(k_ba_lambda0, dim3(1), dim3(64), 0, st, D);
                     }
                     hipLaunchKernelGGL(k_ba_f_init_dinv, dim3(gR + gP), dim3(TB), 0, st, D, (int)gR);
                     hipLaunchKernelGGL(k_ba_schur, dim3(n_local * (n_local + 1) / 2), dim3(64), 0, st, D);
-                    (void)raise_dynamic_lds(reinterpret_cast<const void*>(k_ba_chol_solve), BA_CHOL_LDS_BYTES);
                     hipLaunchKernelGGL(k_ba_chol_solve, dim3(1), dim3(BA_CHOL_THREADS), BA_CHOL_LDS_BYTES, st, D);
                     hipLaunchKernelGGL(k_ba_f_backsub8_update, dim3((unsigned)std::max((8 * npts + TB - 1) / TB, 1)), dim3(TB), 0, st, D);
-                    hipLaunchKernelGGL(k_ba_f_errors_decide, dim3(gE), dim3(TB), 0, st, D, mono_kernel, 0);
+                    hipLaunchKernelGGL(k_ba_f_errors_decide, dim3(gE), dim3(TB), 0, st, D, mono_kernel);
                 }
-                D.use_ctl = 0;
-                VIORB_HIP_TRY(hipMemcpyAsync(h, D.scal, 8 * sizeof(double), hipMemcpyDeviceToHost, st));
-                VIORB_HIP_TRY(hipMemcpyAsync(h + 8, D.ctl, BA_CTL_N * sizeof(double), hipMemcpyDeviceToHost, st));
-                state = ST_FAST_WAIT;
-                return BA_WAIT;
+                VIORB_HIP_TRY(hipGetLastError());
+                VIORB_HIP_TRY(hipMemcpyAsync(c, D.ctl, BA_B_N * sizeof(double), hipMemcpyDeviceToHost, st));
+                VIORB_HIP_TRY(ba_wait(st, &self, 1));
+                if (c[BA_B_GATE] == 0.0 && c[BA_CTL_TRIALS] == trials) { set_error("window solve: a chunk of trials took no decision"); return VIORB_ERR_HIP; }
             }
-            case ST_FAST_WAIT: {
-                const double* c = h + 8;
-                its[phase] = (int)c[BA_CTL_ITS]; chi[phase] = c[BA_CTL_CHI]; it = (int)c[BA_CTL_IT];
-                ntrials[phase] = its[phase];       // the device chunk: every iteration it finished was one accepted trial; the rejected one is counted below
-                currentChi = c[BA_CTL_CHI]; iniChi = c[BA_CTL_INICHI]; lambda = c[BA_CTL_LAMBDA]; ni = c[BA_CTL_NI]; nBad = (int)c[BA_CTL_NBAD];
-                const int halt = (int)c[BA_CTL_HALT];
-                if (halt == 1) { qmax = 0; rho = 0; fast_phase = false; state = ST_AFTER_TRIAL; break; }      // a rejected trial: h[0..2] hold its scalars
-                if (halt == 2 || it >= iterations) { state = ST_FINISH; break; }
-                state = ST_FAST_CHUNK;
-                break;
-            }
-            case ST_ITER_BEGIN:
-                if (it >= iterations || terminate()) { state = ST_FINISH; break; }
-                if ((rc = enqueue_errors()) != VIORB_OK) return rc;
-                VIORB_HIP_TRY(hipMemcpyAsync(h + 8, D.scal, sizeof(double), hipMemcpyDeviceToHost, st));
-                state = ST_AFTER_CHI;
-                return BA_WAIT;
-            case ST_AFTER_CHI:
-                currentChi = h[8]; iniChi = currentChi;
-                VIORB_HIP_TRY(hipMemsetAsync(D.Hpp, 0, n2 * sizeof(double), st));
-                VIORB_HIP_TRY(hipMemsetAsync(D.bp, 0, D.np * sizeof(double), st));
-                if (model == 0) hipLaunchKernelGGL(k_ba_lin_points, dim3(gP), dim3(TB), 0, st, D, mono_kernel);
-                else hipLaunchKernelGGL(k_ba_se3_lin_points, dim3(gP), dim3(TB), 0, st, D, mono_kernel);
-                hipLaunchKernelGGL(k_ba_hpp, dim3(n_local), dim3(256), 0, st, D);
-                if (model == 0) hipLaunchKernelGGL(k_ba_imu, dim3(n_local), dim3(256), 0, st, D);
-                rho = 0; qmax = 0;
-                if (it == 0) {
-                    VIORB_HIP_TRY(hipMemsetAsync(D.scal + 3, 0, sizeof(double), st));
-                    hipLaunchKernelGGL(k_ba_max_diag, dim3(32), dim3(256), 0, st, D);
-                    VIORB_HIP_TRY(hipMemcpyAsync(h, D.scal, 8 * sizeof(double), hipMemcpyDeviceToHost, st));
-                    state = ST_AFTER_DIAG;
-                    return BA_WAIT;
-                }
-                state = ST_TRIAL_ENQ;
-                break;
-            case ST_AFTER_DIAG:
-                lambda = lm_lambda_init(h[3]); ni = 2; nBad = 0; state = ST_TRIAL_ENQ;
-                break;
-            case ST_TRIAL_ENQ:
-                hipLaunchKernelGGL(k_ba_init_reduced, dim3((unsigned)((nl2 + TB - 1) / TB)), dim3(TB), 0, st, D, lambda);
-                hipLaunchKernelGGL(k_ba_dinv, dim3(gP), dim3(TB), 0, st, D, lambda);
-                hipLaunchKernelGGL(k_ba_schur, dim3(n_local * (n_local + 1) / 2), dim3(64), 0, st, D);
-                (void)raise_dynamic_lds(reinterpret_cast<const void*>(k_ba_chol_solve), BA_CHOL_LDS_BYTES);
-                    hipLaunchKernelGGL(k_ba_chol_solve, dim3(1), dim3(BA_CHOL_THREADS), BA_CHOL_LDS_BYTES, st, D);
-                hipLaunchKernelGGL(k_ba_backsub, dim3(gP), dim3(TB), 0, st, D, lambda);
-                if (model == 0) hipLaunchKernelGGL(k_ba_update, dim3(std::max(gP, 1)), dim3(TB), 0, st, D);
-                else hipLaunchKernelGGL(k_ba_se3_update, dim3(std::max(gP, 1)), dim3(TB), 0, st, D);
-                // chi2 of the trial state, the solver's flag and the gain denominator come back in one copy / one synchronisation
-                // (the factorisation kernel has zeroed both accumulators; the state backup is part of the update kernel)
-                if (model == 0) hipLaunchKernelGGL(k_ba_errors, dim3(gE), dim3(TB), 0, st, D, mono_kernel);
-                else hipLaunchKernelGGL(k_ba_se3_errors, dim3(gE), dim3(TB), 0, st, D, mono_kernel);
-                VIORB_HIP_TRY(hipMemcpyAsync(h, D.scal, 8 * sizeof(double), hipMemcpyDeviceToHost, st));
-                state = ST_AFTER_TRIAL;
-                return BA_WAIT;
-            case ST_AFTER_TRIAL: {
-                const bool ok2 = h[2] > 0.5;
-                const double tempChi = lm_trial_chi2(ok2, h[0]);
-                rho = lm_rho(currentChi, tempChi, ok2 ? h[1] : 0.0);
-                ntrials[phase]++;
-                if (lm_accepted(rho, tempChi)) { lm_good_step(lambda, ni, lm_cube_pow(2 * rho - 1)); currentChi = tempChi; }
-                else {
-                    lm_bad_step(lambda, ni); nrejects++;
-                    hipLaunchKernelGGL(k_ba_restore, dim3(std::max(gP, 1)), dim3(TB), 0, st, D);
-                }
-                qmax++;
-                if (lm_retry(rho, qmax) && !terminate()) { state = ST_TRIAL_ENQ; break; }
-                its[phase]++; chi[phase] = currentChi;
-                it++;
-                if (lm_iteration_stops(rho, qmax, iniChi, currentChi, nBad)) it = iterations;    // leaves the iteration loop through ST_ITER_BEGIN
-                state = ST_ITER_BEGIN;
-                break;
-            }
-            case ST_FINISH:
-                if (phase == 0 && !terminate()) {
-                    if (model == 0) hipLaunchKernelGGL(k_ba_gate, dim3(gE), dim3(TB), 0, st, D, d_erase, 1);
-                    else hipLaunchKernelGGL(k_ba_se3_gate, dim3(gE), dim3(TB), 0, st, D, d_erase, 1);
-                    mono_kernel = 0; phase = 1; iterations = 10; state = ST_OPT_BEGIN;
-                    break;
-                }
-                if (model == 0) hipLaunchKernelGGL(k_ba_gate, dim3(gE), dim3(TB), 0, st, D, d_erase, 0);
-                else hipLaunchKernelGGL(k_ba_se3_gate, dim3(gE), dim3(TB), 0, st, D, d_erase, 0);
-                VIORB_HIP_TRY(hipMemcpyAsync(kfs_out, D.kf, (size_t)n_local * D.kf_stride * sizeof(double), hipMemcpyDeviceToHost, st));
-                VIORB_HIP_TRY(hipMemcpyAsync(points_out, D.pt, (size_t)npts * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-                VIORB_HIP_TRY(hipMemcpyAsync(erase, d_erase, ne, hipMemcpyDeviceToHost, st));
-                state = ST_AFTER_FINAL;
-                return BA_WAIT;
-            case ST_AFTER_FINAL:
-                info[0] = chi[0]; info[1] = chi[1]; info[2] = its[0]; info[3] = its[1]; info[4] = ntrials[0] + ntrials[1]; info[5] = nrejects;
-                state = ST_DONE;
-                return BA_DONE;
-            case ST_DONE:
-                return BA_DONE;
-            }
-        }
-    }
-    // one window: block on the stream between the steps
-    int run() {
-        if (state != ST_DONE) { const int rc = ba_launch_pairs(D, st); if (rc != VIORB_OK) return rc; }
-        for (;;) {
-            const int r = advance();
-            if (r < 0 || r == BA_DONE) return r < 0 ? r : VIORB_OK;
-            BaSolve* self = this;
-            VIORB_HIP_TRY(ba_wait(st, &self, 1));
-        }
+            // a trial rejected at the very end is undone before the gate, which then sees that trial's errors beside the restored estimate
+            if (c[BA_B_RESTORE] != 0.0) hipLaunchKernelGGL(k_ba_restore, dim3(std::max(gP, 1)), dim3(TB), 0, st, D);
+            if (terminate()) c[BA_B_GATE] = 2.0;                   // "&& !terminate()": no second optimize(), final gate on the state as it is
+            const int set_level = c[BA_B_GATE] == 1.0;            // after the first optimize() the gate drops edges; after the last it writes the erase flags
+            if (model == 0) hipLaunchKernelGGL(k_ba_gate, dim3(gE), dim3(TB), 0, st, D, d_erase, set_level);
+            else hipLaunchKernelGGL(k_ba_se3_gate, dim3(gE), dim3(TB), 0, st, D, d_erase, set_level);
+            if (set_level) hipLaunchKernelGGL(k_ba_phase, dim3(1), dim3(64), 0, st, D);      // the second optimize(): the device's block and the host's copy take the same step
+        } while (!lba_phase(c));
+        VIORB_HIP_TRY(hipMemcpyAsync(kfs_out, D.kf, (size_t)n_local * D.kf_stride * sizeof(double), hipMemcpyDeviceToHost, st));
+        VIORB_HIP_TRY(hipMemcpyAsync(points_out, D.pt, (size_t)npts * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        VIORB_HIP_TRY(hipMemcpyAsync(erase, d_erase, ne, hipMemcpyDeviceToHost, st));
+        VIORB_HIP_TRY(ba_wait(st, &self, 1));
+        ba_info_from_ctl(c, info);
+        state = ST_DONE;
+        return VIORB_OK;
     }
 };
 
@@ -1360,7 +1140,7 @@ static size_t ba_pairs_bound(const std::vector<int>& e_kf, const std::vector<int
     return tot;
 }
 
-// Argument checks, host-side graph bookkeeping and the upload of one NavState window; leaves `S` ready for advance() (or already done
+// Argument checks, host-side graph bookkeeping and the upload of one NavState window; leaves `S` ready for BaSolve::run() or a lock-step group (or already done
 // when the stop flag was set on entry).
 static int ba_prepare_navstate(BaSolve& S, const double* kfs, int nk, int n_local, int prev_kf, const double* preint, const double* points, int npts,
                                const int32_t* edge_idx, const double* edge_obs, int ne, const double gw[3], const double cam[16],
@@ -1434,54 +1214,6 @@ extern "C" int viorb_local_ba_navstate(const double* kfs, int nk, int n_local, i
     BaSolve S;
     const int rc = ba_prepare_navstate(S, kfs, nk, n_local, prev_kf, preint, points, npts, edge_idx, edge_obs, ne, gw, cam, stop, kfs_out, points_out, erase, info);
     return rc != VIORB_OK ? rc : S.run();
-}
-
-// One host thread keeps up to max_in_flight windows going, each on its own stream: whenever a window's stream has drained, its driver
-// takes the next LM decision and enqueues the next batch of kernels. prepare(i, S) fills window i's solve and returns its status.
-template <class Prepare, class SetStatus>
-static int ba_run_batch(int n, int max_in_flight, Prepare prepare, SetStatus set_status) {
-    VIORB_TRY(require_device());
-    if (max_in_flight <= 0) max_in_flight = 16;
-    VIORB_HIP_TRY(hipSetDevice(lba_device()));
-    std::vector<std::unique_ptr<BaSolve>> live(std::min(max_in_flight, std::max(n, 1)));
-    std::vector<int> which(live.size(), -1);
-    int next = 0, finished = 0, first_error = VIORB_OK;
-    auto start_next = [&](size_t slot) {
-        while (next < n) {
-            const int i = next++;
-            auto S = std::make_unique<BaSolve>();
-            int status = prepare(i, *S);
-            if (status == VIORB_OK && S->state != BaSolve::ST_DONE) status = ba_launch_pairs(S->D, S->st);
-            if (status == VIORB_OK && S->state != BaSolve::ST_DONE) {
-                const int r = S->advance();                      // first batch of work
-                if (r == BA_WAIT) { live[slot] = std::move(S); which[slot] = i; return; }
-                status = r < 0 ? r : VIORB_OK;
-            }
-            set_status(i, status);
-            if (status != VIORB_OK && first_error == VIORB_OK) first_error = status;
-            finished++;
-        }
-        live[slot].reset(); which[slot] = -1;
-    };
-    for (size_t k = 0; k < live.size(); k++) start_next(k);
-    while (finished < n) {
-        bool progressed = false;
-        for (size_t k = 0; k < live.size(); k++) {
-            if (!live[k]) continue;
-            const hipError_t e = hipStreamQuery(live[k]->st);
-            if (e == hipErrorNotReady) continue;
-            progressed = true;
-            const int r = e == hipSuccess ? live[k]->advance() : VIORB_ERR_HIP;
-            if (e != hipSuccess) set_error("hipStreamQuery failed: %s", hipGetErrorString(e));
-            if (r == BA_WAIT) continue;
-            set_status(which[k], r < 0 ? r : VIORB_OK);
-            if (r < 0 && first_error == VIORB_OK) first_error = r;
-            finished++;
-            start_next(k);
-        }
-        if (!progressed) for (volatile int spin = 0; spin < 200; spin = spin + 1) {}
-    }
-    return first_error;
 }
 
 // Lock-step batch of NavState windows (kernels k_bab_*): returns the first error; every window's status through set_status.
@@ -1641,10 +1373,7 @@ static int ba_run_lockstep(Win* w, int n, int max_in_flight, Prepare prepare) {
                 memcpy(B.kfs_out, hb + offs[4 * a], (size_t)B.D.W * B.D.kf_stride * sizeof(double));
                 memcpy(B.points_out, hb + offs[4 * a + 1], (size_t)B.D.NP * 3 * sizeof(double));
                 memcpy(B.erase, hb + offs[4 * a + 2], (size_t)B.D.NE);
-                const double* c = reinterpret_cast<const double*>(hb + offs[4 * a + 3]);
-                double* info = B.info;
-                info[0] = c[BA_B_CHI0]; info[1] = c[BA_B_CHI1]; info[2] = c[BA_B_ITS0]; info[3] = c[BA_B_ITS1];
-                info[4] = c[BA_CTL_TRIALS]; info[5] = c[BA_CTL_REJECTS];
+                ba_info_from_ctl(reinterpret_cast<const double*>(hb + offs[4 * a + 3]), B.info);
             }
         }
         return VIORB_OK;
@@ -1661,18 +1390,10 @@ static int ba_run_lockstep(Win* w, int n, int max_in_flight, Prepare prepare) {
 
 extern "C" int viorb_local_ba_navstate_batch(viorb_lba_window* w, int n, int max_in_flight) {
     VIORB_REQUIRE(w && n >= 0, "null windows");
-    static const bool per_stream = getenv("VIORB_LBA_STREAMS") != nullptr;      // the round-1 driver: one stream and host LM loop per window
-    if (!per_stream) return ba_run_lockstep(w, n, max_in_flight, [](BaSolve& S, viorb_lba_window& q) {
+    return ba_run_lockstep(w, n, max_in_flight, [](BaSolve& S, viorb_lba_window& q) {
         return ba_prepare_navstate(S, q.kfs, q.nk, q.n_local, q.prev_kf, q.preint, q.points, q.np, q.edge_idx, q.edge_obs, q.ne, q.gw, q.cam, q.stop,
                                    q.kfs_out, q.points_out, q.erase, q.info);
     });
-    return ba_run_batch(n, max_in_flight,
-        [&](int i, BaSolve& S) {
-            viorb_lba_window& q = w[i];
-            return ba_prepare_navstate(S, q.kfs, q.nk, q.n_local, q.prev_kf, q.preint, q.points, q.np, q.edge_idx, q.edge_obs, q.ne, q.gw, q.cam, q.stop,
-                                       q.kfs_out, q.points_out, q.erase, q.info);
-        },
-        [&](int i, int status) { w[i].status = status; });
 }
 
 static int ba_prepare_se3(BaSolve& S, const double* kfs, int nk, int n_local, const double* points, int npts, const int32_t* edge_idx,
@@ -1738,14 +1459,7 @@ extern "C" int viorb_local_ba_se3(const double* kfs, int nk, int n_local, const 
 
 extern "C" int viorb_local_ba_se3_batch(viorb_lba_se3_window* w, int n, int max_in_flight) {
     VIORB_REQUIRE(w && n >= 0, "null windows");
-    static const bool per_stream = getenv("VIORB_LBA_STREAMS") != nullptr;      // the round-1 driver: one stream and host LM loop per window
-    if (!per_stream) return ba_run_lockstep(w, n, max_in_flight, [](BaSolve& S, viorb_lba_se3_window& q) {
+    return ba_run_lockstep(w, n, max_in_flight, [](BaSolve& S, viorb_lba_se3_window& q) {
         return ba_prepare_se3(S, q.kfs, q.nk, q.n_local, q.points, q.np, q.edge_idx, q.edge_obs, q.ne, q.intr5, q.stop, q.kfs_out, q.points_out, q.erase, q.info);
     });
-    return ba_run_batch(n, max_in_flight,
-        [&](int i, BaSolve& S) {
-            viorb_lba_se3_window& q = w[i];
-            return ba_prepare_se3(S, q.kfs, q.nk, q.n_local, q.points, q.np, q.edge_idx, q.edge_obs, q.ne, q.intr5, q.stop, q.kfs_out, q.points_out, q.erase, q.info);
-        },
-        [&](int i, int status) { w[i].status = status; });
 }
