@@ -942,6 +942,10 @@ int viorb_debug_gba_last_trials(uint8_t* accepted, int cap, int* n);
  * factorisation, in a header of its own. */
 #include "viorb_essential_graph.h"
 
+/* The map correction before that solve (the propagation of LoopClosing::CorrectLoop over the current key frame's covisibles: both Sim3
+ * tables, the corrected points with their normals, the corrected poses), in a header of its own. */
+#include "viorb_map_correction.h"
+
 /* The two culling routines of the mapping thread (LocalMapping::KeyFrameCulling, ordered and exact, and LocalMapping::MapPointCulling),
  * in a header of their own. */
 #include "viorb_culling.h"

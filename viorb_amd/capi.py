@@ -2,7 +2,7 @@
 declared entry point of viorb.h is exported, has a signature here and that the argument counts agree; tests/test_global_ba_se3_ref.py
 does the same for SIGNATURES_GLOBAL_BA_SE3, tests/test_two_view_ref.py for SIGNATURES_TWO_VIEW, tests/test_sim3_ref.py for SIGNATURES_SIM3,
 tests/test_sim3_match_ref.py for SIGNATURES_SIM3_MATCH, tests/test_kf_culling_ref.py for SIGNATURES_CULLING, tests/test_reloc_ref.py for
-SIGNATURES_RELOCALIZATION, tests/test_local_map_ref.py for SIGNATURES_LOCAL_MAP, tests/test_covis_ref.py for SIGNATURES_COVISIBILITY)."""
+SIGNATURES_RELOCALIZATION, tests/test_local_map_ref.py for SIGNATURES_LOCAL_MAP, tests/test_covis_ref.py for SIGNATURES_COVISIBILITY, tests/test_map_correction_ref.py for SIGNATURES_MAP_CORRECTION)."""
 import ctypes as C
 import os
 import numpy as np
@@ -206,6 +206,39 @@ class CovisMap(C.Structure):
 class CovisResult(C.Structure):
     """viorb_covis_result (include/viorb_covisibility.h)."""
     _fields_ = [(n, C.c_void_p) for n in COVIS_RESULT_FIELDS]
+
+
+CORRECT_LOOP_INTS = ("batch", "n_kf", "n_kp", "n_pt", "n_obs", "n_conn")
+CORRECT_LOOP_ARRAYS = ("kf_start", "kf_by_key", "kp_start", "kp_point", "pt_start", "pt_bad", "obs_start", "obs", "pose12", "pts_f", "pt_ref",
+                       "pt_corrected_by", "cur_kf", "cur_id", "Scw8", "conn_start", "conn_kf")
+CORRECT_LOOP_RESULT_FIELDS = ("status", "n_member", "member_kf", "Scw_f12", "Scw_out", "Smeas_out", "pose12_out", "Ow_out", "pts_f_out",
+                              "pt_corrected_by_out", "pt_corrected_ref_out", "pt_touched")
+
+
+APPLY_GBA_INTS = ("batch", "n_kf", "n_child", "n_origin", "n_pt")
+APPLY_GBA_ARRAYS = ("kf_start", "child_start", "child_kf", "origin_start", "origin_kf", "kf_in_gba", "pose12", "TcwGBA12", "ns22", "nsGBA22",
+                    "pt_start", "pt_bad", "pt_in_gba", "Pw", "PosGBA", "pt_ref")
+APPLY_GBA_RESULT_FIELDS = ("status", "pose12_out", "ns22_out", "TcwBef_out", "nsBef_out", "TcwGBA_out", "nsGBA_out", "kf_in_gba_out", "kf_reached", "Pw_out", "pt_code")
+
+
+class ApplyGbaMap(C.Structure):
+    """viorb_apply_gba_map (include/viorb_map_correction.h)."""
+    _fields_ = [(n, C.c_int32) for n in APPLY_GBA_INTS] + [(n, C.c_void_p) for n in APPLY_GBA_ARRAYS]
+
+
+class ApplyGbaResult(C.Structure):
+    """viorb_apply_gba_result (include/viorb_map_correction.h)."""
+    _fields_ = [(n, C.c_void_p) for n in APPLY_GBA_RESULT_FIELDS]
+
+
+class CorrectLoopMap(C.Structure):
+    """viorb_correct_loop_map (include/viorb_map_correction.h)."""
+    _fields_ = [(n, C.c_int32) for n in CORRECT_LOOP_INTS] + [(n, C.c_void_p) for n in CORRECT_LOOP_ARRAYS]
+
+
+class CorrectLoopResult(C.Structure):
+    """viorb_correct_loop_result (include/viorb_map_correction.h)."""
+    _fields_ = [(n, C.c_void_p) for n in CORRECT_LOOP_RESULT_FIELDS]
 
 
 class TrackerConfig(C.Structure):
@@ -523,6 +556,21 @@ SIGNATURES_COVISIBILITY = {
     "viorb_debug_update_connections_host": (i32, [PP(CovisMap), PP(CovisResult), i32, i32]),
 }
 
+# mirrors include/viorb_map_correction.h (the propagation of LoopClosing::CorrectLoop); tests/test_map_correction_ref.py checks names and
+# argument counts against it
+SIGNATURES_MAP_CORRECTION = {
+    "viorb_correct_loop_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "viorb_correct_loop_device": (i32, [PP(CorrectLoopMap), PP(MappingCamera), PP(CorrectLoopResult), vp, sz, vp]),
+    "viorb_correct_loop": (i32, [PP(CorrectLoopMap), PP(MappingCamera), PP(CorrectLoopResult)]),
+    "viorb_correct_loop_shape": (i32, [vp]),
+    "viorb_debug_correct_loop_host": (i32, [PP(CorrectLoopMap), PP(MappingCamera), PP(CorrectLoopResult)]),
+    "viorb_apply_global_ba_workspace_bytes": (sz, [i32, i32]),
+    "viorb_apply_global_ba_device": (i32, [PP(ApplyGbaMap), vp, PP(ApplyGbaResult), vp, sz, vp]),
+    "viorb_apply_global_ba": (i32, [PP(ApplyGbaMap), vp, PP(ApplyGbaResult)]),
+    "viorb_apply_global_ba_shape": (i32, [vp]),
+    "viorb_debug_apply_global_ba_host": (i32, [PP(ApplyGbaMap), vp, PP(ApplyGbaResult)]),
+}
+
 _lib = None
 
 
@@ -545,7 +593,7 @@ def lib():
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GLOBAL_BA_SE3.items()) + list(SIGNATURES_TWO_VIEW.items()) \
                 + list(SIGNATURES_SIM3.items()) + list(SIGNATURES_SIM3_MATCH.items()) + list(SIGNATURES_ESSENTIAL_GRAPH.items()) \
                 + list(SIGNATURES_SEARCH_INIT.items()) + list(SIGNATURES_CULLING.items()) + list(SIGNATURES_RELOCALIZATION.items()) \
-                + list(SIGNATURES_LOCAL_MAP.items()) + list(SIGNATURES_COVISIBILITY.items()):
+                + list(SIGNATURES_LOCAL_MAP.items()) + list(SIGNATURES_COVISIBILITY.items()) + list(SIGNATURES_MAP_CORRECTION.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
