@@ -958,6 +958,10 @@ int viorb_debug_gba_last_trials(uint8_t* accepted, int cap, int* n);
  * exact, and the LoopConnections of LoopClosing::CorrectLoop), in a header of its own. */
 #include "viorb_covisibility.h"
 
+/* A key frame leaves the map (KeyFrame::SetBadFlag and SetErase with EraseConnection, EraseObservation, the spanning tree, mTcp and the
+ * links, for ordered operations), between the culling and the covisibility graph, in a header of its own. */
+#include "viorb_kf_removal.h"
+
 /* Relocalisation after the PnP hypothesis (Tracking::Relocalization): the key-frame projection search
  * ORBmatcher::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) and the solve / search / solve cascade, in a header of
  * their own. */

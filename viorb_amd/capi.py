@@ -2,7 +2,8 @@
 declared entry point of viorb.h is exported, has a signature here and that the argument counts agree; tests/test_global_ba_se3_ref.py
 does the same for SIGNATURES_GLOBAL_BA_SE3, tests/test_two_view_ref.py for SIGNATURES_TWO_VIEW, tests/test_sim3_ref.py for SIGNATURES_SIM3,
 tests/test_sim3_match_ref.py for SIGNATURES_SIM3_MATCH, tests/test_kf_culling_ref.py for SIGNATURES_CULLING, tests/test_reloc_ref.py for
-SIGNATURES_RELOCALIZATION, tests/test_local_map_ref.py for SIGNATURES_LOCAL_MAP, tests/test_covis_ref.py for SIGNATURES_COVISIBILITY, tests/test_map_correction_ref.py for SIGNATURES_MAP_CORRECTION)."""
+SIGNATURES_RELOCALIZATION, tests/test_local_map_ref.py for SIGNATURES_LOCAL_MAP, tests/test_covis_ref.py for SIGNATURES_COVISIBILITY, tests/test_map_correction_ref.py for SIGNATURES_MAP_CORRECTION,
+tests/test_kf_removal_ref.py for SIGNATURES_KF_REMOVAL)."""
 import ctypes as C
 import os
 import numpy as np
@@ -206,6 +207,26 @@ class CovisMap(C.Structure):
 class CovisResult(C.Structure):
     """viorb_covis_result (include/viorb_covisibility.h)."""
     _fields_ = [(n, C.c_void_p) for n in COVIS_RESULT_FIELDS]
+
+
+KFR_INTS = ("batch", "n_kf", "n_kp", "n_pt", "n_obs", "n_conn", "n_ord", "n_op")
+KFR_ARRAYS = ("kf_start", "kf_by_key", "kf_flags", "kf_parent", "kf_prev", "kf_next", "kf_pose12", "kp_start", "kp_point",
+              "pt_start", "pt_bad", "pt_nobs", "pt_ref", "obs_start", "obs", "conn_start", "conn_kf", "conn_w", "ord_start", "ord_kf", "ord_w",
+              "op_start", "op_kf", "op_kind")
+KFR_RESULT_REQUIRED = COVIS_RESULT_REQUIRED
+KFR_RESULT_FIELDS = KFR_RESULT_REQUIRED + ("kf_parent_out", "kf_flags_out", "kf_prev_out", "kf_next_out", "kf_repreint", "kf_Tcp_out", "kf_touched",
+                                           "pt_nobs_out", "pt_bad_out", "obs_alive", "pt_ref_out", "kp_point_out",
+                                           "op_reason", "op_children", "op_fallback", "op_rebuilt", "op_points_bad")
+
+
+class KfrMap(C.Structure):
+    """viorb_kfr_map (include/viorb_kf_removal.h)."""
+    _fields_ = [(n, C.c_int32) for n in KFR_INTS] + [(n, C.c_void_p) for n in KFR_ARRAYS]
+
+
+class KfrResult(C.Structure):
+    """viorb_kfr_result (include/viorb_kf_removal.h)."""
+    _fields_ = [(n, C.c_void_p) for n in KFR_RESULT_FIELDS]
 
 
 CORRECT_LOOP_INTS = ("batch", "n_kf", "n_kp", "n_pt", "n_obs", "n_conn")
@@ -571,6 +592,16 @@ SIGNATURES_MAP_CORRECTION = {
     "viorb_debug_apply_global_ba_host": (i32, [PP(ApplyGbaMap), vp, PP(ApplyGbaResult)]),
 }
 
+# mirrors include/viorb_kf_removal.h (KeyFrame::SetBadFlag / SetErase for ordered operations); tests/test_kf_removal_ref.py checks names
+# and argument counts against it
+SIGNATURES_KF_REMOVAL = {
+    "viorb_remove_key_frames_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "viorb_remove_key_frames_device": (i32, [PP(KfrMap), PP(KfrResult), i32, vp, sz, vp]),
+    "viorb_remove_key_frames": (i32, [PP(KfrMap), PP(KfrResult), i32]),
+    "viorb_remove_key_frames_shape": (i32, [vp]),
+    "viorb_debug_remove_key_frames_host": (i32, [PP(KfrMap), PP(KfrResult), i32]),
+}
+
 _lib = None
 
 
@@ -593,7 +624,8 @@ def lib():
         for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_GLOBAL_BA_SE3.items()) + list(SIGNATURES_TWO_VIEW.items()) \
                 + list(SIGNATURES_SIM3.items()) + list(SIGNATURES_SIM3_MATCH.items()) + list(SIGNATURES_ESSENTIAL_GRAPH.items()) \
                 + list(SIGNATURES_SEARCH_INIT.items()) + list(SIGNATURES_CULLING.items()) + list(SIGNATURES_RELOCALIZATION.items()) \
-                + list(SIGNATURES_LOCAL_MAP.items()) + list(SIGNATURES_COVISIBILITY.items()) + list(SIGNATURES_MAP_CORRECTION.items()):
+                + list(SIGNATURES_LOCAL_MAP.items()) + list(SIGNATURES_COVISIBILITY.items()) + list(SIGNATURES_MAP_CORRECTION.items()) \
+                + list(SIGNATURES_KF_REMOVAL.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -156,6 +156,20 @@ VIORB_HD bool cov_is_added(const int32_t* cinfo, int k, int w) { return w >= COV
 // Rows are in ascending key, so a higher position is a higher key: descending weight, then descending key.
 VIORB_HD bool cov_before(int wj, int j, int wi, int i) { return wj > wi || (wj == wi && j > i); }
 
+// ---- UpdateBestCovisibles (:429-448): the ordered list (ok_, ow) of a key frame from its whole map (ck, cw) of n entries -----------------
+// The rank sort of the share of `lane` of `nl`; old_n: the list's length before, -1 goes behind the new end. Also kf_removal_core.h's.
+VIORB_HD void cov_rebuild_ordered(const int32_t* ck, const int32_t* cw, int32_t* ok_, int32_t* ow, int n, int old_n, int lane, int nl) {
+    for (int i0 = 0; i0 < n; i0 += nl) {
+        const int i = i0 + lane;
+        if (i >= n) continue;
+        const int wi = snap_ld_wg(&cw[i]);
+        int before = 0;
+        for (int j = 0; j < n; j++) before += cov_before(snap_ld_wg(&cw[j]), j, wi, i) ? 1 : 0;
+        snap_st_wg(&ok_[before], snap_ld_wg(&ck[i])); snap_st_wg(&ow[before], wi);
+    }
+    for (int i = n + lane; i < old_n; i += nl) { snap_st_wg(&ok_[i], -1); snap_st_wg(&ow[i], -1); }
+}
+
 // ---- AddConnection (:414-427) with UpdateBestCovisibles (:429-448): key frame x learns weight w for target kt ---------------------------
 // Run by `nl` lanes in step (the device: one wavefront; the host: lane 0 of 1); Wave::sum and Wave::any combine a value over them. The
 // row's words go through snap_ld_wg / snap_st_wg, with a fence between a lane's write and another lane's read. Returns 0 for the early
@@ -191,15 +205,7 @@ VIORB_HD int cov_add_connection(const CovMap& M, const SnapStream& S, const CovO
     }
     snap_fence_wg();
     const int old_n = snap_ld_wg(&R.ord_n_out[g]);
-    for (int i0 = 0; i0 < n; i0 += nl) {                                                         // the rank sort of the whole map
-        const int i = i0 + lane;
-        if (i >= n) continue;
-        const int wi = snap_ld_wg(&cw[i]);
-        int before = 0;
-        for (int j = 0; j < n; j++) before += cov_before(snap_ld_wg(&cw[j]), j, wi, i) ? 1 : 0;
-        snap_st_wg(&ok_[before], snap_ld_wg(&ck[i])); snap_st_wg(&ow[before], wi);
-    }
-    for (int i = n + lane; i < old_n; i += nl) { snap_st_wg(&ok_[i], -1); snap_st_wg(&ow[i], -1); }
+    cov_rebuild_ordered(ck, cw, ok_, ow, n, old_n, lane, nl);                                    // the rank sort of the whole map
     if (lane == 0) {
         snap_st_wg(&R.ord_n_out[g], n);
         if (R.kf_touched) R.kf_touched[g] |= COV_MAP_CHANGED | COV_ORD_REBUILT;
