@@ -962,6 +962,11 @@ int viorb_debug_gba_last_trials(uint8_t* accepted, int cap, int* n);
  * links, for ordered operations), between the culling and the covisibility graph, in a header of its own. */
 #include "viorb_kf_removal.h"
 
+/* The results of the fuse searches applied to the map (the replace / add block of both ORBmatcher::Fuse, the Replace loop of
+ * LoopClosing::SearchAndFuse and MapPoint::Replace, for ordered calls), between the searches and the point update / the covisibility
+ * graph, in a header of its own. */
+#include "viorb_map_fusion.h"
+
 /* Relocalisation after the PnP hypothesis (Tracking::Relocalization): the key-frame projection search
  * ORBmatcher::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) and the solve / search / solve cascade, in a header of
  * their own. */

@@ -20,6 +20,7 @@ from .culling import CullBatch, key_frame_culling, map_point_culling, map_point_
 from .local_map import LocalMapBatch, update_local_map  # noqa: F401
 from .covisibility import CovisBatch, update_connections  # noqa: F401
 from .kf_removal import KfRemovalBatch, remove_key_frames  # noqa: F401
+from .map_fusion import FuseBatch, apply_fuse  # noqa: F401
 from .map_correction import CorrectLoopBatch, correct_loop, ApplyGbaBatch, apply_global_ba  # noqa: F401
 from .essential_graph import OptimizeEssentialGraph, OptimizeEssentialGraphDevice, essential_graph_workspace_bytes  # noqa: F401
 from .sim3 import draw_sets as sim3_draw_sets  # noqa: F401  (draw_sets is the two-view initialiser's)

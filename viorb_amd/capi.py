@@ -3,7 +3,7 @@ declared entry point of viorb.h is exported, has a signature here and that the a
 does the same for SIGNATURES_GLOBAL_BA_SE3, tests/test_two_view_ref.py for SIGNATURES_TWO_VIEW, tests/test_sim3_ref.py for SIGNATURES_SIM3,
 tests/test_sim3_match_ref.py for SIGNATURES_SIM3_MATCH, tests/test_kf_culling_ref.py for SIGNATURES_CULLING, tests/test_reloc_ref.py for
 SIGNATURES_RELOCALIZATION, tests/test_local_map_ref.py for SIGNATURES_LOCAL_MAP, tests/test_covis_ref.py for SIGNATURES_COVISIBILITY, tests/test_map_correction_ref.py for SIGNATURES_MAP_CORRECTION,
-tests/test_kf_removal_ref.py for SIGNATURES_KF_REMOVAL)."""
+tests/test_kf_removal_ref.py for SIGNATURES_KF_REMOVAL, tests/test_map_fusion_ref.py for SIGNATURES_MAP_FUSION)."""
 import ctypes as C
 import os
 import numpy as np
@@ -227,6 +227,25 @@ class KfrMap(C.Structure):
 class KfrResult(C.Structure):
     """viorb_kfr_result (include/viorb_kf_removal.h)."""
     _fields_ = [(n, C.c_void_p) for n in KFR_RESULT_FIELDS]
+
+
+FUSE_INTS = ("batch", "n_kf", "n_kp", "n_pt", "n_obs", "n_call", "n_list", "n_feat", "n_op", "n_obs_out")
+FUSE_ARRAYS = ("kf_start", "kf_by_key", "kf_bad", "kp_start", "kp_point", "kp_octave", "kp_stereo", "pt_start", "pt_bad", "pt_nobs", "pt_found", "pt_visible",
+               "obs_start", "obs", "obs_feat", "call_start", "call_kf", "call_kind", "call_list", "call_n", "call_feat", "call_op",
+               "list_point", "op_feat", "obs_out_start")
+FUSE_RESULT_REQUIRED = ("status", "kp_point_out", "pt_bad_out", "pt_nobs_out", "obs_start_out", "obs_out", "obs_feat_out")
+FUSE_RESULT_FIELDS = FUSE_RESULT_REQUIRED + ("need", "pt_found_out", "pt_visible_out", "pt_replaced_out", "pt_dirty", "obs_touched",
+                                             "dirty_obs_start", "dirty_obs_kf", "dirty_obs_feat", "op_reason", "op_other", "call_nfused")
+
+
+class FuseMap(C.Structure):
+    """viorb_fuse_map (include/viorb_map_fusion.h)."""
+    _fields_ = [(n, C.c_int32) for n in FUSE_INTS] + [(n, C.c_void_p) for n in FUSE_ARRAYS]
+
+
+class FuseResult(C.Structure):
+    """viorb_fuse_result (include/viorb_map_fusion.h)."""
+    _fields_ = [(n, C.c_void_p) for n in FUSE_RESULT_FIELDS]
 
 
 CORRECT_LOOP_INTS = ("batch", "n_kf", "n_kp", "n_pt", "n_obs", "n_conn")
@@ -602,6 +621,17 @@ SIGNATURES_KF_REMOVAL = {
     "viorb_debug_remove_key_frames_host": (i32, [PP(KfrMap), PP(KfrResult), i32]),
 }
 
+# mirrors include/viorb_map_fusion.h (the fuse searches' results applied to the map); tests/test_map_fusion_ref.py checks names and
+# argument counts against it
+SIGNATURES_MAP_FUSION = {
+    "viorb_apply_fuse_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "viorb_apply_fuse_device": (i32, [PP(FuseMap), PP(FuseResult), vp, sz, vp]),
+    "viorb_apply_fuse": (i32, [PP(FuseMap), PP(FuseResult)]),
+    "viorb_apply_fuse_shape": (i32, [vp]),
+    "viorb_fuse_merge_descriptors_device": (i32, [vp, vp, vp, vp, i32, vp]),
+    "viorb_debug_apply_fuse_host": (i32, [PP(FuseMap), PP(FuseResult)]),
+}
+
 _lib = None
 
 
@@ -625,7 +655,7 @@ def lib():
                 + list(SIGNATURES_SIM3.items()) + list(SIGNATURES_SIM3_MATCH.items()) + list(SIGNATURES_ESSENTIAL_GRAPH.items()) \
                 + list(SIGNATURES_SEARCH_INIT.items()) + list(SIGNATURES_CULLING.items()) + list(SIGNATURES_RELOCALIZATION.items()) \
                 + list(SIGNATURES_LOCAL_MAP.items()) + list(SIGNATURES_COVISIBILITY.items()) + list(SIGNATURES_MAP_CORRECTION.items()) \
-                + list(SIGNATURES_KF_REMOVAL.items()):
+                + list(SIGNATURES_KF_REMOVAL.items()) + list(SIGNATURES_MAP_FUSION.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
